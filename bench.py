@@ -15,6 +15,12 @@ micro-steps of 8 sequences as 2 pipelined chains of 16 (``micro_step_fusion``; t
 loss is still normalised per micro-step, so the gradient is the same GA average) --
 reported in the JSON ``config``.  Data: synthetic random token ids
 (no datasets offline); weights: random init of the real architecture.
+
+A plain run sets up, warms up, times the K steps and prints the JSON line.  Weights,
+token ids and dropout streams are seeded, so the same arguments give the same inputs in
+every run; ``--dump-outputs DIR`` writes what the last timed step returned as
+``DIR/<name>.npy`` (``dump_outputs``), to compare two builds output for output.
+``--full`` adds what the headline figure does not need (the GEMM planner's report).
 """
 from __future__ import annotations
 
@@ -31,6 +37,28 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 BASELINE_TPS = {1: 12500.0, 2: 24100.0, 4: 46800.0}  # BASELINE.md (README.md:191-197 of the reference)
+DUMP_PARAM_SAMPLE = 8 * 1024 * 1024  # --dump-outputs: at most this many master weights (32 MB of float32)
+
+
+def dump_outputs(path, trainer, last):
+    """--dump-outputs: what the last timed ``train_step`` handed back to its caller, as
+    ``path/<name>.npy``: ``loss`` and ``grad_norm`` (float64 scalars) and ``params``
+    (float32), the flat fp32 master weights with that step's AdamW update applied (DDP:
+    the whole model; FSDP: this rank's shard).  Past DUMP_PARAM_SAMPLE values ``params``
+    is a sample of them: sorted positions drawn from a CPU generator seeded with a
+    constant, so two builds dump the same positions."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    flat = trainer.flat_params() if hasattr(trainer, "flat_params") else trainer.runtime.master_flat
+    flat = flat.detach().reshape(-1)
+    n = flat.numel()
+    if n > DUMP_PARAM_SAMPLE:
+        g = torch.Generator(device="cpu").manual_seed(20240229)
+        idx = torch.randint(0, n, (DUMP_PARAM_SAMPLE,), generator=g).sort().values
+        flat = flat[idx.to(flat.device)]
+    np.save(os.path.join(path, "params.npy"), flat.float().cpu().numpy())
+    np.save(os.path.join(path, "loss.npy"), np.asarray(float(last["loss"]), dtype=np.float64))
+    np.save(os.path.join(path, "grad_norm.npy"), np.asarray(float(trainer._last_norm), dtype=np.float64))
 
 
 def main():
@@ -77,7 +105,16 @@ def main():
                          "instantiated for IEEE half + dynamic loss scaling, fp32 = the reference/debug mode)")
     ap.add_argument("--dropout", type=float, default=None,
                     help="ablation only: override dropout/attention_dropout (reference config: 0.1)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (loss, gradient norm, "
+                         "the fp32 master weights after its update; a fixed seeded sample when they exceed "
+                         f"{DUMP_PARAM_SAMPLE:,} values) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the GEMM planner's report (every routed shape, "
+                         "its pick and the race timings) on stderr after the result line")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if os.environ.get("DLT_HANG_DUMP"):  # debugging aid: periodic Python stack dumps
         import faulthandler
         faulthandler.dump_traceback_later(float(os.environ["DLT_HANG_DUMP"]), repeat=True, file=sys.stderr)
@@ -161,6 +198,8 @@ def main():
     if trainer.distributed:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed, peak = float(t[0]), float(t[1])
+    if args.dump_outputs and trainer.is_main_process:
+        dump_outputs(args.dump_outputs, trainer, last)
     tokens = args.steps * B * args.seq_len * world
     tps = tokens / elapsed
     eng = getattr(getattr(trainer, "model", None), "engine", None)
@@ -192,7 +231,7 @@ def main():
             "vs_baseline_linear": None if overrides else round(tps / (12500.0 * world), 3),
         }
         print(json.dumps(out), flush=True)
-        if os.environ.get("DLT_GEMM_REPORT"):
+        if (args.full and dev.type == "cuda") or os.environ.get("DLT_GEMM_REPORT"):
             from distributed_llm_trainer_amd.ops import gemm as gemm_mod
             if gemm_mod.available():
                 print(gemm_mod.report(), file=sys.stderr)

@@ -56,6 +56,28 @@ def test_bench_single_process_contract():
     _check(out, 1, 2, 1)
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the last timed step's loss, gradient norm and master weights
+    as float .npy files; same arguments -> same inputs, so two runs agree.  --full keeps
+    the one-line contract."""
+    import numpy as np
+    runs = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        out = _run([sys.executable, "bench.py", "--gpus", "1"] + ARGS + ["--dump-outputs", str(d)] + extra)
+        _check(out, 1, 2, 1)
+        files = sorted(p.name for p in d.iterdir())
+        assert files == ["grad_norm.npy", "loss.npy", "params.npy"]
+        arrs = {f[:-4]: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 1024 * 1024
+        assert arrs["params"].ndim == 1 and arrs["params"].size > 384 * 64 and np.isfinite(arrs["params"]).all()
+        assert float(arrs["loss"]) == pytest.approx(out["final_loss"], abs=1e-4)
+        runs.append(arrs)
+    for f in runs[0]:
+        np.testing.assert_allclose(runs[0][f], runs[1][f], rtol=1e-5, atol=1e-6)
+
+
 def test_bench_torchrun_two_ranks_contract():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2"] + ARGS
