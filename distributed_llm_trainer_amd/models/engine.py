@@ -579,8 +579,30 @@ class GPTEngine:
         """Returns (loss or None, logits or None, state for backward or None)."""
         return _drain(self._forward_gen(ids, targets, train, recompute, return_logits, need_backward))
 
+    def eval_loss(self, ids: torch.Tensor, targets: torch.Tensor):
+        """Loss-only evaluation forward: (sum of the per-row losses, number of valid
+        targets) as device tensors.  Runs as ``train=False`` (no dropout), keeps no caches
+        and does not advance ``micro_counter``.  The head is the logits-free
+        ``lmhead_loss`` when it takes the shape and the activations are 16-bit, else the
+        lm_head GEMM + ``cross_entropy_fwd_bwd`` (fp32, padded vocabularies that are no
+        multiple of 128); ``DLT_EVAL_HEAD=unfused`` forces the latter (A/B knob)."""
+        loss_sum, n_valid, _ = _drain(self._forward_gen(ids, targets, False, need_backward=False, loss_only=True))
+        return loss_sum, n_valid
+
+    def _eval_row_loss(self, nf, w, targets, V: int) -> torch.Tensor:
+        """Per-row loss of the evaluation head (see :meth:`eval_loss`)."""
+        ops = self.ops
+        takes = nf.dtype in (torch.bfloat16, torch.float16) or getattr(ops, "backend", "") == "reference"
+        if (os.environ.get("DLT_EVAL_HEAD", "fused") != "unfused" and takes and hasattr(ops, "lmhead_loss")
+                and ops.lmhead_loss_fits(nf.shape[0], w.shape[0], nf.shape[1])):
+            out = ops.lmhead_loss(nf, w, targets, V)
+            if out is not None:
+                return out[0]
+        lg = self.gemm.linear(nf, w)
+        return ops.cross_entropy_fwd_bwd(lg, targets, V, (targets != -100).sum(), 1.0)
+
     def _forward_gen(self, ids, targets, train, recompute=False, return_logits=False, need_backward=None,
-                     acc=None, head_dloss=None):
+                     acc=None, head_dloss=None, loss_only=False):
         """Generator form of :meth:`forward`: yields after every block so the window
         scheduler (:meth:`train_window`) can interleave it with another micro-step's
         backward; the return value is forward's tuple.  ``acc`` = (slot, n_slots,
@@ -623,6 +645,10 @@ class GPTEngine:
         st.d_last = None
         loss, logits = None, None
         V, Vp = self.cfg.vocab_size, hw.lm_head.shape[0]
+        if loss_only:  # eval_loss: (loss sum, valid targets), nothing kept
+            row_loss = self._eval_row_loss(nf, hw.lm_head, targets, V)
+            prov.post_forward("head")
+            return row_loss.sum(), (targets != -100).sum(), None
         if targets is not None:
             rows = B * S
             nseg = self.loss_segments if (train and B % self.loss_segments == 0) else 1

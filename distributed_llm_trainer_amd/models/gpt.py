@@ -238,6 +238,33 @@ class GPT(nn.Module):
                                       return_logits=True)
         return logits, loss
 
+    # ------------------------------------------------------------ evaluation
+    @torch.no_grad()
+    def eval_loss_sum(self, input_ids: torch.Tensor, labels: Optional[torch.Tensor] = None):
+        """(sum of the token losses, number of predicted tokens) of a held-out batch, without
+        dropout whatever the module's mode; labels default to the inputs and are shifted as
+        in :meth:`forward`.  Engine path: ``GPTEngine.eval_loss`` (no [B, S, V] logits);
+        eager path: the same value from :meth:`forward`'s logits."""
+        labels = input_ids if labels is None else labels
+        if self.engine is not None:
+            from .engine import shift_targets
+            return self.engine.eval_loss(input_ids, shift_targets(labels))
+        was_training = self.training
+        self.eval()
+        try:
+            logits, _ = self(input_ids)
+        finally:
+            self.train(was_training)
+        tgt = labels[..., 1:].reshape(-1)
+        loss_sum = F.cross_entropy(logits[..., :-1, :].reshape(-1, self.config.vocab_size).float(), tgt,
+                                   reduction="sum")
+        return loss_sum, (tgt != -100).sum()
+
+    def eval_loss(self, input_ids: torch.Tensor, labels: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Mean next-token loss of a held-out batch (see :meth:`eval_loss_sum`)."""
+        loss_sum, n = self.eval_loss_sum(input_ids, labels)
+        return loss_sum / n.clamp(min=1).to(loss_sum.dtype)
+
     # ------------------------------------------------------------ generation
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, max_new_tokens: int = 100,

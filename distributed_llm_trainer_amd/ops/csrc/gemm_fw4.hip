@@ -34,6 +34,14 @@
 //     s = silu(gate) * up computed from the accumulators -- each wave's 128 B rows are 64
 //     gate rows and the 64 up rows of the same intermediate indices, a row_ror:8 DPP move
 //     pairs them in one lane, k_swiglu_fwd's arithmetic (same bits); gu keeps [gate | up];
+//   * loss epilogue (template flag LSE, dlt_lmhead_loss: the evaluation lm_head): no C at
+//     all.  The accumulators are rounded to the activation format like stored logits; per
+//     output row (m-tile t, register r) the lane's 8 columns, masked to -inf from column V
+//     on, reduce to a (max, sum exp) pair over the 16 lanes of the row group (row_ror DPP),
+//     and the pair of slot 2 tn + wn goes to part[slot][row] (lane v of a group keeps the
+//     pairs of (t & 3, r) = (v >> 2, v & 3): two 512-byte stores per wave).  The lane that
+//     holds column target[row] stores that logit to tgt_logit[row] (one owner per row in
+//     the whole grid).  k_lse_combine merges a row's slots in slot order;
 //   * LDS images: A rows of 128 bytes, 16-byte chunk c of row r at c ^ (r & 7) (a 16-lane
 //     group of ds_read_b128 covers all 64 banks); the DMA is lane-linear on the LDS side,
 //     so every swizzle lives in the per-lane source offsets;
@@ -101,17 +109,34 @@ __device__ __forceinline__ uint2 f4_pack(const floatx4_t& v) {
   else return __builtin_bit_cast(uint2, __builtin_convertvector(v, f4_f16x4_t));
 }
 
+// row_ror:n move within each row of 16 lanes (CTRL = 0x120 + n)
+template <int CTRL>
+__device__ __forceinline__ float f4_dpp(float x) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
+}
+
+// extra kernel arguments of the loss epilogue (LSE); empty for the storing forms
+struct F4LseArgs {
+  const int64_t* targets;  // [M], ignore_index -100
+  float2* part;            // [2 * ceil(N / 256)][M] (max, sum exp) partials
+  float* tgt_logit;        // [M], written for rows with a real target only
+  int V;                   // columns >= V are padding
+};
+struct F4NoArgs {};
+
 struct F4Frags {
   bf16x8_t a[8], b[8];  // m-tiles / n-tiles of one 32-deep stage
 };
 
 }  // namespace
 
-template <int HK, int SCHED, int TT, bool SW>
+template <int HK, int SCHED, int TT, bool SW, bool LSE = false>
 __global__ __launch_bounds__(256, 1) void k_gemm_fw4(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B,
                                                      bf16_t* __restrict__ C, int M, int N, int K, int lda, int ldb,
-                                                     int ldc, int flags, bf16_t* __restrict__ S, int ldS) {
+                                                     int ldc, int flags, bf16_t* __restrict__ S, int ldS,
+                                                     std::conditional_t<LSE, F4LseArgs, F4NoArgs> X = {}) {
   static_assert(SCHED == 4 || SCHED == 5, "k_gemm_fw4: schedules 4 and 5");
+  static_assert(!LSE || (TT == 1 && !SW), "k_gemm_fw4: the loss epilogue takes one plain tile per workgroup");
   // SCHED 4: two stage buffers, B pieces padded (conflict-free reads); SCHED 5: the
   // five-slot ring, unpadded B (two-way bank conflicts on its reads)
   constexpr bool PAD = SCHED == 4, RING = SCHED == 5;
@@ -329,7 +354,53 @@ __global__ __launch_bounds__(256, 1) void k_gemm_fw4(const bf16_t* __restrict__ 
     // 256 contiguous bytes: one 16-byte store per (m-tile, r), 4 rows per instruction, no LDS
     const auto rs =
         __builtin_amdgcn_make_buffer_rsrc(C + (size_t)(cur.m0 + wm * 128) * ldc, 0, 128 * ldc * 2, 0x00020000);
-    if constexpr (swiglu) {
+    if constexpr (LSE) {
+      // LSE: no C.  Columns n0 + 128 wn + 8 v + u of row (t, r); a wave whose columns all lie
+      // past V (the idle half of a ragged last tile, whose clamped B rows re-read row N - 1)
+      // masks everything and writes the neutral pair (-inf, 0).
+      const int colb = cur.n0 + wn * 128 + 8 * l16;
+      const int rowb = cur.m0 + wm * 128;
+      const float L2E = 1.44269504088896340736f;
+      float km[2] = {-INFINITY, -INFINITY}, ks[2] = {0.f, 0.f};
+#pragma unroll
+      for (int t = 0; t < 8; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = rowb + 16 * t + 4 * q + r;
+          const int64_t tgt = X.targets[row];
+          DLT_DASSERT(tgt == -100 || (tgt >= 0 && tgt < X.V));  // ignore_index or a real token
+          float v[8], mx = -INFINITY, tl = 0.f;
+          const int64_t d = tgt - colb;
+#pragma unroll
+          for (int u = 0; u < 8; ++u) {
+            const float lv = h2f<HK>(f2h<HK>(acc[u][t][r]));  // the logit as it would be stored
+            tl = (d == u) ? lv : tl;
+            v[u] = (colb + u < X.V) ? lv : -INFINITY;
+            mx = fmaxf(mx, v[u]);
+          }
+          if (tgt < X.V && d >= 0 && d < 8) X.tgt_logit[row] = tl;
+          mx = fmaxf(mx, f4_dpp<0x128>(mx));
+          mx = fmaxf(mx, f4_dpp<0x124>(mx));
+          mx = fmaxf(mx, f4_dpp<0x122>(mx));
+          mx = fmaxf(mx, f4_dpp<0x121>(mx));
+          // an all-masked group: exp2(-inf - -inf) would be NaN; against 0 every term is 0
+          const float nm2 = mx == -INFINITY ? 0.f : -mx * L2E;
+          float sm = 0.f;
+#pragma unroll
+          for (int u = 0; u < 8; ++u) sm += __builtin_amdgcn_exp2f(fmaf(v[u], L2E, nm2));
+          sm += f4_dpp<0x128>(sm);
+          sm += f4_dpp<0x124>(sm);
+          sm += f4_dpp<0x122>(sm);
+          sm += f4_dpp<0x121>(sm);
+          if (l16 == 4 * (t & 3) + r) {
+            km[t >> 2] = mx;
+            ks[t >> 2] = sm;
+          }
+        }
+      float2* prow = X.part + (size_t)(2 * cur.tn + wn) * M + rowb + 4 * q + (l16 & 3);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) prow[16 * ((l16 >> 2) + 4 * h)] = make_float2(km[h], ks[h]);
+    } else if constexpr (swiglu) {
       // SWIGLU: lanes v = l & 15 < 8 hold gate indices jb + 8 v + u, lanes v + 8 the up values
       // of the same indices; after a row_ror:8 exchange each lane of the pair has both and
       // computes s = silu(g) * u -- k_swiglu_fwd's arithmetic on the bf16-rounded g and u,
@@ -436,5 +507,76 @@ DLT_API int dlt_gemm_fw4(const bf16_t* A, const bf16_t* B, bf16_t* C, int M, int
   else if (two) F4_LAUNCH(4, 2, false);
   else F4_LAUNCH(4, 1, false);
 #undef F4_LAUNCH
+  DLT_CHECK_LAUNCH();
+}
+
+// Merge of the loss epilogue's partials: one wave per row, lane l takes slots l, l + 64, ...
+// in order, then a fixed butterfly over the lanes -- the same association every call, so the
+// result is bitwise reproducible.  lse[m] = log sum_{j < V} exp(l[m, j]); row_loss[m] =
+// lse[m] - l[m, target[m]], 0 for ignore_index rows (their tgt_logit is never read).
+__global__ __launch_bounds__(256) void k_lse_combine(const float2* __restrict__ part, const float* __restrict__ tgt_logit,
+                                                     const int64_t* __restrict__ targets, float* __restrict__ row_loss,
+                                                     float* __restrict__ lse_out, int M, int nslot, int V) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= M) return;
+  const float L2E = 1.44269504088896340736f;
+  auto merge = [&](float& mx, float& sm, float om, float os) {
+    const float nm = fmaxf(mx, om);
+    sm = (mx == -INFINITY ? 0.f : sm * __builtin_amdgcn_exp2f((mx - nm) * L2E)) +
+         (om == -INFINITY ? 0.f : os * __builtin_amdgcn_exp2f((om - nm) * L2E));
+    mx = nm;
+  };
+  float mx = -INFINITY, sm = 0.f;
+  for (int s = lane; s < nslot; s += 64) {
+    const float2 p = part[(size_t)s * M + row];
+    merge(mx, sm, p.x, p.y);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float om = __shfl_xor(mx, o, 64), os = __shfl_xor(sm, o, 64);
+    merge(mx, sm, om, os);
+  }
+  if (lane == 0) {
+    const float lse = mx + __logf(sm);
+    const int64_t tgt = targets[row];
+    lse_out[row] = lse;
+    row_loss[row] = (tgt >= 0 && tgt < V) ? lse - tgt_logit[row] : 0.f;
+  }
+}
+
+// floats of scratch dlt_lmhead_loss needs: 2 * ceil(Vp / 256) (max, sum exp) pairs per row
+DLT_API long dlt_lmhead_loss_scratch(int M, int Vp) {
+  if (M <= 0 || Vp <= 0) return 0;
+  return 2L * 2L * ((Vp + F4_BN - 1) / F4_BN) * M;
+}
+
+// row_loss[m] = logsumexp_{j < V}(l[m, j]) - l[m, targets[m]] (0 for ignore_index rows) and
+// lse[m], with l = A[M, K] . W[Vp, K]^T rounded to the activation format, without storing l:
+// k_gemm_fw4's loss epilogue, then k_lse_combine.  flags: the tile-order (2, 2048) and schedule
+// (16 | 128) bits of dlt_gemm_fw4; its store-policy and epilogue bits are ignored.  -1 for
+// shapes the kernel does not take.
+DLT_API int dlt_lmhead_loss(const bf16_t* A, const bf16_t* W, const int64_t* targets, float* row_loss, float* lse,
+                            float* scratch, float* tgt_logit, int M, int Vp, int V, int K, int lda, int ldb, int flags,
+                            int hk, hipStream_t st) {
+  if (M <= 0 || Vp <= 0 || K <= 0 || V <= 0 || V > Vp || M % F4_BM || Vp % 128 || K % F4_BK || K < 2 * F4_BK ||
+      lda % 8 || ldb % 8 || lda < K || ldb < K)
+    return -1;
+  const int sched_bits = flags & (16 | 128);
+  if (sched_bits == 16 || sched_bits == 128) return -1;
+  const int ntn = (Vp + F4_BN - 1) / F4_BN;
+  const long tiles = (long)(M / F4_BM) * ntn;
+  if (tiles > 0x7fffffff || 256L * lda * 2 > 0xffffffffL || 256L * ldb * 2 > 0xffffffffL) return -1;
+  flags &= 2 | 2048;
+  const F4LseArgs x{targets, reinterpret_cast<float2*>(scratch), tgt_logit, V};
+#define F4_LSE_LAUNCH(SC)                                                                                        \
+  DLT_HK_DISPATCH(hk, k_gemm_fw4<HKC, SC, 1, false, true><<<(int)tiles, 256, 0, st>>>(A, W, nullptr, M, Vp, K, lda, ldb, \
+                                                                                      0, flags, nullptr, 0, x))
+  if (sched_bits) F4_LSE_LAUNCH(5);
+  else F4_LSE_LAUNCH(4);
+#undef F4_LSE_LAUNCH
+  const int rc = (int)hipGetLastError();
+  if (rc) return rc;
+  k_lse_combine<<<M / 4, 256, 0, st>>>(reinterpret_cast<const float2*>(scratch), tgt_logit, targets, row_loss, lse, M,
+                                       2 * ntn, V);
   DLT_CHECK_LAUNCH();
 }

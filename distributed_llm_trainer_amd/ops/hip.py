@@ -66,6 +66,8 @@ _SIGS = {
                          c_void_p],
     "dlt_gemm_fw4": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                      c_int, c_void_p],
+    "dlt_lmhead_loss": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                        c_int, c_int, c_int, c_int, c_void_p],
     "dlt_gemm_bf16_qkv_rope": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                c_void_p],
     "dlt_gemm_bf16_gu_swiglu": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
@@ -118,6 +120,8 @@ def lib():
             fn.restype = c_int
         L.dlt_gemm_wgrad_sk_scratch.argtypes = [c_int, c_int, c_int, c_int]
         L.dlt_gemm_wgrad_sk_scratch.restype = ctypes.c_long
+        L.dlt_lmhead_loss_scratch.argtypes = [c_int, c_int]
+        L.dlt_lmhead_loss_scratch.restype = ctypes.c_long
         _LIB = L
     return _LIB
 
@@ -920,6 +924,42 @@ def gemm_fw4(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = Non
         return None  # a launch variant the shape does not take (two tiles per workgroup: tiles % 16)
     _chk(rc, "gemm_fw4")
     return c
+
+
+def lmhead_loss_fits(M: int, Vp: int, K: int) -> bool:
+    """Shapes the logits-free lm_head loss (k_gemm_fw4's loss epilogue) tiles."""
+    return gemm_fw4_fits(M, Vp, K)
+
+
+def lmhead_loss(nf: torch.Tensor, w: torch.Tensor, targets: torch.Tensor, V: int, flags: Optional[int] = None):
+    """(row_loss [M], lse [M]) fp32 of the lm_head without its logits: with
+    l = nf[M, K] @ w[Vp, K]^T rounded to the activation format (bf16 or fp16), lse[m] =
+    logsumexp over the columns j < V and row_loss[m] = lse[m] - l[m, targets[m]], 0 where
+    the target is ignore_index (-100).  k_gemm_fw4 reduces every 128-column half tile to a
+    (max, sum exp) pair per row, k_lse_combine merges them in fixed order (bitwise
+    reproducible).  Returns None (nothing launched) when the shape does not tile
+    (M % 256, Vp % 128, K % 64, K < 128)."""
+    M, K = nf.shape
+    Vp = w.shape[0]
+    if not lmhead_loss_fits(M, Vp, K) or w.shape[1] != K:
+        return None
+    if not 0 < V <= Vp:
+        raise ValueError(f"lmhead_loss: vocab {V} outside (0, {Vp}]")
+    hk = _req_act(nf, nf.dtype, "lmhead_loss.nf")
+    _req(w, nf.dtype, "lmhead_loss.w")
+    targets = targets.contiguous()
+    if not targets.is_cuda or targets.dtype != torch.int64 or targets.numel() != M:
+        raise ValueError("lmhead_loss.targets must be a GPU int64 [M]")
+    n = int(lib().dlt_lmhead_loss_scratch(M, Vp))
+    scratch = torch.empty(n, dtype=torch.float32, device=nf.device)
+    out = torch.empty(3, M, dtype=torch.float32, device=nf.device)  # row_loss, lse, target logit
+    fl = _FW4_FLAGS if flags is None else flags
+    rc = lib().dlt_lmhead_loss(_p(nf), _p(w), _p(targets), _p(out[0]), _p(out[1]), _p(scratch), _p(out[2]), M, Vp,
+                               int(V), K, K, K, fl, hk, _stream())
+    if rc == -1:
+        return None
+    _chk(rc, "lmhead_loss")
+    return out[0], out[1]
 
 
 def gemm_fw4_swiglu_fits(M: int, I2: int, K: int) -> bool:

@@ -280,6 +280,30 @@ def cross_entropy_fwd_bwd(logits: torch.Tensor, targets: torch.Tensor, vocab: in
     return loss
 
 
+def lmhead_loss_fits(M: int, Vp: int, K: int) -> bool:
+    return M > 0 and Vp > 0 and K > 0
+
+
+def lmhead_loss(nf: torch.Tensor, w: torch.Tensor, targets: torch.Tensor, V: int, block_rows: int = 1024):
+    """(row_loss [M], lse [M]) fp32 of the lm_head without keeping its logits: the product
+    nf[M, K] @ w[Vp, K]^T in fp32, rounded to the activation dtype (as stored logits are),
+    then an fp32 log-sum-exp over the columns < V; row_loss = lse - logit[target], 0 for
+    IGNORE_INDEX rows.  Row blocks bound the fp32 temporaries to [block_rows, V]."""
+    M = nf.shape[0]
+    wf = w[:V].float()
+    loss = torch.empty(M, dtype=torch.float32, device=nf.device)
+    lse = torch.empty(M, dtype=torch.float32, device=nf.device)
+    for a in range(0, M, block_rows):
+        b = min(M, a + block_rows)
+        lf = (nf[a:b].float() @ wf.t()).to(nf.dtype).float()
+        t = targets[a:b]
+        valid = t != IGNORE_INDEX
+        lse[a:b] = torch.logsumexp(lf, dim=-1)
+        picked = lf.gather(1, torch.where(valid, t, torch.zeros_like(t)).unsqueeze(1)).squeeze(1)
+        loss[a:b] = torch.where(valid, lse[a:b] - picked, torch.zeros_like(picked))
+    return loss, lse
+
+
 # -------------------------------------------------------------- optimizer
 def adamw_step(param: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor,
                shadow: Optional[torch.Tensor], lr: float, beta1: float, beta2: float, eps: float,

@@ -3,9 +3,11 @@ selection, seeding, LR schedule, memory stats and the YAML/CLI config merge."""
 from __future__ import annotations
 
 import datetime
+import json
 import math
 import os
 import random
+import time
 from typing import Optional
 
 import numpy as np
@@ -125,6 +127,84 @@ def global_mean_loss(total: torch.Tensor, world: int) -> float:
     t = total.detach().reshape(1).float().clone()
     dist.all_reduce(t)
     return float(t.item()) / world
+
+
+EVAL_SEED_OFFSET = 1_000_003  # the dummy held-out stream's seed is the training seed + this
+
+
+class HeldOutBatches:
+    """The first batches of a held-out loader, the same ones at every evaluation: the
+    native loader is rewound (``seek(0)``), any other loader is read once -- with the
+    global RNG forked, so a shuffling sampler draws nothing from the training run's
+    stream -- and its batches are kept on the host."""
+
+    def __init__(self, loader):
+        self.loader = loader
+        self._kept = []
+
+    def take(self, n: int):
+        if hasattr(self.loader, "seek"):
+            self.loader.seek(0)
+            it = iter(self.loader)
+            for _ in range(n):
+                yield unwrap_batch(next(it))
+            return
+        if len(self._kept) < n:
+            with torch.random.fork_rng(devices=[]):
+                it = iter(self.loader)
+                try:
+                    self._kept = [unwrap_batch(next(it)).clone() for _ in range(n)]
+                except StopIteration:
+                    raise ValueError(f"the held-out loader has fewer than {n} batches") from None
+                del it
+        yield from self._kept[:n]
+
+
+@torch.no_grad()
+def evaluate_held_out(model, held_out: HeldOutBatches, n_batches: int, device, distributed: bool) -> dict:
+    """Token-weighted mean held-out loss over ``n_batches`` batches per rank.  Every rank
+    runs the same number of forwards (FSDP gathers are collectives); the loss sum and the
+    token count are each all-reduced, then divided.  Reads the model only."""
+    if torch.device(device).type == "cuda":
+        torch.cuda.synchronize(device)  # eval_s is the evaluation's time, not the queued training work's
+    t0 = time.time()
+    acc = torch.zeros(2, dtype=torch.float64, device=device)
+    for ids in held_out.take(int(n_batches)):
+        loss_sum, n = model.eval_loss_sum(ids.to(device, non_blocking=True))
+        acc[0] += loss_sum.double()
+        acc[1] += n.double()
+    if distributed and dist.is_initialized() and dist.get_world_size() > 1:
+        dist.all_reduce(acc)
+    loss_sum, tokens = acc.tolist()
+    val_loss = loss_sum / max(tokens, 1.0)
+    return {"val_loss": val_loss, "val_ppl": math.exp(min(val_loss, 700.0)), "eval_tokens": int(tokens),
+            "eval_s": time.time() - t0}
+
+
+def held_out_of(cache: dict, loader) -> HeldOutBatches:
+    """``loader`` as HeldOutBatches, one per loader (so its kept batches survive between calls)."""
+    if isinstance(loader, HeldOutBatches):
+        return loader
+    if id(loader) not in cache:
+        cache[id(loader)] = HeldOutBatches(loader)
+    return cache[id(loader)]
+
+
+def log_evaluation(step: int, res: dict, metrics_f=None) -> None:
+    """The main process's evaluation output: one log line, one metrics JSONL record."""
+    print(f"Step {step:6d} | Val loss: {res['val_loss']:.4f} | Val ppl: {res['val_ppl']:.2f}", flush=True)
+    if metrics_f:
+        metrics_f.write(json.dumps({"step": step, **res}) + "\n")
+        metrics_f.flush()
+
+
+def add_eval_args(p) -> None:
+    p.add_argument("--eval_interval", type=int, default=None,
+                   help="evaluate every this many steps (and once after the last) when --eval_batches > 0")
+    p.add_argument("--eval_batches", type=int, default=None,
+                   help="held-out batches per rank and evaluation; 0 (default) = no evaluation")
+    p.add_argument("--eval_data_path", type=str, default=None,
+                   help="held-out data for tinystories / openwebtext (same formats as --data_path)")
 
 
 def unwrap_batch(batch):

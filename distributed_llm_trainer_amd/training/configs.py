@@ -66,6 +66,9 @@ class TrainingConfig:
     # train_step returns).  Readers outside a forward flush it (save, state_dict, eval):
     # DistributedTrainer.flush_optimizer.  See training/optim.py LazyStep.
     lazy_optimizer: str = "inline"
+    # held-out evaluation every eval_interval steps and once after the last step, over this
+    # many batches of batch_size sequences per rank; 0 = off (--eval_batches)
+    eval_batches: int = 0
 
 
 @dataclass
@@ -93,6 +96,7 @@ class FSDPTrainingConfig:
     # F micro-steps per executed chain, as in TrainingConfig (0 = auto, 1 = off); the
     # per-micro-step reduce-scatter (Q15 parity) then runs once per chain -- the same sum
     micro_step_fusion: int = 0
+    eval_batches: int = 0              # held-out batches per rank and evaluation, 0 = off (as TrainingConfig)
 
 
 @dataclass

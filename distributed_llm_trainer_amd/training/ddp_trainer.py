@@ -40,7 +40,7 @@ from ..parallel.flat import FlatParamStore
 from ..utils import checkpoint as ckpt
 from ..utils import debug as dbg
 from ..utils.profiling import Profiler, range_push, range_pop
-from .common import cosine_lr, gemm_plan_hook, global_mean_loss, memory_stats, micro_step_fusion, seed_all, select_device, setup_distributed, unwrap_batch
+from .common import EVAL_SEED_OFFSET, HeldOutBatches, add_eval_args, cosine_lr, evaluate_held_out, gemm_plan_hook, global_mean_loss, held_out_of, log_evaluation, memory_stats, micro_step_fusion, seed_all, select_device, setup_distributed, unwrap_batch
 from .configs import TrainingConfig
 from .optim import flat_store_optimizer
 
@@ -298,6 +298,17 @@ class DistributedTrainer:
         self.flush_optimizer()
         return self.store.flat
 
+    # ------------------------------------------------------------- evaluation
+    def evaluate(self, loader, n_batches: int) -> dict:
+        """Held-out loss over the first ``n_batches`` batches of ``loader`` on every rank:
+        ``{"val_loss", "val_ppl", "eval_tokens", "eval_s"}``, the token-weighted mean over
+        all ranks.  A recorded (lazy) optimizer step is applied first, so the forward reads
+        the current weights; nothing the training run depends on changes (parameters,
+        gradients, dropout counters, step and token counts)."""
+        self.flush_optimizer()
+        held = held_out_of(self.__dict__.setdefault("_held_out", {}), loader)
+        return evaluate_held_out(self.model, held, n_batches, self.device, self.distributed)
+
     # ------------------------------------------------------------ checkpoints
     def save_checkpoint(self, path: str):
         self.flush_optimizer()
@@ -387,7 +398,27 @@ def build_parser() -> argparse.ArgumentParser:
                    help="no weight gradient deferred to the end of the accumulation window: every micro-step "
                         "chain runs its own (no [GA*M, N] slot buffers, no window-wide dlogits; lm_head in row "
                         "chunks): ~56 %% of the default peak memory at -3 %% tok/s")
+    add_eval_args(p)
     return p
+
+
+def make_dataloader(args, tc, model_config, trainer, path, batch_size: int, seed: int):
+    """The training loader, or (``path`` = --eval_data_path, another seed) the held-out one."""
+    seq_len = model_config.max_seq_len
+    if args.dataset in ("tinystories", "openwebtext"):
+        from ..data import create_openwebtext_dataloader, create_tinystories_dataloader
+        fn = create_tinystories_dataloader if args.dataset == "tinystories" else create_openwebtext_dataloader
+        return fn(path=path, batch_size=batch_size, seq_len=seq_len, distributed=trainer.distributed,
+                  rank=trainer.rank, world_size=trainer.world_size, tokenizer_name=args.tokenizer,
+                  max_tokens=args.max_tokens, streaming=args.streaming,
+                  cache_max_tokens=args.cache_max_tokens, num_workers=0 if args.streaming else 2,
+                  seed=seed, device=trainer.device)
+    from ..data import create_dummy_dataloader
+    return create_dummy_dataloader(batch_size=batch_size, seq_len=seq_len,
+                                   vocab_size=model_config.vocab_size, distributed=trainer.distributed,
+                                   rank=trainer.rank, world_size=trainer.world_size,
+                                   num_batches=int(os.environ.get("DLT_DUMMY_BATCHES", "64")),
+                                   seed=seed, device=trainer.device)
 
 
 def main(argv=None):
@@ -420,6 +451,15 @@ def main(argv=None):
         tc.defer_roles = LEAN_DEFER_ROLES
     if args.memory_first:
         tc.memory_first = True
+    for k in ("eval_interval", "eval_batches"):
+        if getattr(args, k) is not None:
+            setattr(tc, k, getattr(args, k))
+    if tc.eval_batches > 0:
+        if tc.eval_interval <= 0:
+            raise ValueError("--eval_batches needs an --eval_interval > 0")
+        if args.dataset in ("tinystories", "openwebtext") and not args.eval_data_path:
+            raise ValueError(f"--eval_batches {tc.eval_batches} with the {args.dataset} dataset requires "
+                             "--eval_data_path (held-out data)")
 
     trainer = DistributedTrainer(model_config, tc)
     if tc.resume_from:
@@ -427,23 +467,15 @@ def main(argv=None):
 
     loader_bs = tc.batch_size * tc.gradient_accumulation_steps
     seq_len = model_config.max_seq_len
-    if args.dataset in ("tinystories", "openwebtext"):
-        if args.data_path is None:
-            raise ValueError(f"{args.dataset} dataset requires --data_path")
-        from ..data import create_openwebtext_dataloader, create_tinystories_dataloader
-        fn = create_tinystories_dataloader if args.dataset == "tinystories" else create_openwebtext_dataloader
-        dataloader = fn(path=args.data_path, batch_size=loader_bs, seq_len=seq_len, distributed=trainer.distributed,
-                        rank=trainer.rank, world_size=trainer.world_size, tokenizer_name=args.tokenizer,
-                        max_tokens=args.max_tokens, streaming=args.streaming,
-                        cache_max_tokens=args.cache_max_tokens, num_workers=0 if args.streaming else 2,
-                        seed=tc.seed, device=trainer.device)
-    else:
-        from ..data import create_dummy_dataloader
-        dataloader = create_dummy_dataloader(batch_size=loader_bs, seq_len=seq_len,
-                                             vocab_size=model_config.vocab_size, distributed=trainer.distributed,
-                                             rank=trainer.rank, world_size=trainer.world_size,
-                                             num_batches=int(os.environ.get("DLT_DUMMY_BATCHES", "64")),
-                                             seed=tc.seed, device=trainer.device)
+    if args.dataset in ("tinystories", "openwebtext") and args.data_path is None:
+        raise ValueError(f"{args.dataset} dataset requires --data_path")
+    dataloader = make_dataloader(args, tc, model_config, trainer, args.data_path, loader_bs, tc.seed)
+    # held-out data: the dummy stream under another seed, or --eval_data_path through the
+    # same loader factory; rewound for every evaluation (HeldOutBatches)
+    held_out = None
+    if tc.eval_batches > 0:
+        held_out = HeldOutBatches(make_dataloader(args, tc, model_config, trainer, args.eval_data_path,
+                                                  tc.batch_size, tc.seed + EVAL_SEED_OFFSET))
     if hasattr(dataloader, "seek") and trainer.global_step:
         dataloader.seek(trainer.global_step)  # native loader: resume the exact batch stream
 
@@ -496,10 +528,20 @@ def main(argv=None):
             trainer.save_checkpoint(f"{tc.checkpoint_dir}/step_{step}.pt")
             if steady_t0 is not None:  # checkpoint I/O is not training throughput
                 steady_ckpt += time.time() - t_ck
+        if held_out is not None and step > 0 and step % tc.eval_interval == 0:
+            res = trainer.evaluate(held_out, tc.eval_batches)
+            if trainer.is_main_process:
+                log_evaluation(step, res, metrics_f)
+            if steady_t0 is not None:  # nor is evaluation
+                steady_ckpt += res["eval_s"]
     if trainer.device.type == "cuda":
         torch.cuda.synchronize(trainer.device)
     steady_t1 = time.time()
     prof.close()
+    if held_out is not None:  # once after the last step
+        res = trainer.evaluate(held_out, tc.eval_batches)
+        if trainer.is_main_process:
+            log_evaluation(trainer.global_step, res, metrics_f)
     if not args.no_final_save:
         trainer.save_checkpoint(f"{tc.checkpoint_dir}/final.pt")
     if trainer.distributed:

@@ -33,7 +33,8 @@ from ..parallel.fsdp import FSDPRuntime
 from ..utils import checkpoint as ckpt
 from ..utils import debug as dbg
 from ..utils.profiling import Profiler
-from .common import cosine_lr, gemm_plan_hook, global_mean_loss, memory_stats, micro_step_fusion, seed_all, select_device, setup_distributed, unwrap_batch
+from .common import (EVAL_SEED_OFFSET, HeldOutBatches, add_eval_args, cosine_lr, evaluate_held_out, gemm_plan_hook,
+                     global_mean_loss, held_out_of, log_evaluation, memory_stats, micro_step_fusion, seed_all, select_device, setup_distributed, unwrap_batch)
 from .configs import FSDPConfig, FSDPTrainingConfig
 from .optim import FlatAdamW
 
@@ -212,6 +213,18 @@ class FSDPTrainer:
         if sync_loss and self.distributed and self.world_size > 1:
             out["loss_global"] = global_mean_loss(total, self.world_size)
         return out
+
+    # ------------------------------------------------------------- evaluation
+    def evaluate(self, loader, n_batches: int) -> dict:
+        """Held-out loss over the first ``n_batches`` batches of ``loader`` on every rank (the
+        same count everywhere: the unit gathers are collectives): ``{"val_loss", "val_ppl",
+        "eval_tokens", "eval_s"}``, the token-weighted mean over all ranks.  Training state
+        (shards, gradients, dropout counters, step and token counts) is only read."""
+        flush = getattr(self.runtime, "flush_pending", None)
+        if flush is not None:  # a recorded optimizer step: the forward must read the current weights
+            flush()
+        held = held_out_of(self.__dict__.setdefault("_held_out", {}), loader)
+        return evaluate_held_out(self.model, held, n_batches, self.device, self.distributed)
 
     # ------------------------------------------------------------ checkpoints
     def _full_state(self, rank0_only: bool = False):
@@ -408,6 +421,7 @@ def build_parser():
     p.add_argument("--state_dict_type", choices=["full", "sharded"], default="full",
                    help="full: reference FULL_STATE_DICT file (rank-0 gather); sharded: per-rank shard "
                         "directory, no gather (resume with --resume_from DIR)")
+    add_eval_args(p)  # (--eval_data_path: this trainer reads the dummy stream only)
     return p
 
 
@@ -443,6 +457,11 @@ def main(argv=None):
         fc.reduce_dtype = args.reduce_dtype
     if args.seq_len:
         model_config.max_seq_len = args.seq_len
+    for k in ("eval_interval", "eval_batches"):
+        if getattr(args, k) is not None:
+            setattr(tc, k, getattr(args, k))
+    if tc.eval_batches > 0 and tc.eval_interval <= 0:
+        raise ValueError("--eval_batches needs an --eval_interval > 0")
 
     trainer = FSDPTrainer(model_config, tc, fc)
     if tc.resume_from:
@@ -455,6 +474,13 @@ def main(argv=None):
                                          device=trainer.device)
     if hasattr(dataloader, "seek") and trainer.global_step:
         dataloader.seek(trainer.global_step)
+    held_out = None
+    if tc.eval_batches > 0:  # the dummy stream under another seed, rewound for every evaluation
+        held_out = HeldOutBatches(create_dummy_dataloader(
+            batch_size=tc.batch_size, seq_len=model_config.max_seq_len, vocab_size=model_config.vocab_size,
+            distributed=trainer.distributed, rank=trainer.rank, world_size=trainer.world_size,
+            num_batches=int(os.environ.get("DLT_DUMMY_BATCHES", "64")), seed=tc.seed + EVAL_SEED_OFFSET,
+            device=trainer.device))
     if trainer.is_main_process:
         print("\n" + "=" * 60)
         print("Starting FSDP training...")
@@ -506,10 +532,20 @@ def main(argv=None):
             save(f"{tc.checkpoint_dir}/step_{step}")
             if steady_t0 is not None:  # checkpoint I/O is not training throughput
                 steady_ckpt += time.time() - t_ck
+        if held_out is not None and step > 0 and step % tc.eval_interval == 0:
+            res = trainer.evaluate(held_out, tc.eval_batches)
+            if trainer.is_main_process:
+                log_evaluation(step, res, metrics_f)
+            if steady_t0 is not None:  # nor is evaluation
+                steady_ckpt += res["eval_s"]
     if trainer.device.type == "cuda":
         torch.cuda.synchronize(trainer.device)
     steady_t1 = time.time()
     prof.close()
+    if held_out is not None:  # once after the last step
+        res = trainer.evaluate(held_out, tc.eval_batches)
+        if trainer.is_main_process:
+            log_evaluation(trainer.global_step, res, metrics_f)
     if not args.no_final_save:
         save(f"{tc.checkpoint_dir}/final")
     if trainer.is_main_process:
