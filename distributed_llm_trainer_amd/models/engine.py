@@ -1055,14 +1055,18 @@ class GPTEngine:
                     side.wait_event(ev)
                     side_ctx = torch.cuda.stream(side)
                     side_ctx.__enter__()
+                # the layer's deferred roles go out together: one grouped launch where the
+                # GEMM plan pins the group (HipGemm.wgrad_acc_group), else one GEMM each
+                grp = []
                 if dfl["down"]:
-                    _wgrad(gm, gr.wdown, full(i, "dd", H), full(i, "s", I))
+                    grp.append((gr.wdown, full(i, "dd", H), full(i, "s", I)))
                 if dfl["gu"]:
-                    _wgrad(gm, gr.wgu, full(i, "dgu", 2 * I), full(i, "n2", H))
+                    grp.append((gr.wgu, full(i, "dgu", 2 * I), full(i, "n2", H)))
                 if dfl["o"]:
-                    _wgrad(gm, gr.wo, full(i, "da", H), full(i, "o", H))
+                    grp.append((gr.wo, full(i, "da", H), full(i, "o", H)))
                 if dfl["qkv"]:
-                    _wgrad(gm, gr.wqkv, full(i, "dqkv", 3 * H), full(i, "n1", H))
+                    grp.append((gr.wqkv, full(i, "dqkv", 3 * H), full(i, "n1", H)))
+                _wgrad_group(gm, grp)
                 if self._ring:
                     ev = torch.cuda.Event()
                     ev.record()
@@ -1428,6 +1432,16 @@ def _wgrad(gm, dw: torch.Tensor, dy: torch.Tensor, x: torch.Tensor) -> None:
         gm.wgrad_acc(dw, dy, x)
 
 
+def _wgrad_group(gm, problems) -> None:
+    """The deferred weight gradients (dw, dy, x) a layer issues at one point: fp32
+    accumulators go to the backend together, anything else one by one."""
+    if len(problems) > 1 and all(dw.dtype == torch.float32 for dw, _, _ in problems):
+        gm.wgrad_acc_group(problems)
+    else:
+        for dw, dy, x in problems:
+            _wgrad(gm, dw, dy, x)
+
+
 class _TorchGemm:
     """Plain library GEMMs (hipBLASLt on ROCm via torch.matmul).
 
@@ -1481,6 +1495,10 @@ class _TorchGemm:
             except (RuntimeError, TypeError):
                 self._fp32_out_ok = False
         dw2.add_(torch.matmul(dy.t(), x))
+
+    def wgrad_acc_group(self, problems) -> None:
+        for dw, dy, x in problems:
+            self.wgrad_acc(dw, dy, x)
 
 
 class EngineFunction(torch.autograd.Function):

@@ -336,15 +336,12 @@ struct GwSk {
   }
 };
 
-template <int HK, int BN = 192>
-__global__ __launch_bounds__(512, 1) void k_gemm_wgrad_sk(const bf16_t* __restrict__ dY, const bf16_t* __restrict__ X,
-                                                          float* __restrict__ dW, float* __restrict__ part, int Nr,
-                                                          int Nc, int ldy, int ldx, GwSk sk) {
-  __shared__ __attribute__((aligned(16))) bf16_t lds[2 * GW_BUF];
-  const int ntc = Nc / BN;
-  const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-  const int c = q % ntc, g = (q / ntc) * 8 + xcd;
-  if (g >= sk.Gc) return;  // padding (uniform, before any barrier)
+// Share g of column tile c of one stream-K problem: its segments, one per row tile it
+// touches (shared by the single-problem and the grouped kernel, so both sum alike).
+template <int HK, int BN>
+__device__ __forceinline__ void gw_sk_share(bf16_t* lds, const bf16_t* __restrict__ dY, const bf16_t* __restrict__ X,
+                                            float* __restrict__ dW, float* __restrict__ part, int Nr, int Nc, int ldy,
+                                            int ldx, const GwSk& sk, int c, int g) {
   const int c0 = c * BN;
   const long e = sk.s_of(g + 1);
   long i = sk.s_of(g);
@@ -361,16 +358,71 @@ __global__ __launch_bounds__(512, 1) void k_gemm_wgrad_sk(const bf16_t* __restri
   }
 }
 
+template <int HK, int BN = 192>
+__global__ __launch_bounds__(512, 1) void k_gemm_wgrad_sk(const bf16_t* __restrict__ dY, const bf16_t* __restrict__ X,
+                                                          float* __restrict__ dW, float* __restrict__ part, int Nr,
+                                                          int Nc, int ldy, int ldx, GwSk sk) {
+  __shared__ __attribute__((aligned(16))) bf16_t lds[2 * GW_BUF];
+  const int ntc = Nc / BN;
+  const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
+  const int c = q % ntc, g = (q / ntc) * 8 + xcd;
+  if (g >= sk.Gc) return;  // padding (uniform, before any barrier)
+  gw_sk_share<HK, BN>(lds, dY, X, dW, part, Nr, Nc, ldy, ldx, sk, c, g);
+}
+
+// ---------------------------------------------------------------- grouped stream-K
+// The four projection weight gradients of a layer are issued at the same point, share T
+// and are each too small for the chip: one launch runs them all.  Every problem keeps its
+// own GwSk plan (its share count apportioned by the caller from its tile count), so a
+// problem's result is bit-identical to dlt_gemm_wgrad_sk with that share count; only the
+// workgroup -> (problem, column tile, share) map differs.  It is a host-built table
+// (ops/hip.py wgrad_group_table): the ntc column tiles of one share sit on one XCD (ids
+// equal mod 8 -- they read the same dY rows), and the XCDs get equal numbers of working
+// workgroups, which the padded id map of the single-problem kernel cannot do for share
+// counts such as 4 or 12.  Padding entries are negative.  Slots of problem p live at
+// part + part_off; k_wgrad_grp_fix sums the split tiles of every problem in one launch.
+constexpr int GW_GRP_MAX = 8;
+struct GwGrpProb {
+  const bf16_t* dY;
+  const bf16_t* X;
+  float* dW;
+  long part_off;  // floats
+  int Nr, Nc, ldy, ldx;
+  int tile0;  // first tile of this problem in the group's (row tile, column tile) list
+  GwSk sk;
+};
+struct GwGrp {
+  GwGrpProb p[GW_GRP_MAX];
+  int n;
+};
+
+template <int HK, int BN = 192>
+__global__ __launch_bounds__(512, 1) void k_gemm_wgrad_grp(GwGrp grp, const int2* __restrict__ table,
+                                                           float* __restrict__ part) {
+  __shared__ __attribute__((aligned(16))) bf16_t lds[2 * GW_BUF];
+  const int2 ent = table[blockIdx.x];  // x: problem << 24 | column tile, y: share
+  if (ent.x < 0) return;               // padding (uniform, before any barrier)
+  const int pi = ent.x >> 24, c = ent.x & 0xffffff, g = ent.y;
+  if (pi >= grp.n) return;
+  // static indices only: the descriptors stay in the kernel-argument segment
+  GwGrpProb d = grp.p[0];
+#pragma unroll
+  for (int q = 1; q < GW_GRP_MAX; ++q)
+    if (q == pi) d = grp.p[q];
+  // an entry outside its problem's plan would address outside dW / part: refuse it
+  if (c >= d.Nc / BN || g < 0 || g >= d.sk.Gc) return;
+  gw_sk_share<HK, BN>(lds, d.dY, d.X, d.dW, part + d.part_off, d.Nr, d.Nc, d.ldy, d.ldx, d.sk, c, g);
+}
+
 // dW tile (rt, c) += sum over the shares g_lo..g_hi that split it of their slots, in
-// increasing g.  Grid: (GW_FIX_SPLIT, tiles); each block sums 1/GW_FIX_SPLIT of the tile.
+// increasing g.  Each block sums 1/GW_FIX_SPLIT of the tile.
 // The slot index of every share is computed once per block (64-bit divisions) into LDS.
 constexpr int GW_FIX_SPLIT = 48;
-template <int BN = 192>
-__global__ __launch_bounds__(256) void k_wgrad_sk_fix(const float* __restrict__ part, float* __restrict__ dW, int Nr,
-                                                      int Nc, GwSk sk) {
-  __shared__ int jt[256];
+template <int BN>
+__device__ __forceinline__ void gw_sk_fix_tile(int* jt, const float* __restrict__ part, float* __restrict__ dW, int Nr,
+                                               int Nc, const GwSk& sk, int tile) {
   const int ntc = Nc / BN;
-  const int tile = blockIdx.y, rt = tile / ntc, c = tile - rt * ntc;
+  const int rt = tile / ntc, c = tile - rt * ntc;
   const long i0 = (long)rt * sk.npair, i1 = i0 + sk.npair - 1;
   const int g_lo = sk.g_of(i0), g_hi = sk.g_of(i1);
   if (g_lo == g_hi) return;  // one share ran the whole tile into dW
@@ -395,6 +447,27 @@ __global__ __launch_bounds__(256) void k_wgrad_sk_fix(const float* __restrict__ 
     }
     *d = a;
   }
+}
+
+// Grid: (GW_FIX_SPLIT, tiles).
+template <int BN = 192>
+__global__ __launch_bounds__(256) void k_wgrad_sk_fix(const float* __restrict__ part, float* __restrict__ dW, int Nr,
+                                                      int Nc, GwSk sk) {
+  __shared__ int jt[256];
+  gw_sk_fix_tile<BN>(jt, part, dW, Nr, Nc, sk, blockIdx.y);
+}
+
+// The same for every problem of a group.  Grid: (GW_FIX_SPLIT, tiles of all problems).
+template <int BN = 192>
+__global__ __launch_bounds__(256) void k_wgrad_grp_fix(GwGrp grp, const float* __restrict__ part) {
+  __shared__ int jt[256];
+  const int tile = blockIdx.y;
+  GwGrpProb d = grp.p[0];
+#pragma unroll
+  for (int q = 1; q < GW_GRP_MAX; ++q)
+    if (q < grp.n && tile >= grp.p[q].tile0) d = grp.p[q];
+  if (tile - d.tile0 >= d.sk.nrt * (d.Nc / BN)) return;
+  gw_sk_fix_tile<BN>(jt, part + d.part_off, d.dW, d.Nr, d.Nc, d.sk, tile - d.tile0);
 }
 
 // dW column tile of a shape: 192 when it divides Nc, else 128 (0 = neither tiles)
@@ -464,5 +537,87 @@ DLT_API int dlt_gemm_wgrad(const bf16_t* dY, const bf16_t* X, float* dW, float* 
     DLT_HK_DISPATCH(hk, k_gemm_wgrad<HKC, 128><<<grid, 512, 0, st>>>(dY, X, splits > 1 ? part : dW, T, Nr, Nc, ldy,
                                                                     ldx, splits, splits > 1 ? 0 : 1));
   }
+  DLT_CHECK_LAUNCH();
+}
+
+// Plan of a group: every problem's GwSk with its explicit share count, slot offsets and
+// tile offsets.  Returns the floats of scratch (0 when no tile is split between
+// workgroups), or -1 when the group is refused: more
+// than GW_GRP_MAX problems, a shape the kernel cannot tile, column tiles that differ
+// between problems, or a share count outside [1, row tiles x token pairs].
+static long gw_grp_plan(GwGrp& grp, int n, int T, const int* Nr, const int* Nc, const int* shares, int* bn_out,
+                        int* tiles_out, int* wgs_out, bool* split_out) {
+  if (n < 1 || n > GW_GRP_MAX || T <= 0 || T % 128 || !Nr || !Nc || !shares) return -1;
+  const int bn = gw_bn(Nc[0]);
+  long off = 0;
+  int tiles = 0, wgs = 0;
+  bool split = false;  // some tile is shared between workgroups (a share boundary inside a row tile)
+  for (int p = 0; p < n; ++p) {
+    if (Nr[p] <= 0 || Nr[p] % 128 || Nc[p] <= 0 || !bn || gw_bn(Nc[p]) != bn || shares[p] < 1) return -1;
+    GwGrpProb& d = grp.p[p];
+    d.sk = gw_sk_plan(T, Nr[p], Nc[p], shares[p]);
+    if (d.sk.Gc != shares[p]) return -1;
+    const int ntc = Nc[p] / bn;
+    d.Nr = Nr[p];
+    d.Nc = Nc[p];
+    d.part_off = off;
+    d.tile0 = tiles;
+    off += (long)ntc * d.sk.Gc * d.sk.maxseg * 256 * bn;
+    tiles += d.sk.nrt * ntc;
+    wgs += d.sk.Gc * ntc;
+    for (int g = 1; g < d.sk.Gc && !split; ++g) split = ((long)g * d.sk.Wc / d.sk.Gc) % d.sk.npair != 0;
+  }
+  grp.n = n;
+  *split_out = split;
+  if (!split) off = 0;  // no partial segment exists: no slot is ever written or read
+  *bn_out = bn;
+  *tiles_out = tiles;
+  *wgs_out = wgs;
+  return off;
+}
+
+// Floats of scratch the grouped stream-K weight gradient needs (-1 = group refused).
+DLT_API long dlt_gemm_wgrad_grp_scratch(int n, int T, const int* Nr, const int* Nc, const int* shares) {
+  GwGrp grp{};
+  int bn, tiles, wgs;
+  bool split;
+  return gw_grp_plan(grp, n, T, Nr, Nc, shares, &bn, &tiles, &wgs, &split);
+}
+
+// dW_p[Nr_p, Nc_p] (fp32) += dY_p[T, Nr_p]^T . X_p[T, Nc_p] for p < n in ONE stream-K launch
+// plus one fix-up launch (none when no tile is split); problem p runs shares[p] shares per column tile and its result
+// equals dlt_gemm_wgrad_sk(..., Gc = shares[p]) bit for bit.  `table` (device, nblocks
+// int2 entries, nblocks % 8 == 0) maps workgroup ids to (problem << 24 | column tile,
+// share), negative x = padding; it must list every (problem, column tile, share) once
+// (ops/hip.py wgrad_group_table).  `part`: dlt_gemm_wgrad_grp_scratch() floats (unused
+// when that is 0).
+// Returns -1 with nothing launched when the group is refused.
+DLT_API int dlt_gemm_wgrad_grp(int n, const bf16_t* const* dY, const bf16_t* const* X, float* const* dW, float* part,
+                               const int* table, int nblocks, int T, const int* Nr, const int* Nc, const int* ldy,
+                               const int* ldx, const int* shares, int hk, hipStream_t st) {
+  GwGrp grp{};
+  int bn, tiles, wgs;
+  bool split;
+  if (gw_grp_plan(grp, n, T, Nr, Nc, shares, &bn, &tiles, &wgs, &split) < 0) return -1;
+  if (!dY || !X || !dW || (split && !part) || !table || !ldy || !ldx || nblocks % 8 || nblocks < wgs) return -1;
+  for (int p = 0; p < n; ++p) {
+    if (!dY[p] || !X[p] || !dW[p] || (ldy[p] | ldx[p]) % 8 || ldy[p] < Nr[p] || ldx[p] < Nc[p]) return -1;
+    grp.p[p].dY = dY[p];
+    grp.p[p].X = X[p];
+    grp.p[p].dW = dW[p];
+    grp.p[p].ldy = ldy[p];
+    grp.p[p].ldx = ldx[p];
+  }
+  const int2* tb = reinterpret_cast<const int2*>(table);
+  if (bn == 192) {
+    DLT_HK_DISPATCH(hk, k_gemm_wgrad_grp<HKC, 192><<<nblocks, 512, 0, st>>>(grp, tb, part));
+  } else {
+    DLT_HK_DISPATCH(hk, k_gemm_wgrad_grp<HKC, 128><<<nblocks, 512, 0, st>>>(grp, tb, part));
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  if (!split) return 0;  // every share is whole row tiles, all written straight into dW: nothing to sum
+  if (bn == 192) k_wgrad_grp_fix<192><<<dim3(GW_FIX_SPLIT, tiles), 256, 0, st>>>(grp, part);
+  else k_wgrad_grp_fix<128><<<dim3(GW_FIX_SPLIT, tiles), 256, 0, st>>>(grp, part);
   DLT_CHECK_LAUNCH();
 }

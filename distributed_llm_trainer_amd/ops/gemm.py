@@ -25,6 +25,11 @@ between runs, or between a run and its resumed continuation.  A plan file pins t
   it (no timing); otherwise the first process to finish a step writes it
   (``save_plan``).  ``DLT_GEMM_PLAN=none``: no plan.  ``DLT_GEMM_PLAN_OUT=path`` keeps
   the shipped plan and writes it, merged with the choices raced in this process, to path.
+  A plan's ``"wgrad_group"`` section pins which weight gradients issued together run as
+  one grouped stream-K launch (``HipGemm.wgrad_acc_group``): ``"T:NrxNc,NrxNc,..."`` (the
+  group's dW shapes in issue order) -> ``{"grid": workgroups, "members": [grouped
+  indices, default all]}`` or false.  Groups a plan does not pin are not grouped;
+  ``DLT_WGRAD_GROUP=0`` turns the route off, ``=1`` groups everything the kernel tiles.
 DDP replicas stay in sync regardless (the all-reduced gradient is identical on every
 rank).  For bitwise run-to-run reproducibility without a plan file use
 ``DLT_GEMM_TUNE=0 DLT_WGRAD_SPLITK=0 DLT_GEMM_TN=0 DLT_GEMM_FUSED=0`` (heuristic #0 everywhere).
@@ -73,7 +78,7 @@ def lib():
 
 
 # ---------------------------------------------------------------- plan pinning
-_PINNED = {"tn": {}, "splitk": {}, "hipblaslt": {}}  # replayed choices (see module docstring)
+_PINNED = {"tn": {}, "splitk": {}, "wgrad_group": {}, "hipblaslt": {}}  # replayed choices (see module docstring)
 _PLAN_STATE = {"path": None, "loaded": False, "saved": False}
 _INSTANCES = []  # weak references to live HipGemm objects (for save_plan)
 _RACES = {}  # process-wide race outcomes, see HipGemm.__init__
@@ -135,9 +140,15 @@ def load_plan(path: str, shipped: bool = False) -> None:
             _PINNED["tn"][(kind, *(int(x) for x in dims.split("x")))] = (
                 (int(c) if c is not None and c is not False else None) if kind == "swiglu4" else bool(c))
     _PINNED["splitk"] = {_splitk_key(k): int(c) for k, c in plan.get("splitk", {}).items()}
+    # "wgrad_group": "T:NrxNc,NrxNc,..." (the weight gradients a layer issues together, in
+    # issue order) -> {"grid": workgroups the shares are apportioned for, "members": indices
+    # of the problems that run in the grouped stream-K launch (default all; the others keep
+    # their own "splitk" route)}; false / 0 = not grouped.  DLT_WGRAD_GROUP=0/1 overrides.
+    _PINNED["wgrad_group"] = {_group_key(k): _group_value(c) for k, c in plan.get("wgrad_group", {}).items()}
     if _RACES:
         _RACES["tn"].update(_PINNED["tn"])
         _RACES["splitk"].update(_PINNED["splitk"])
+        _RACES["wgrad_group"].update(_PINNED["wgrad_group"])
     if not shipped:
         _PLAN_STATE["loaded"] = True
 
@@ -149,6 +160,22 @@ def _splitk_key(text: str):
     return tuple(p if p in ("bf16", "fp16") else int(p) for p in parts)
 
 
+def _group_key(text: str):
+    """'T:NrxNc,NrxNc' -> (T, ((Nr, Nc), (Nr, Nc)))."""
+    t, shapes = text.split(":", 1)
+    return int(t), tuple(tuple(int(v) for v in sh.split("x")) for sh in shapes.split(","))
+
+
+def _group_value(c):
+    """Plan value of a weight-gradient group -> (grid, members or None), or None (off)."""
+    if not c:
+        return None
+    if isinstance(c, dict):
+        grid, members = int(c.get("grid", 256)), c.get("members")
+        return (grid, tuple(int(m) for m in members) if members is not None else None) if grid > 0 else None
+    return (256 if c is True else int(c), None)
+
+
 def export_plan() -> dict:
     """Every choice made so far in this process (hipBLASLt heuristic indices, the
     hand-written GEMM race and the split-K factors of all live HipGemm objects)."""
@@ -157,6 +184,8 @@ def export_plan() -> dict:
     if n < 0:
         raise RuntimeError("plan table too large")
     tn, sk = dict(_PINNED["tn"]), dict(_PINNED["splitk"])
+    grp = dict(_PINNED["wgrad_group"])
+    grp.update(_RACES.get("wgrad_group", {}))
     for ref in _INSTANCES:
         g = ref()
         if g is not None:
@@ -172,7 +201,10 @@ def export_plan() -> dict:
             "tn": {"x".join(map(str, k)): c for k, c in tn.items() if len(k) == 3},
             "fused": {f"{k[0]}:" + "x".join(map(str, k[1:])): (c if k[0] == "swiglu4" else bool(c))
                       for k, c in tn.items() if len(k) == 4},
-            "splitk": {"x".join(map(str, k)): c for k, c in sk.items()}}
+            "splitk": {"x".join(map(str, k)): c for k, c in sk.items()},
+            "wgrad_group": {f"{t}:" + ",".join(f"{a}x{b}" for a, b in shapes):
+                            ({"grid": v[0], **({"members": list(v[1])} if v[1] is not None else {})} if v else False)
+                            for (t, shapes), v in grp.items()}}
 
 
 def save_plan(path: str) -> None:
@@ -291,11 +323,18 @@ class HipGemm:
         if not _RACES:
             _RACES["tn"] = dict(_PINNED["tn"])
             _RACES["splitk"] = dict(_PINNED["splitk"])
+            _RACES["wgrad_group"] = dict(_PINNED["wgrad_group"])
         self._choice = _RACES["tn"]  # (M, N, K) -> "bf16" | None (library); (kind, M, N, K) -> bool (fused)
         self._race = os.environ.get("DLT_GEMM_TN", "1") != "0"
         self._splitk = _RACES["splitk"]  # wgrad (M, N, K) -> token slices (1 = plain accumulate GEMM)
         self._splitk_on = os.environ.get("DLT_WGRAD_SPLITK", "1") != "0"
         self._hand_wgrad = os.environ.get("DLT_WGRAD_HAND", "1") != "0"
+        # weight-gradient groups (wgrad_acc_group): (T, shapes) -> (grid, members) | None, from
+        # the plan's "wgrad_group"; DLT_WGRAD_GROUP=0: never grouped, =1: every group that
+        # tiles (all members, DLT_WGRAD_GROUP_GRID workgroups, default 256)
+        self._group = _RACES["wgrad_group"]
+        self._group_env = os.environ.get("DLT_WGRAD_GROUP", "")
+        self._group_grid = int(os.environ.get("DLT_WGRAD_GROUP_GRID", "256"))
         self._fuse = os.environ.get("DLT_GEMM_FUSED", "1") != "0"
         self._dgrad_on = os.environ.get("DLT_GEMM_DGRAD", "1") != "0"
         # fp16 activations on the hand-written forward (the plan's shape pins) and fused
@@ -680,3 +719,41 @@ class HipGemm:
             raise ValueError("wgrad accumulator must be contiguous fp32")
         s = self._resolve(self._pick_splitk(dw2, dy, x), dy, x)
         self._run_wgrad(dw2, dy, x, s, False)
+
+    def _group_route(self, problems):
+        """(grid, members) when ``problems`` run as a grouped launch, else None: every dw
+        contiguous fp32, operands the hand-written kernel takes, one T and column tile, and
+        the route enabled (DLT_WGRAD_GROUP, else the plan's pin; unpinned groups stay off)."""
+        from . import hip
+        if self._group_env == "0" or not self._hand_wgrad or not 2 <= len(problems) <= hip.WGRAD_GROUP_MAX:
+            return None
+        T = problems[0][1].shape[0]
+        bn = hip.wgrad_bn(problems[0][2].shape[1])
+        for dw, dy, x in problems:
+            if (dw.dtype != torch.float32 or not dw.is_contiguous() or dy.dim() != 2 or x.dim() != 2
+                    or dy.shape[0] != T or x.shape[0] != T or dy.dtype != problems[0][1].dtype
+                    or not self._wgrad_hand_ok(dy, x) or not hip.wgrad_fits(T, dy.shape[1], x.shape[1])
+                    or hip.wgrad_bn(x.shape[1]) != bn or dw.numel() != dy.shape[1] * x.shape[1]):
+                return None
+        if self._group_env == "1":
+            return self._group_grid, None
+        return self._group.get((T, tuple((dy.shape[1], x.shape[1]) for _, dy, x in problems)))
+
+    def wgrad_acc_group(self, problems) -> None:
+        """dw (fp32) += dy^T @ x for every (dw, dy, x) of ``problems``, weight gradients
+        issued at one point (a layer's projections over one accumulation window): one
+        grouped stream-K launch (hip.gemm_wgrad_group) where the plan pins the group,
+        otherwise -- and for the problems the pin leaves out -- one ``wgrad_acc`` each."""
+        from . import hip
+        problems = list(problems)
+        route = self._group_route(problems)
+        rest = problems
+        if route is not None:
+            grid, members = route
+            members = range(len(problems)) if members is None else members
+            grp = [problems[i] for i in members]
+            if len(grp) >= 2 and hip.gemm_wgrad_group(
+                    [(dw.view(dy.shape[1], x.shape[1]), dy, x) for dw, dy, x in grp], grid=grid):
+                rest = [p for i, p in enumerate(problems) if i not in members]
+        for dw, dy, x in rest:
+            self.wgrad_acc(dw, dy, x)

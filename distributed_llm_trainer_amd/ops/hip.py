@@ -61,6 +61,8 @@ _SIGS = {
                        c_void_p],
     "dlt_gemm_wgrad_sk": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                           c_int, c_void_p],
+    "dlt_gemm_wgrad_grp": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                           c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     "dlt_scale_bf16": [c_void_p, c_void_p, ctypes.c_long, c_void_p, c_float, c_int, c_void_p],
     "dlt_gemm_bf16_tn": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                          c_void_p],
@@ -120,6 +122,8 @@ def lib():
             fn.restype = c_int
         L.dlt_gemm_wgrad_sk_scratch.argtypes = [c_int, c_int, c_int, c_int]
         L.dlt_gemm_wgrad_sk_scratch.restype = ctypes.c_long
+        L.dlt_gemm_wgrad_grp_scratch.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p]
+        L.dlt_gemm_wgrad_grp_scratch.restype = ctypes.c_long
         L.dlt_lmhead_loss_scratch.argtypes = [c_int, c_int]
         L.dlt_lmhead_loss_scratch.restype = ctypes.c_long
         _LIB = L
@@ -823,6 +827,150 @@ def gemm_wgrad_sk(dw: torch.Tensor, dy: torch.Tensor, x: torch.Tensor, shares: i
     part = torch.empty(n, device=dw.device, dtype=torch.float32)
     _chk(lib().dlt_gemm_wgrad_sk(_p(dy), _p(x), _p(dw), _p(part), T, Nr, Nc, dy.stride(0), x.stride(0), shares,
                                  _WG_HK[dy.dtype], _stream()), "gemm_wgrad_sk")
+    return True
+
+
+# ---------------------------------------------------------------- grouped wgrad GEMM
+WGRAD_GROUP_MAX = 8  # problems per launch (GW_GRP_MAX of csrc/gemm_wgrad.hip)
+
+
+def wgrad_group_shares(T: int, shapes, grid: int = 256):
+    """Shares per column tile of every problem of a grouped weight gradient
+    (``shapes``: (Nr, Nc) per problem, one column tile for all), so that ``grid``
+    workgroups each get about the same number of (row tile, 128-token pair) iterations:
+    problem p's workgroups are shares x column tiles, its work row tiles x column tiles x
+    pairs, so equal shares mean shares proportional to row tiles.  Every problem gets at
+    least one share (then sum(shares x column tiles) can exceed ``grid`` only when the
+    column tiles alone do); workgroups left over by the rounding go, one share at a time,
+    to the problem with the longest shares.  Pure arithmetic, no GPU."""
+    bn = wgrad_bn(shapes[0][1])
+    if T <= 0 or T % 128 or bn == 0 or any(wgrad_bn(nc) != bn or nr % 128 or nr <= 0 for nr, nc in shapes):
+        raise ValueError("wgrad_group_shares: the group does not tile")
+    npair = T // 128
+    ntc = [nc // bn for _, nc in shapes]
+    work = [((nr + 255) // 256) * npair for nr, _ in shapes]  # iterations of one column tile
+    total = sum(w * c for w, c in zip(work, ntc))
+    shares = [max(1, min(w, grid * w // total)) for w in work]
+
+    def used():
+        return sum(s * c for s, c in zip(shares, ntc))
+    while used() > grid:  # only after the max(1, .) above: take from the shortest shares
+        cand = [p for p in range(len(shapes)) if shares[p] > 1]
+        if not cand:
+            break
+        shares[min(cand, key=lambda p: (work[p] / shares[p], p))] -= 1
+    while True:
+        cand = [p for p in range(len(shapes)) if shares[p] < work[p] and used() + ntc[p] <= grid]
+        if not cand:
+            break
+        shares[max(cand, key=lambda p: (work[p] / shares[p], -p))] += 1
+    return shares
+
+
+# DLT_WGRAD_GROUP_SPREAD=1: deal the shares of a group to the least-loaded XCD instead of
+# packing problem after problem (A/B knob)
+_GRP_SPREAD = os.environ.get("DLT_WGRAD_GROUP_SPREAD", "0") == "1"
+
+
+def wgrad_group_table(shapes, shares, spread=None):
+    """Workgroup id -> (problem, column tile, share) of a grouped weight gradient, as a list
+    with a multiple of 8 entries, ``None`` for padding.  The dispatcher deals ids round-robin
+    to the 8 XCDs (id % 8).  The column tiles of one share read the same dY rows, so they
+    go to one XCD, on consecutive ids of it.  Shares are placed widest first (most column
+    tiles), problem after problem, each on the first XCD that stays within an equal part
+    of all workgroups: the shares of one problem read the same X columns, so packing them
+    onto few XCDs keeps X in few L2s, and every XCD gets the same number of working
+    workgroups whenever the share widths allow it (small preset, 256 workgroups: two
+    16-column down shares fill an XCD, the 52 four-column shares fill the other six).  A
+    share that fits nowhere -- and every share with ``spread`` -- goes to the XCD with the
+    fewest workgroups so far."""
+    spread = _GRP_SPREAD if spread is None else spread
+    bn = wgrad_bn(shapes[0][1])
+    ntc = [nc // bn for _, nc in shapes]
+    units = sorted(((p, g) for p in range(len(shapes)) for g in range(shares[p])), key=lambda u: -ntc[u[0]])
+    cap = -(-sum(s * c for s, c in zip(shares, ntc)) // 8)
+    lists = [[] for _ in range(8)]
+    for p, g in units:
+        fit = [] if spread else [i for i in range(8) if len(lists[i]) + ntc[p] <= cap]
+        x = fit[0] if fit else min(range(8), key=lambda i: (len(lists[i]), i))
+        lists[x].extend((p, c, g) for c in range(ntc[p]))
+    depth = max(len(li) for li in lists)
+    return [lists[i % 8][i // 8] if i // 8 < len(lists[i % 8]) else None for i in range(8 * depth)]
+
+
+_GRP_CACHE = {}  # (device, stream, T, shapes, shares) -> table / scratch / static arguments
+
+
+def _grp_state(dev, T, shapes, shares):
+    """Device table, scratch and static argument arrays of a group signature, made once
+    per (device, stream): launches on one stream are ordered, so they can share scratch."""
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream, T, shapes, shares)
+    st = _GRP_CACHE.get(key)
+    if st is None:
+        if torch.cuda.is_current_stream_capturing():
+            return None  # a table cannot be uploaded inside a capture: warm the group up first
+        n = len(shapes)
+        ints = ctypes.c_int * n
+        nr, nc, sh = ints(*(s[0] for s in shapes)), ints(*(s[1] for s in shapes)), ints(*shares)
+        floats = int(lib().dlt_gemm_wgrad_grp_scratch(n, T, nr, nc, sh))
+        if floats < 0:
+            _GRP_CACHE[key] = st = False
+            return st
+        ents = wgrad_group_table(shapes, shares)
+        table = torch.tensor([(-1, 0) if e is None else ((e[0] << 24) | e[1], e[2]) for e in ents],
+                             dtype=torch.int32, device=dev)
+        part = torch.empty(max(floats, 4), dtype=torch.float32, device=dev)
+        _GRP_CACHE[key] = st = (table, len(ents), part, nr, nc, sh)
+    return st
+
+
+def gemm_wgrad_group(problems, shares=None, grid: int = 256) -> bool:
+    """dw_p[Nr_p, Nc_p] (fp32) += dy_p[T, Nr_p]^T @ x_p[T, Nc_p] for every (dw, dy, x) of
+    ``problems`` in one stream-K launch and one fix-up launch (csrc/gemm_wgrad.hip
+    k_gemm_wgrad_grp): the weight gradients of a layer are each too small to fill the chip
+    well, together they are a whole number of three-quarter-tile shares.  ``shares``: shares
+    per column tile for every problem (default ``wgrad_group_shares(T, shapes, grid)``);
+    problem p's result equals ``gemm_wgrad_sk(dw_p, dy_p, x_p, shares[p])`` bit for bit.
+    Returns False with nothing launched and no dw touched when the group is refused:
+    different T, dtypes or column tiles, a shape that does not tile, a dw that is not
+    contiguous fp32, more than WGRAD_GROUP_MAX problems (or, inside a stream capture, a
+    group signature not run before)."""
+    n = len(problems)
+    if n < 1 or n > WGRAD_GROUP_MAX:
+        return False
+    dw0, dy0, x0 = problems[0]
+    T, bn = dy0.shape[0], wgrad_bn(x0.shape[1])
+    if dy0.dtype not in _WG_HK or bn == 0:
+        return False
+    for dw, dy, x in problems:
+        if (dy.dim() != 2 or x.dim() != 2 or dy.shape[0] != T or x.shape[0] != T or dy.dtype != dy0.dtype
+                or x.dtype != dy0.dtype or not wgrad_fits(T, dy.shape[1], x.shape[1]) or wgrad_bn(x.shape[1]) != bn
+                or dy.stride(1) != 1 or x.stride(1) != 1 or dy.stride(0) % 8 or x.stride(0) % 8
+                or dy.data_ptr() % 16 or x.data_ptr() % 16
+                or not dw.is_cuda or dw.dtype != torch.float32 or not dw.is_contiguous()
+                or dw.numel() != dy.shape[1] * x.shape[1] or dw.data_ptr() % 16 or dw.device != dy0.device
+                or dy.device != dy0.device or x.device != dy0.device):
+            return False
+    shapes = tuple((dy.shape[1], x.shape[1]) for _, dy, x in problems)
+    if shares is None:
+        shares = wgrad_group_shares(T, shapes, grid)
+    shares = tuple(int(s) for s in shares)
+    npair = T // 128
+    if len(shares) != n or any(s < 1 or s > ((nr + 255) // 256) * npair for s, (nr, _) in zip(shares, shapes)):
+        return False
+    st = _grp_state(dy0.device, T, shapes, shares)
+    if not st:
+        return False
+    table, nblocks, part, nr, nc, sh = st
+    ptrs, ints = ctypes.c_void_p * n, ctypes.c_int * n
+    rc = lib().dlt_gemm_wgrad_grp(n, ptrs(*(p[1].data_ptr() for p in problems)),
+                                  ptrs(*(p[2].data_ptr() for p in problems)),
+                                  ptrs(*(p[0].data_ptr() for p in problems)), _p(part), _p(table), nblocks, T, nr, nc,
+                                  ints(*(p[1].stride(0) for p in problems)), ints(*(p[2].stride(0) for p in problems)),
+                                  sh, _WG_HK[dy0.dtype], _stream())
+    if rc == -1:
+        return False
+    _chk(rc, "gemm_wgrad_group")
     return True
 
 
