@@ -247,6 +247,9 @@ def _reset(cache: KVCache) -> KVCache:
 @torch.no_grad()
 def kv_cached_generate(model, input_ids: torch.Tensor, max_new_tokens: int = 100, temperature: float = 1.0,
                        top_k: int = 50) -> torch.Tensor:
+    """KV-cached top-k sampling (``GPT.generate`` on the engine path).  The document mask
+    of ``GPT.set_doc_separator`` is not applied here: generation continues one document,
+    so the prompt and every cached key are taken to belong to it."""
     cfg = model.config
     eng = model.engine
     B = input_ids.shape[0]

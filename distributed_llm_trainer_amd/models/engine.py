@@ -168,6 +168,7 @@ class _StepState:
     dnf: Any = None     # early head: d(final norm output), computed in the forward
     head_acc: Any = None  # chunked head: this micro-step's fp32 lm_head weight gradient
     d_last: Any = None  # bf16 d of last layer (input of final norm)
+    doc: Any = None     # document mask bounds (lo, hi) of ids, or None (set_doc_separator)
 
 
 class GPTEngine:
@@ -270,6 +271,23 @@ class GPTEngine:
         # budget; beyond it (long context: 3.2 GB per layer at S = 32768, nh 12) the
         # backward regenerates each layer's bits (one extra VALU kernel per layer)
         self.attn_mask_budget = float(os.environ.get("DLT_ATTN_MASK_BUDGET_GB", "32")) * 1e9
+        # intra-document attention mask of packed sequences (set_doc_separator): None = off
+        self.doc_sep_token: Optional[int] = None
+
+    def set_doc_separator(self, token_id: Optional[int]) -> None:
+        """Mask attention inside documents: ``token_id`` ends a document (and belongs to
+        it), and a token attends only to its own document (``ops.doc_bounds``; None turns
+        the mask off).  The bounds are computed from the ids once per micro-step chain and
+        reach the attention forward, its recompute and its backward, and ``eval_loss``.
+        RoPE positions, the loss and the dropout keep bits are unchanged.  Raises
+        NotImplementedError here -- before any step -- when this model's attention route
+        has no mask (head_dim above 128, fp32 activations on the GPU)."""
+        if token_id is not None:
+            from ..ops import check_doc_mask
+            token_id = int(token_id)
+            if getattr(self.ops, "backend", "") == "hip":  # the GPU routes; reference ops mask densely
+                check_doc_mask("cuda", self.cfg.head_dim, self.act_dtype)
+        self.doc_sep_token = token_id
 
     def set_loss_segments(self, n: int) -> None:
         """Declare that each training forward carries ``n`` fused micro-steps.
@@ -469,6 +487,8 @@ class GPTEngine:
         if mask is not None:
             torch.cuda.current_stream().wait_event(mask_ev)
         kw = {"mask": mask} if mask is not None else {}
+        if st.doc is not None:
+            kw["doc"] = st.doc
         if pa > 0.0 and getattr(ops, "backend", "") == "hip" and getattr(ops, "attn_backend", "hip") in ("hip", "gemm"):
             # keep this layer's keep bits for the backward only within the memory budget.
             # The masks (two layouts, 1 bit per causal score: 8 * B * nh * S * ceil(S/32) B)
@@ -619,6 +639,8 @@ class GPTEngine:
         else:
             micro = 0
         st = _StepState(ids=ids, B=B, S=S, micro=micro, train=train, recompute=recompute)
+        if self.doc_sep_token is not None:  # once per chain, on this chain's stream
+            st.doc = self.ops.doc_bounds(ids, self.doc_sep_token)
         slot, n_slots, defer = acc if acc is not None else (self.acc_slot, self.acc_slots, self.defer)
         if need_bwd and defer:
             st.slot, st.defer, st.last = slot, True, slot == n_slots - 1
@@ -1019,13 +1041,14 @@ class GPTEngine:
                                       ddelta_out=sb(i, "da", H))
             del dn2
             # attention
+            dkw = {"doc": st.doc} if st.doc is not None else {}
             do = gm.linear_dgrad(da, w.wo)
             if c.k is None:  # packed: dq/dk/dv land in [M, 3H] with the inverse RoPE applied
                 dqkv = ops.attention_bwd_packed(c.q, c.o, do, c.lse, pa, k_attn, B, S, cfg.num_heads, cos, sin,
-                                                out=sb(i, "dqkv", 3 * H))
+                                                out=sb(i, "dqkv", 3 * H), **dkw)
                 del do
             else:
-                dq, dk, dv = ops.attention_bwd(c.q, c.k, c.v, c.o, do, c.lse, pa, k_attn, True)
+                dq, dk, dv = ops.attention_bwd(c.q, c.k, c.v, c.o, do, c.lse, pa, k_attn, True, **dkw)
                 del do
                 dqkv = ops.rope_qkv_bwd(dq, dk, dv, cos, sin, out=sb(i, "dqkv", 3 * H))
                 del dq, dk, dv

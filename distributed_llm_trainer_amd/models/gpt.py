@@ -94,21 +94,31 @@ class CausalSelfAttention(nn.Module):
         self.rotary_emb = RotaryPositionEmbedding(self.head_dim, config.max_seq_len)
         self.use_flash = config.use_flash_attention
 
-    def forward(self, hidden_states: torch.Tensor, attention_mask: Optional[torch.Tensor] = None):
+    def forward(self, hidden_states: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
+                doc_hidden: Optional[torch.Tensor] = None):
+        """``doc_hidden``: bool [B, 1, S, S], True where a query must not see a key because
+        it lies before the query's document (``GPT.set_doc_separator``); applied on top of
+        the causal mask in both the naive and the SDPA setting."""
         B, S, _ = hidden_states.shape
         q = self.q_proj(hidden_states).view(B, S, self.num_heads, self.head_dim).transpose(1, 2)
         k = self.k_proj(hidden_states).view(B, S, self.num_heads, self.head_dim).transpose(1, 2)
         v = self.v_proj(hidden_states).view(B, S, self.num_heads, self.head_dim).transpose(1, 2)
         cos, sin = self.rotary_emb(q, S)
         q, k = apply_rotary_pos_emb(q, k, cos[None, None], sin[None, None])
-        if self.use_flash:
+        if self.use_flash and doc_hidden is not None:
+            causal = torch.tril(torch.ones(S, S, device=hidden_states.device, dtype=torch.bool))
+            out = F.scaled_dot_product_attention(
+                q, k, v, attn_mask=causal[None, None] & ~doc_hidden,
+                dropout_p=self.config.attention_dropout if self.training else 0.0, is_causal=False)
+        elif self.use_flash:
             out = F.scaled_dot_product_attention(
                 q, k, v, attn_mask=None,
                 dropout_p=self.config.attention_dropout if self.training else 0.0, is_causal=True)
         else:
             scores = torch.matmul(q, k.transpose(-2, -1)) / math.sqrt(self.head_dim)
             mask = torch.triu(torch.ones(S, S, device=hidden_states.device, dtype=torch.bool), diagonal=1)
-            scores = scores.masked_fill(mask[None, None], float("-inf"))
+            mask = mask[None, None] if doc_hidden is None else mask[None, None] | doc_hidden
+            scores = scores.masked_fill(mask, float("-inf"))
             probs = F.softmax(scores, dim=-1, dtype=torch.float32).to(scores.dtype)
             out = self.attn_dropout(probs) @ v
         out = out.transpose(1, 2).contiguous().view(B, S, -1)
@@ -138,8 +148,8 @@ class TransformerBlock(nn.Module):
         self.post_attention_layernorm = RMSNorm(config.hidden_size)
         self.mlp = MLP(config)
 
-    def forward(self, hidden_states, attention_mask=None):
-        h = hidden_states + self.attention(self.input_layernorm(hidden_states), attention_mask)
+    def forward(self, hidden_states, attention_mask=None, doc_hidden=None):
+        h = hidden_states + self.attention(self.input_layernorm(hidden_states), attention_mask, doc_hidden)
         return h + self.mlp(self.post_attention_layernorm(h))
 
 
@@ -157,6 +167,35 @@ class GPT(nn.Module):
         self.engine = None
         self.store = None
         self._anchor = None
+        # intra-document attention mask (set_doc_separator); run-time state, not a
+        # GPTConfig field: checkpoints and the pickled config are unchanged
+        self.doc_sep_token: Optional[int] = None
+
+    def set_doc_separator(self, token_id: Optional[int]) -> None:
+        """Intra-document masking for packed training sequences: ``token_id`` (GPT-2:
+        50256) ends a document and belongs to it, and every token attends only to the
+        tokens of its own document at or before it.  ``None`` (the default) restores plain
+        causal attention.  RoPE positions stay absolute and the loss is unchanged.  Applies
+        to the eager path and to the engine (now or when it is enabled later); the engine
+        raises NotImplementedError if its attention route has no mask."""
+        token_id = None if token_id is None else int(token_id)
+        if self.engine is not None:
+            self.engine.set_doc_separator(token_id)
+        self.doc_sep_token = token_id
+
+    def _doc_hidden(self, input_ids: torch.Tensor) -> Optional[torch.Tensor]:
+        """Eager path: the dense mask [B, 1, S, S] of keys before each query's document, or
+        None when no separator is set or none precedes any token of the batch (the plain
+        causal path then runs, bit for bit; one host sync, oracle / CPU path only)."""
+        if self.doc_sep_token is None:
+            return None
+        from ..ops.reference import doc_bounds
+        lo, _ = doc_bounds(input_ids, self.doc_sep_token)
+        if not bool((lo > 0).any()):
+            return None
+        S = input_ids.shape[1]
+        kpos = torch.arange(S, device=input_ids.device).view(1, 1, 1, S)
+        return kpos < lo.view(lo.shape[0], 1, S, 1)
 
     def _init_weights(self, module):
         if isinstance(module, nn.Linear):
@@ -194,6 +233,8 @@ class GPT(nn.Module):
             if os.environ.get("DLT_GEMM", "planner") == "planner" and gemm_mod.available():
                 gemm = gemm_mod.HipGemm()
         self.engine = GPTEngine(self.config, provider, ops, act_dtype=act_dtype, seed=seed, gemm=gemm)
+        if self.doc_sep_token is not None:
+            self.engine.set_doc_separator(self.doc_sep_token)
         self._anchor = torch.zeros((), device=dev, requires_grad=True)
         return self.engine
 
@@ -209,11 +250,12 @@ class GPT(nn.Module):
         if self.engine is not None:
             return self._engine_forward(input_ids, labels)
         h = self.embed_tokens(input_ids)
+        doc_hidden = self._doc_hidden(input_ids)
         for layer in self.layers:
             if self.gradient_checkpointing and self.training:
-                h = checkpoint(layer, h, attention_mask, use_reentrant=False)
+                h = checkpoint(layer, h, attention_mask, doc_hidden, use_reentrant=False)
             else:
-                h = layer(h, attention_mask)
+                h = layer(h, attention_mask, doc_hidden)
         h = self.norm(h)
         logits = self.lm_head(h)
         loss = None
@@ -272,7 +314,9 @@ class GPT(nn.Module):
         """Top-k sampling with the reference's semantics (``gpt.py:457-484``).
 
         With the engine enabled this uses the KV-cached decoder in
-        ``eval/decode.py`` (one token per step instead of a full re-forward)."""
+        ``eval/decode.py`` (one token per step instead of a full re-forward).  The
+        KV-cached decoder does not apply the document mask of ``set_doc_separator``:
+        generation continues one document, so every cached key belongs to it."""
         self.eval()
         flush = getattr(getattr(self.engine, "provider", None), "flush_pending", None)
         if flush is not None:  # a recorded (lazy) optimizer step: the decoder reads every unit

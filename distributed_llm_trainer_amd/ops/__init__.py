@@ -16,7 +16,7 @@ from . import reference, rng
 _FUNCS = ("rope_tables", "embedding_fwd", "embedding_bwd", "add_dropout_rmsnorm_fwd", "rmsnorm_bwd",
           "rope_qkv_fwd", "rope_qkv_bwd", "attention_fwd", "attention_bwd", "swiglu_fwd", "swiglu_bwd",
           "cross_entropy_fwd_bwd", "scale_bf16", "rope_qk_inplace", "attention_fwd_packed",
-          "attention_bwd_packed", "lmhead_loss", "lmhead_loss_fits")
+          "attention_bwd_packed", "lmhead_loss", "lmhead_loss_fits", "doc_bounds")
 
 
 def _namespace(mod, name):
@@ -46,6 +46,23 @@ def hip_ops():
 # the attention-side ops whose HIP kernels are specialised for head_dims 64 / 128
 _ATTN_FUNCS = ("rope_qkv_fwd", "rope_qkv_bwd", "attention_fwd", "attention_bwd", "rope_qk_inplace",
                "attention_fwd_packed", "attention_bwd_packed")
+
+
+def check_doc_mask(device, head_dim: int = 64, act_dtype=torch.bfloat16) -> None:
+    """Raises NotImplementedError when the attention route :func:`for_device` picks for
+    this model has no document mask (``doc=``): on the GPU only the 16-bit flash kernels
+    (head_dim 64 / 128, and smaller heads zero-padded onto them) implement it; the
+    GEMM-formulated route (head_dim above 128) and the fp32 routes do not.  Called where a
+    separator is configured, so the error comes before the first step, not inside it."""
+    if torch.device(device).type != "cuda" or os.environ.get("DLT_ALLOW_REFERENCE_ON_GPU") == "1":
+        return
+    from . import attn_gemm
+    from .hip import ATTN_HEAD_DIMS
+    if head_dim not in ATTN_HEAD_DIMS:  # names the padded / GEMM route it would take
+        attn_gemm.check_doc(act_dtype, head_dim, True)
+    if act_dtype == torch.float32:
+        from . import hip_f32
+        hip_f32._no_doc(True)
 
 
 def for_device(device, head_dim: int = 64, act_dtype=torch.bfloat16) -> types.SimpleNamespace:

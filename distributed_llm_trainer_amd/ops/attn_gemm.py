@@ -101,10 +101,10 @@ def _rows_padded(t, B, S, nh, hd, Dp):
     return out
 
 
-def _fwd_pad(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask, dt):
+def _fwd_pad(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask, dt, doc=None):
     from . import hip
     o_p, aux = hip.attention_fwd(q4p[0], q4p[1], q4p[2], p, key, True, store_mask=store_mask, mask=mask,
-                                 scale=1.0 / math.sqrt(hd))
+                                 scale=1.0 / math.sqrt(hd), doc=doc)
     H = nh * hd
     o = torch.empty(B * S, H, dtype=dt, device=q4p.device) if out is None else out
     if o.dtype != dt or not o.is_contiguous() or o.numel() != B * S * H:
@@ -113,11 +113,12 @@ def _fwd_pad(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask, dt):
     return o, aux
 
 
-def _bwd_pad(q4p, o, do, aux, B, S, nh, hd, Dp, p, key):
+def _bwd_pad(q4p, o, do, aux, B, S, nh, hd, Dp, p, key, doc=None):
     """(dq, dk, dv) [3, B, nh, S, hd] from the padded flash backward."""
     from . import hip
     dq, dk, dv = hip.attention_bwd(q4p[0], q4p[1], q4p[2], _rows_padded(o, B, S, nh, hd, Dp),
-                                   _rows_padded(do, B, S, nh, hd, Dp), aux, p, key, scale=1.0 / math.sqrt(hd))
+                                   _rows_padded(do, B, S, nh, hd, Dp), aux, p, key, scale=1.0 / math.sqrt(hd),
+                                   doc=doc)
     g = torch.empty(3, B, nh, S, hd, dtype=dq.dtype, device=dq.device)
     for j, t in enumerate((dq, dk, dv)):
         _relayout16(t, (nh * S * Dp, Dp, S * Dp), g[j], (nh * S * hd, hd, S * hd), B, S, nh, hd, 1)
@@ -286,8 +287,26 @@ def _rope_bwd(dq, dk, dv, cos, sin, out=None):
 
 
 # ----------------------------------------------------------------------- entry points
-def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=True):
+def doc_route(dtype, hd: int) -> str:
+    """Name of the route a (dtype, head_dim) takes here, for messages."""
+    if pad_dim(dtype, hd):
+        return "fp32 zero-padded flash" if dtype == torch.float32 else "zero-padded 16-bit flash"
+    return "GEMM-formulated attention (batched GEMMs + HIP row kernels)"
+
+
+def check_doc(dtype, hd: int, doc) -> None:
+    """The document mask reaches the 16-bit flash kernels only: heads zero-padded onto them
+    pass the bounds through, every other route here raises (no silent fallback)."""
+    if doc is None or (dtype in _HK and pad_dim(dtype, hd)):
+        return
+    raise NotImplementedError(
+        f"document-masked attention (doc_sep_token) is not implemented on the {doc_route(dtype, hd)} route "
+        f"(head_dim {hd}, {dtype}); use bf16 or fp16 activations with head_dim <= 128")
+
+
+def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=True, doc=None):
     hd = qkv.shape[1] // (3 * nh)
+    check_doc(qkv.dtype, hd, doc)
     Dp = pad_dim(qkv.dtype, hd)
     H, ld = nh * hd, qkv.stride(0)
     if Dp and qkv.dtype == torch.float32:
@@ -295,7 +314,7 @@ def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=
         return _fwd_pad32(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask)
     if Dp:
         q4p = _pad16(qkv, (S * ld, ld, hd), B, S, nh, hd, Dp, 3, nh * hd)
-        return _fwd_pad(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask, qkv.dtype)
+        return _fwd_pad(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask, qkv.dtype, doc)
     _need_fit(B, nh, S, hd)
     if use16(qkv.dtype, B, nh, S, hd):
         q4, k4, v4 = _heads16(qkv, B, S, nh, hd, 3)
@@ -306,8 +325,9 @@ def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=
     return _narrow(o32, qkv.dtype, out), aux
 
 
-def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None):
+def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, doc=None):
     hd = qkv.shape[1] // (3 * nh)
+    check_doc(qkv.dtype, hd, doc)
     Dp = pad_dim(qkv.dtype, hd)
     H, ld = nh * hd, qkv.stride(0)
     if Dp and qkv.dtype == torch.float32:
@@ -317,7 +337,7 @@ def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None):
         return _rope_bwd(g[0], g[1], g[2], cos, sin, out=out)
     if Dp:
         q4p = _pad16(qkv, (S * ld, ld, hd), B, S, nh, hd, Dp, 3, nh * hd)
-        g = _bwd_pad(q4p, o, do, aux, B, S, nh, hd, Dp, p, key)
+        g = _bwd_pad(q4p, o, do, aux, B, S, nh, hd, Dp, p, key, doc)
         del q4p
         return _rope_bwd(g[0], g[1], g[2], cos, sin, out=out)
     _need_fit(B, nh, S, hd)
@@ -334,10 +354,11 @@ def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None):
     return _narrow(hip_f32.rope_qkv_bwd(dq, dk, dv, cos, sin, out=o32), qkv.dtype, out)
 
 
-def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=None):
+def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=None, doc=None):
     if not causal:
         raise NotImplementedError("only causal attention is implemented (the model is a causal LM)")
     B, nh, S, hd = q.shape
+    check_doc(q.dtype, hd, doc)
     Dp = pad_dim(q.dtype, hd)
     hm = (nh * S * hd, hd, S * hd)
     if Dp and q.dtype == torch.float32:
@@ -346,7 +367,7 @@ def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=
         return _fwd_pad32(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask)
     if Dp:
         q4p = torch.stack([_pad16(t.contiguous(), hm, B, S, nh, hd, Dp, 1, 0)[0] for t in (q, k, v)])
-        return _fwd_pad(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask, q.dtype)
+        return _fwd_pad(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask, q.dtype, doc)
     _need_fit(B, nh, S, hd)
     if use16(q.dtype, B, nh, S, hd):
         return _fwd16(q.contiguous(), k.contiguous(), v.contiguous(), B, nh, S, hd, p, key, out, mask, store_mask)
@@ -355,8 +376,9 @@ def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=
     return _narrow(o32, q.dtype, out), aux
 
 
-def attention_bwd(q, k, v, o, do, aux, p, key, causal=True):
+def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, doc=None):
     B, nh, S, hd = q.shape
+    check_doc(q.dtype, hd, doc)
     Dp = pad_dim(q.dtype, hd)
     hm = (nh * S * hd, hd, S * hd)
     if Dp and q.dtype == torch.float32:
@@ -365,7 +387,7 @@ def attention_bwd(q, k, v, o, do, aux, p, key, causal=True):
         return tuple(_bwd_pad32(q4p, o, do, aux, B, S, nh, hd, Dp, p, key).unbind(0))
     if Dp:
         q4p = torch.stack([_pad16(t.contiguous(), hm, B, S, nh, hd, Dp, 1, 0)[0] for t in (q, k, v)])
-        return tuple(_bwd_pad(q4p, o, do, aux, B, S, nh, hd, Dp, p, key).unbind(0))
+        return tuple(_bwd_pad(q4p, o, do, aux, B, S, nh, hd, Dp, p, key, doc).unbind(0))
     _need_fit(B, nh, S, hd)
     if use16(q.dtype, B, nh, S, hd):
         return _bwd16(q.contiguous(), k.contiguous(), v.contiguous(), o, do, aux, B, nh, S, hd, p, key)

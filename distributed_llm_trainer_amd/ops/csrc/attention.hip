@@ -27,6 +27,11 @@
 //  * Backward = 2 kernels: dQ (recomputes S, dP; also emits Delta = rowsum(dO*O)),
 //    then dK/dV (accumulated in registers) -- no fp32 atomics anywhere.  Causal
 //    tile skipping; workgroups process paired items of equal total length.
+//  * Document mask (DOC instantiations, packed training sequences): query q sees key k
+//    iff lo[q] <= k <= q, equivalently k <= q <= hi[k] (lo / hi: int32 [B, S], first /
+//    last position of the token's document, both non-decreasing).  The K/V loop of an
+//    item starts at the tile of its smallest lo, the Q/dO loop of dK/dV ends at the tile
+//    of its largest hi, and only tiles that straddle a bound take the masked kind.
 //
 // Layouts: q, k, v, dq, dk, dv: strided views -- head-major [B*nh, S, 64] or the
 // packed [B*S, 3, nh, 64] QKV GEMM output (see dlt_attn_fwd_ex); o, do: [B, S, nh, 64]
@@ -440,6 +445,14 @@ __device__ __forceinline__ void store_row16(bf16_t* __restrict__ row, const uint
 // exact in fp32 l/O and the same relative bf16 precision for P).  Almost every
 // rescale after a row's first tile is skipped.
 #define RESCALE_LOG2 8.0f
+// Running max of a row that has seen no live key yet.  Causal-only rows meet key 0 in
+// their first tile, so -inf never survives it.  Under a document mask the later rows
+// of an item can have whole leading tiles masked; with m = -inf such a tile gives
+// mx - m = -inf - -inf = NaN (and exp2(-inf * c + inf) = NaN).  The DOC kernels start
+// from this finite value instead: a dead tile leaves m alone and adds p = exp2(-inf) = 0
+// to l and O, and the first live tile rescales by alpha = exp2(-huge) = 0 exactly as
+// from -inf, so trivial bounds reproduce the causal kernel bit for bit.
+#define M_DEAD (-1e30f)
 
 template <int D>
 struct FwdState {
@@ -447,10 +460,10 @@ struct FwdState {
   float m, l;  // running max (raw score units) and per-lane partial row sum
 };
 
-template <bool MASK, bool DROP, int HK, int D>
+template <bool MASK, bool DROP, int HK, int D, bool DOC = false>
 __device__ __forceinline__ void fwd_tile(FwdState<D>& fs, const bf16_t* Kt, const bf16_t* Vt,
                                          const bf16x8_t (&qf)[D / 16], int k0, int qa, int S, int lane, float c_log2,
-                                         uint2 mw) {
+                                         uint2 mw, int lo = 0) {
   // One 64-key tile as ONE online-softmax step: S = K.Q^T of both 32-key halves first
   // (two independent MFMA chains), one row max / rescale decision for the tile, then
   // per half exp -> dropout -> P.V; the second half's softmax VALU runs while the
@@ -505,7 +518,7 @@ __device__ __forceinline__ void fwd_tile(FwdState<D>& fs, const bf16_t* Kt, cons
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int ka = k0 + 32 * t + acc_row(i, h);
-        sacc[t][i] = (ka > qa || ka >= S) ? -INFINITY : sacc[t][i];
+        sacc[t][i] = (ka > qa || ka >= S || (DOC && ka < lo)) ? -INFINITY : sacc[t][i];
       }
   }
   // row max as a depth-3 max3 tree per half (a linear fmaxf chain is 9 dependent ops)
@@ -573,15 +586,37 @@ __device__ unsigned long long* g_attn_ftim;
 #define FWD_ACC(c, w) ((void)0)
 #endif
 
+// DOC tile range of the 64-query item qb (fwd, dQ).  lo is non-decreasing, so the
+// item's smallest / largest bound are those of its first / last valid query: two
+// workgroup-uniform loads, no reduction.  ks = first K/V tile any row needs, kdoc =
+// first tile at or above every row's bound; both clamped into the causal range
+// [0, qb], so the loop stays inside the sequence whatever the arrays hold.
+__device__ __forceinline__ void doc_q_range(const int* __restrict__ lrow, int qb, int S, int& ks, int& kdoc) {
+  const int lo_min = lrow[qb * RB], lo_max = lrow[min(S, qb * RB + RB) - 1];
+  ks = min(max(lo_min, 0) / KVB, qb);
+  kdoc = min((max(lo_max, 0) + KVB - 1) / KVB, qb);
+}
+// The mirror image for the 64-key item kblk of dK/dV: hi of its first / last valid key.
+// nqe = end of the query-tile loop (the tile after the one holding the largest hi),
+// t_unm = first tile that reaches past the smallest hi; clamped to (kblk, nqt].
+__device__ __forceinline__ void doc_k_range(const int* __restrict__ hrow, int kblk, int S, int nqt, int& nqe,
+                                            int& t_unm) {
+  const int hi_min = hrow[kblk * RB], hi_max = hrow[min(S, kblk * RB + RB) - 1];
+  nqe = min(max(hi_max / QSTEP, kblk) + 1, nqt);
+  t_unm = min(max(hi_min + 1, 0) / QSTEP, S / QSTEP);
+}
+
 // D = 128 doubles the O accumulators and Q / K / V fragments: 256 VGPRs would spill,
 // so its instantiation may take the whole 512-register file (one wave per SIMD).
 #define ATTN_WAVES(D) __attribute__((amdgpu_waves_per_eu(D == 64 ? 2 : 1, 2)))
-template <bool DROP, int HK, int D>
+// DOC: dlo = lo [B, S] of the document mask (see the header); unused otherwise.
+template <bool DROP, int HK, int D, bool DOC = false>
 __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_fwd(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                     const bf16_t* __restrict__ v, bf16_t* __restrict__ o,
                                                     float* __restrict__ lse, const uint32_t* __restrict__ mask,
                                                     int S, int nh, float c_log2, float dscale, long in_bs,
-                                                    int in_hs, int in_rs, int xcd_map) {
+                                                    int in_hs, int in_rs, int xcd_map,
+                                                    const int* __restrict__ dlo = nullptr) {
   __shared__ __attribute__((aligned(16))) bf16_t lds[2 * 2 * KVB * D];  // [buf][K|V][64][D]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -617,12 +652,22 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_fwd(const bf16_t* __r
     FwdState<D> fs;
 #pragma unroll
     for (int dt = 0; dt < D / 32; ++dt) fs.o[dt] = zero16();
-    fs.m = -INFINITY;
+    fs.m = DOC ? M_DEAD : -INFINITY;
     fs.l = 0.f;
 
+    // DOC: this lane's bound, the wave's smallest (its first query's), and the item's
+    // tile range: the loop starts at tile ks, tiles below kdoc straddle some row's bound
+    int lo_q = 0, lo_w = 0, ks = 0, kdoc = 0;
+    if constexpr (DOC) {
+      const int* lrow = dlo + (size_t)b * S;
+      lo_q = lrow[min(qa, S - 1)];
+      lo_w = __builtin_amdgcn_readfirstlane(lo_q);
+      doc_q_range(lrow, qb, S, ks, kdoc);
+    }
+
     const int nkv = (min(S, qb * RB + RB) + KVB - 1) / KVB;  // = qb + 1 except at a ragged end
-    glds_tile<D>(k + hin, 0, S, in_rs, lds, wid, lane);
-    glds_tile<D>(v + hin, 0, S, in_rs, lds + KVB * D, wid, lane);
+    glds_tile<D>(k + hin, ks * KVB, S, in_rs, lds, wid, lane);
+    glds_tile<D>(v + hin, ks * KVB, S, in_rs, lds + KVB * D, wid, lane);
     __syncthreads();
 
     // One K/V tile per step.  BUF is a compile-time LDS buffer index and MASKED a
@@ -630,7 +675,10 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_fwd(const bf16_t* __r
     // item (straight-line unmasked loop, unrolled by two so every LDS address is
     // lane-base + immediate); tile qb holds the diagonal.
     uint2 mw_cur = make_uint2(0u, 0u), mw_next = make_uint2(0u, 0u);
-    if (DROP) mw_cur = make_uint2(mrow[0], W > 1 ? mrow[S] : 0u);  // words of tile 0
+    if (DROP) {  // words of the first tile
+      if constexpr (DOC) mw_cur = make_uint2(mrow[(size_t)(2 * ks) * S], 2 * ks + 1 < W ? mrow[(size_t)(2 * ks + 1) * S] : 0u);
+      else mw_cur = make_uint2(mrow[0], W > 1 ? mrow[S] : 0u);
+    }
     auto step = [&](auto bufc, auto maskc, int kb) {
       constexpr int BUF = decltype(bufc)::value;
       constexpr bool MASKED = decltype(maskc)::value;
@@ -647,8 +695,8 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_fwd(const bf16_t* __r
       const int k0 = kb * KVB;
       if (!MASKED)
         fwd_tile<false, DROP, HK, D>(fs, Kt, Vt, qf, k0, qa, S, lane, c_log2, mw_cur);
-      else if (k0 <= q0 + 31)
-        fwd_tile<true, DROP, HK, D>(fs, Kt, Vt, qf, k0, qa, S, lane, c_log2, mw_cur);
+      else if (k0 <= q0 + 31 && (!DOC || k0 + KVB > lo_w))  // DOC: not wholly below this wave's documents
+        fwd_tile<true, DROP, HK, D, DOC>(fs, Kt, Vt, qf, k0, qa, S, lane, c_log2, mw_cur, lo_q);
       mw_cur = mw_next;
       FWD_T(tb);
       tile_barrier();
@@ -656,16 +704,32 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_fwd(const bf16_t* __r
       FWD_ACC(tb - ta, tc - tb);
     };
     const int nfull = min(qb, nkv);
-    int kb = 0;
-    for (; kb + 1 < nfull; kb += 2) {
-      step(B0{}, UNM{}, kb);
-      step(B1{}, UNM{}, kb + 1);
-    }
-    if (kb < nfull) {  // odd count: last unmasked tile in buffer 0, diagonal in buffer 1
-      step(B0{}, UNM{}, kb);
-      if (kb + 1 < nkv) step(B1{}, MSK{}, kb + 1);
-    } else if (kb < nkv) {
-      step(B0{}, MSK{}, kb);
+    if constexpr (DOC) {
+      // Tile kb sits in buffer (kb - ks) & 1.  [ks, kdoc): masked by some row's bound;
+      // [kdoc, nfull): unmasked; [nfull, nkv): the diagonal.  One body per (buffer, kind),
+      // picked by two wave-uniform scalar branches per tile.
+      for (int kb = ks; kb < nkv; ++kb) {
+        const bool msk = kb < kdoc || kb >= nfull;
+        if ((kb - ks) & 1) {
+          if (msk) step(B1{}, MSK{}, kb);
+          else step(B1{}, UNM{}, kb);
+        } else {
+          if (msk) step(B0{}, MSK{}, kb);
+          else step(B0{}, UNM{}, kb);
+        }
+      }
+    } else {
+      int kb = 0;
+      for (; kb + 1 < nfull; kb += 2) {
+        step(B0{}, UNM{}, kb);
+        step(B1{}, UNM{}, kb + 1);
+      }
+      if (kb < nfull) {  // odd count: last unmasked tile in buffer 0, diagonal in buffer 1
+        step(B0{}, UNM{}, kb);
+        if (kb + 1 < nkv) step(B1{}, MSK{}, kb + 1);
+      } else if (kb < nkv) {
+        step(B0{}, MSK{}, kb);
+      }
     }
 
     const float l_tot = xhalf_sum(fs.l);
@@ -754,11 +818,12 @@ __device__ unsigned long long* g_attn_tim;
 // ---------------------------------------------------------------- dK / dV
 // One workgroup per 128 keys (32 per wave); sweep query tiles of 64 (two 32-row
 // sub-tiles).  Accumulators: S and dP with queries in registers, keys on lanes.
-template <bool MASK, bool DROP, int HK, int D>
+template <bool MASK, bool DROP, int HK, int D, bool DOC = false>
 __device__ __forceinline__ void dkdv_subtile(floatx16_t (&dka)[D / 32], floatx16_t (&dva)[D / 32], const bf16_t* Qt,
                                              const bf16_t* Dt, const float* rl, const float* rd,
                                              uint32_t mw, const bf16x8_t (&kf)[D / 16], const bf16x8_t (&vf)[D / 16],
-                                             int qs, int ka, int S, int lane, float c_log2, float dscale) {
+                                             int qs, int ka, int S, int lane, float c_log2, float dscale,
+                                             int hi = 0) {
   const int h = lane >> 5, kl = lane & 31;
   floatx16_t sacc = zero16(), pacc = zero16();
 #pragma unroll
@@ -779,7 +844,7 @@ __device__ __forceinline__ void dkdv_subtile(floatx16_t (&dka)[D / 32], floatx16
       float p = fast_exp2(fmaf(sacc[i], c_log2, -lv[e]));
       if (MASK) {
         const int qa = qs + r;
-        p = (ka > qa || qa >= S || ka >= S) ? 0.f : p;
+        p = (ka > qa || qa >= S || ka >= S || (DOC && qa > hi)) ? 0.f : p;
       }
       const float dp = pacc[i];
       if (DROP) {
@@ -811,7 +876,8 @@ __device__ __forceinline__ void dkdv_subtile(floatx16_t (&dka)[D / 32], floatx16
 
 // Work items: 64 keys (2 waves x 32); a workgroup processes the pair of key blocks
 // (p, nrb-1-p) -- equal work per workgroup (see the forward).
-template <bool DROP, int HK, int D>
+// DOC: dhi = hi [B, S] of the document mask (lanes are keys here); unused otherwise.
+template <bool DROP, int HK, int D, bool DOC = false>
 __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_bwd_dkdv(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                          const bf16_t* __restrict__ v,
                                                          const bf16_t* __restrict__ dout,
@@ -822,7 +888,8 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_bwd_dkdv(const bf16_t
                                                          float scale, float dscale, long in_bs, int in_hs, int in_rs,
                                                          long out_bs, int out_hs, int out_rs,
                                                          const float* __restrict__ cosT,
-                                                         const float* __restrict__ sinT, int xcd_map) {
+                                                         const float* __restrict__ sinT, int xcd_map,
+                                                         const int* __restrict__ dhi = nullptr) {
   // one LDS object (avoids hipcc's extra vmcnt waits with several __shared__ arrays)
   __shared__ __attribute__((aligned(16))) char smem[2 * 2 * QSTEP * D * 2 + 2 * 2 * QSTEP * 4];
   bf16_t* lds = reinterpret_cast<bf16_t*>(smem);                              // [buf][Q|dO][64][D]
@@ -866,6 +933,16 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_bwd_dkdv(const bf16_t
     for (int dt = 0; dt < D / 32; ++dt) dka[dt] = dva[dt] = zero16();
 
     const int qt_begin = kblk;  // the 64-query tile holding this item's diagonal
+    // DOC: this lane's bound, the wave's largest (its last key's), and the item's tile
+    // range: the loop ends before tile nqe, tiles from t_unm on reach past some key's bound
+    int hi_k = 0, hi_w = 0, nqe_doc = 0, t_unm = 0;
+    if constexpr (DOC) {
+      const int* hrow = dhi + (size_t)b * S;
+      hi_k = hrow[kc];
+      hi_w = __builtin_amdgcn_readlane(hi_k, 31);
+      doc_k_range(hrow, kblk, S, nqt, nqe_doc, t_unm);
+    }
+    const int nqe = DOC ? nqe_doc : nqt;
     float rl = 0.f, rd = 0.f;
     uint2 mw_cur = make_uint2(0u, 0u), mw_next = make_uint2(0u, 0u);
     auto load_rows = [&](int t, int buf) {  // Q / dO tiles by LDS-DMA, row stats via registers
@@ -900,7 +977,7 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_bwd_dkdv(const bf16_t
     auto step = [&](auto maskc, int t) {
       constexpr bool MASKED = decltype(maskc)::value;
       const int cur = (t - qt_begin) & 1;
-      const bool more = t + 1 < nqt;
+      const bool more = t + 1 < nqe;
       const uint32_t mw0 = mw_cur.x, mw1 = mw_cur.y;
       if (more) load_rows(t + 1, cur ^ 1);
       const bf16_t* Qt = lds + cur * 2 * QSTEP * D;
@@ -916,20 +993,20 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_bwd_dkdv(const bf16_t
         if (!MASKED)
           dkdv_subtile<false, DROP, HK, D>(dka, dva, Qs, Ds, rlp + 32 * qt, rdp + 32 * qt, mw, kf, vf, qs, ka, S,
                                            lane, c_log2, dscale);
-        else if (qs + 31 >= k0)
-          dkdv_subtile<true, DROP, HK, D>(dka, dva, Qs, Ds, rlp + 32 * qt, rdp + 32 * qt, mw, kf, vf, qs, ka, S,
-                                          lane, c_log2, dscale);
+        else if (qs + 31 >= k0 && (!DOC || qs <= hi_w))  // DOC: not wholly past this wave's documents
+          dkdv_subtile<true, DROP, HK, D, DOC>(dka, dva, Qs, Ds, rlp + 32 * qt, rdp + 32 * qt, mw, kf, vf, qs, ka, S,
+                                               lane, c_log2, dscale, hi_k);
       }
       if (more) store_rows(cur ^ 1);
       mw_cur = mw_next;
       tile_barrier();
     };
     int t = qt_begin;
-    const int t_full = S / QSTEP;
-    if (t < nqt) step(MSK{}, t++);
+    const int t_full = DOC ? t_unm : S / QSTEP;  // DOC: the first tile past the item's smallest hi
+    if (t < nqe) step(MSK{}, t++);
     ATTN_STAMP(2);
     for (; t < t_full; ++t) step(UNM{}, t);
-    for (; t < nqt; ++t) step(MSK{}, t);
+    for (; t < nqe; ++t) step(MSK{}, t);
     ATTN_STAMP(3);
 
     if (ka < S) {
@@ -945,10 +1022,11 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_bwd_dkdv(const bf16_t
 }
 
 // ---------------------------------------------------------------------- dQ
-template <bool MASK, bool DROP, int HK, int D>
+template <bool MASK, bool DROP, int HK, int D, bool DOC = false>
 __device__ __forceinline__ void dq_tile(floatx16_t (&dqa)[D / 32], const bf16_t* Kt, const bf16_t* Vt,
                                         const bf16x8_t (&qf)[D / 16], const bf16x8_t (&df)[D / 16], int k0, int qa,
-                                        int S, int lane, float c_log2, float nl2, float dl, float dscale, uint2 mw) {
+                                        int S, int lane, float c_log2, float nl2, float dl, float dscale, uint2 mw,
+                                        int lo = 0) {
   constexpr int NS = D / 16;
   const int h = lane >> 5, ql = lane & 31;
   floatx16_t sacc[2], pacc[2];
@@ -991,7 +1069,7 @@ __device__ __forceinline__ void dq_tile(floatx16_t (&dqa)[D / 32], const bf16_t*
       float p = fast_exp2(fmaf(sacc[t][i], c_log2, nl2));
       if (MASK) {
         const int kA = k0 + 32 * t + kr;
-        p = (kA > qa || kA >= S) ? 0.f : p;
+        p = (kA > qa || kA >= S || (DOC && kA < lo)) ? 0.f : p;
       }
       float dp = pacc[t][i];
       if (DROP) {
@@ -1010,7 +1088,8 @@ __device__ __forceinline__ void dq_tile(floatx16_t (&dqa)[D / 32], const bf16_t*
   }
 }
 
-template <bool DROP, int HK, int D>
+// DOC: dlo = lo [B, S] of the document mask, as in the forward; unused otherwise.
+template <bool DROP, int HK, int D, bool DOC = false>
 __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_bwd_dq(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                        const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
                                                        const bf16_t* __restrict__ o,
@@ -1020,7 +1099,8 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_bwd_dq(const bf16_t* 
                                                        int S, int nh, float c_log2, float scale, float dscale,
                                                        long in_bs, int in_hs, int in_rs, long out_bs, int out_hs,
                                                        int out_rs, const float* __restrict__ cosT,
-                                                       const float* __restrict__ sinT, int xcd_map) {
+                                                       const float* __restrict__ sinT, int xcd_map,
+                                                       const int* __restrict__ dlo = nullptr) {
   __shared__ __attribute__((aligned(16))) bf16_t lds[2 * 2 * KVB * D];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1065,15 +1145,26 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_bwd_dq(const bf16_t* 
 #pragma unroll
     for (int dt = 0; dt < D / 32; ++dt) dqa[dt] = zero16();
 
+    int lo_q = 0, lo_w = 0, ks = 0, kdoc = 0;  // DOC: as in the forward
+    if constexpr (DOC) {
+      const int* lrow = dlo + (size_t)b * S;
+      lo_q = lrow[qc];
+      lo_w = __builtin_amdgcn_readfirstlane(lo_q);
+      doc_q_range(lrow, qb, S, ks, kdoc);
+    }
+
     const int nkv = (min(S, qb * RB + RB) + KVB - 1) / KVB;
-    glds_tile<D>(k + hin, 0, S, in_rs, lds, wid, lane);
-    glds_tile<D>(v + hin, 0, S, in_rs, lds + KVB * D, wid, lane);
+    glds_tile<D>(k + hin, ks * KVB, S, in_rs, lds, wid, lane);
+    glds_tile<D>(v + hin, ks * KVB, S, in_rs, lds + KVB * D, wid, lane);
     __syncthreads();
 
     // Same loop structure as the forward: straight-line unmasked tiles (static LDS
     // buffers, unrolled by two), then the diagonal tile.
     uint2 mw_cur = make_uint2(0u, 0u), mw_next = make_uint2(0u, 0u);
-    if (DROP) mw_cur = make_uint2(mrow[0], W > 1 ? mrow[S] : 0u);
+    if (DROP) {
+      if constexpr (DOC) mw_cur = make_uint2(mrow[(size_t)(2 * ks) * S], 2 * ks + 1 < W ? mrow[(size_t)(2 * ks + 1) * S] : 0u);
+      else mw_cur = make_uint2(mrow[0], W > 1 ? mrow[S] : 0u);
+    }
     auto step = [&](auto bufc, auto maskc, int kb) {
       constexpr int BUF = decltype(bufc)::value;
       constexpr bool MASKED = decltype(maskc)::value;
@@ -1089,22 +1180,35 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_bwd_dq(const bf16_t* 
       const int k0 = kb * KVB;
       if (!MASKED)
         dq_tile<false, DROP, HK, D>(dqa, Kt, Vt, qf, df, k0, qa, S, lane, c_log2, nl2, dl, dscale, mw_cur);
-      else if (k0 <= q0 + 31)
-        dq_tile<true, DROP, HK, D>(dqa, Kt, Vt, qf, df, k0, qa, S, lane, c_log2, nl2, dl, dscale, mw_cur);
+      else if (k0 <= q0 + 31 && (!DOC || k0 + KVB > lo_w))
+        dq_tile<true, DROP, HK, D, DOC>(dqa, Kt, Vt, qf, df, k0, qa, S, lane, c_log2, nl2, dl, dscale, mw_cur, lo_q);
       mw_cur = mw_next;
       tile_barrier();
     };
     const int nfull = min(qb, nkv);
-    int kb = 0;
-    for (; kb + 1 < nfull; kb += 2) {
-      step(B0{}, UNM{}, kb);
-      step(B1{}, UNM{}, kb + 1);
-    }
-    if (kb < nfull) {
-      step(B0{}, UNM{}, kb);
-      if (kb + 1 < nkv) step(B1{}, MSK{}, kb + 1);
-    } else if (kb < nkv) {
-      step(B0{}, MSK{}, kb);
+    if constexpr (DOC) {  // tile kinds and buffers as in the forward's DOC loop
+      for (int kb = ks; kb < nkv; ++kb) {
+        const bool msk = kb < kdoc || kb >= nfull;
+        if ((kb - ks) & 1) {
+          if (msk) step(B1{}, MSK{}, kb);
+          else step(B1{}, UNM{}, kb);
+        } else {
+          if (msk) step(B0{}, MSK{}, kb);
+          else step(B0{}, UNM{}, kb);
+        }
+      }
+    } else {
+      int kb = 0;
+      for (; kb + 1 < nfull; kb += 2) {
+        step(B0{}, UNM{}, kb);
+        step(B1{}, UNM{}, kb + 1);
+      }
+      if (kb < nfull) {
+        step(B0{}, UNM{}, kb);
+        if (kb + 1 < nkv) step(B1{}, MSK{}, kb + 1);
+      } else if (kb < nkv) {
+        step(B0{}, MSK{}, kb);
+      }
     }
     if (qok) store_head_row<HK, D>(dq + hout + (size_t)qa * out_rs, dqa, scale, h, cosT, sinT, qa);
   }
@@ -1124,6 +1228,17 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_bwd_dq(const bf16_t* 
     }                            \
   } while (0)
 static inline bool attn_hd_ok(int hd) { return hd == 64 || hd == 128; }
+// document mask dispatch: DOCC = true with the bound array, false (the causal-only kernels) without
+#define DLT_DOC_DISPATCH(ptr, ...) \
+  do {                             \
+    if (ptr) {                     \
+      constexpr bool DOCC = true;  \
+      __VA_ARGS__;                 \
+    } else {                       \
+      constexpr bool DOCC = false; \
+      __VA_ARGS__;                 \
+    }                              \
+  } while (0)
 // XCD-aware work map on by default; DLT_ATTN_XCD=0 restores the natural order (A/B).
 static int xcd_map_enabled() {
   static int v = -1;
@@ -1159,9 +1274,10 @@ DLT_API int dlt_attn_dropout_mask(uint32_t* mask, int B, int nh, int S, uint32_t
 // q/k/v element (b, head, row, d) lives at base + b*in_bs + head*in_hs + row*in_rs + d:
 // head-major [B*nh, S, 64] (bs = nh*S*64, hs = S*64, rs = 64) or straight inside the
 // packed [B*S, 3H] QKV GEMM output (bs = S*3H, hs = 64, rs = 3H; k, v = q + H, q + 2H).
-DLT_API int dlt_attn_fwd_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse, uint32_t* mask,
-                            int B, int nh, int S, int hd, float scale, uint32_t key, uint32_t thr, float dscale,
-                            int gen_mask, long in_bs, int in_hs, int in_rs, int hk, hipStream_t st) {
+// dlt_attn_fwd_doc: the same with the document mask's lo [B, S] (int32; null = causal only).
+static int attn_fwd_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse, uint32_t* mask,
+                           int B, int nh, int S, int hd, float scale, uint32_t key, uint32_t thr, float dscale,
+                           int gen_mask, long in_bs, int in_hs, int in_rs, int hk, const int* lo, hipStream_t st) {
   if (!attn_hd_ok(hd) || S <= 0 || in_rs % 8 || in_hs % 8 || in_bs % 8) return -1;
   if (thr && !mask) return -2;  // dropout needs the keep-bit buffer
   const int nrb = (S + RB - 1) / RB;
@@ -1173,13 +1289,25 @@ DLT_API int dlt_attn_fwd_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, b
       const int rc = dlt_attn_dropout_mask(mask, B, nh, S, key, thr, st);
       if (rc) return rc;
     }
-    DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_fwd<true, HKC, HDC><<<grid, NT, 0, st>>>(
-                                                q, k, v, o, lse, mask, S, nh, c_log2, dscale, in_bs, in_hs, in_rs, xm)));
+    DLT_DOC_DISPATCH(lo, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_fwd<true, HKC, HDC, DOCC><<<grid, NT, 0, st>>>(
+                                                q, k, v, o, lse, mask, S, nh, c_log2, dscale, in_bs, in_hs, in_rs, xm, lo))));
   } else {
-    DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_fwd<false, HKC, HDC><<<grid, NT, 0, st>>>(
-                                                q, k, v, o, lse, nullptr, S, nh, c_log2, dscale, in_bs, in_hs, in_rs, xm)));
+    DLT_DOC_DISPATCH(lo, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_fwd<false, HKC, HDC, DOCC><<<grid, NT, 0, st>>>(
+                                                q, k, v, o, lse, nullptr, S, nh, c_log2, dscale, in_bs, in_hs, in_rs, xm, lo))));
   }
   DLT_CHECK_LAUNCH();
+}
+DLT_API int dlt_attn_fwd_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse, uint32_t* mask,
+                            int B, int nh, int S, int hd, float scale, uint32_t key, uint32_t thr, float dscale,
+                            int gen_mask, long in_bs, int in_hs, int in_rs, int hk, hipStream_t st) {
+  return attn_fwd_launch(q, k, v, o, lse, mask, B, nh, S, hd, scale, key, thr, dscale, gen_mask, in_bs, in_hs, in_rs, hk,
+                         nullptr, st);
+}
+DLT_API int dlt_attn_fwd_doc(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse, uint32_t* mask,
+                             int B, int nh, int S, int hd, float scale, uint32_t key, uint32_t thr, float dscale,
+                             int gen_mask, long in_bs, int in_hs, int in_rs, int hk, const int* lo, hipStream_t st) {
+  return attn_fwd_launch(q, k, v, o, lse, mask, B, nh, S, hd, scale, key, thr, dscale, gen_mask, in_bs, in_hs, in_rs, hk,
+                         lo, st);
 }
 
 DLT_API int dlt_attn_fwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse, uint32_t* mask,
@@ -1192,11 +1320,14 @@ DLT_API int dlt_attn_fwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16
 // dq/dk/dv use the (out_bs, out_hs, out_rs) layout; with cosT/sinT ([>= S, 32] fp32)
 // the inverse RoPE rotation is applied to dq and dk in the store (the gradient w.r.t.
 // the pre-rotation q/k of the packed QKV).
-DLT_API int dlt_attn_bwd_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o, const bf16_t* dout,
-                            const float* lse, const uint32_t* mask, float* delta_ws, bf16_t* dq, bf16_t* dk,
-                            bf16_t* dv, int B, int nh, int S, int hd, float scale, float dscale, long in_bs,
-                            int in_hs, int in_rs, long out_bs, int out_hs, int out_rs, const float* cosT,
-                            const float* sinT, int hk, hipStream_t st) {
+// dlt_attn_bwd_doc: the same with the document mask's lo (dQ) and hi (dK/dV), both
+// int32 [B, S] and given together (both null = causal only).
+static int attn_bwd_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o, const bf16_t* dout,
+                           const float* lse, const uint32_t* mask, float* delta_ws, bf16_t* dq, bf16_t* dk,
+                           bf16_t* dv, int B, int nh, int S, int hd, float scale, float dscale, long in_bs,
+                           int in_hs, int in_rs, long out_bs, int out_hs, int out_rs, const float* cosT,
+                           const float* sinT, int hk, const int* lo, const int* hi, hipStream_t st) {
+  if ((lo == nullptr) != (hi == nullptr)) return -4;
   if (!attn_hd_ok(hd) || S <= 0 || in_rs % 8 || in_hs % 8 || in_bs % 8 || out_rs % 4 || out_hs % 4 || out_bs % 4)
     return -1;
   if ((cosT == nullptr) != (sinT == nullptr)) return -3;
@@ -1208,21 +1339,37 @@ DLT_API int dlt_attn_bwd_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, c
   // dK/dV then reads.
   if (mask) {
     const uint32_t* maskT = mask + (size_t)B * nh * S * ((S + 31) / 32);
-    DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_bwd_dq<true, HKC, HDC><<<gq, NT, 0, st>>>(
+    DLT_DOC_DISPATCH(lo, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_bwd_dq<true, HKC, HDC, DOCC><<<gq, NT, 0, st>>>(
                             q, k, v, dout, o, lse, delta_ws, mask, dq, S, nh, c_log2, scale, dscale, in_bs, in_hs,
-                            in_rs, out_bs, out_hs, out_rs, cosT, sinT, xm)));
-    DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_bwd_dkdv<true, HKC, HDC><<<gk, NT, 0, st>>>(
+                            in_rs, out_bs, out_hs, out_rs, cosT, sinT, xm, lo))));
+    DLT_DOC_DISPATCH(hi, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_bwd_dkdv<true, HKC, HDC, DOCC><<<gk, NT, 0, st>>>(
                             q, k, v, dout, lse, delta_ws, maskT, dk, dv, S, nh, c_log2, scale, dscale, in_bs, in_hs,
-                            in_rs, out_bs, out_hs, out_rs, cosT, sinT, xm)));
+                            in_rs, out_bs, out_hs, out_rs, cosT, sinT, xm, hi))));
   } else {
-    DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_bwd_dq<false, HKC, HDC><<<gq, NT, 0, st>>>(
+    DLT_DOC_DISPATCH(lo, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_bwd_dq<false, HKC, HDC, DOCC><<<gq, NT, 0, st>>>(
                             q, k, v, dout, o, lse, delta_ws, mask, dq, S, nh, c_log2, scale, dscale, in_bs, in_hs,
-                            in_rs, out_bs, out_hs, out_rs, cosT, sinT, xm)));
-    DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_bwd_dkdv<false, HKC, HDC><<<gk, NT, 0, st>>>(
+                            in_rs, out_bs, out_hs, out_rs, cosT, sinT, xm, lo))));
+    DLT_DOC_DISPATCH(hi, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_bwd_dkdv<false, HKC, HDC, DOCC><<<gk, NT, 0, st>>>(
                             q, k, v, dout, lse, delta_ws, mask, dk, dv, S, nh, c_log2, scale, dscale, in_bs, in_hs,
-                            in_rs, out_bs, out_hs, out_rs, cosT, sinT, xm)));
+                            in_rs, out_bs, out_hs, out_rs, cosT, sinT, xm, hi))));
   }
   DLT_CHECK_LAUNCH();
+}
+DLT_API int dlt_attn_bwd_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o, const bf16_t* dout,
+                            const float* lse, const uint32_t* mask, float* delta_ws, bf16_t* dq, bf16_t* dk,
+                            bf16_t* dv, int B, int nh, int S, int hd, float scale, float dscale, long in_bs,
+                            int in_hs, int in_rs, long out_bs, int out_hs, int out_rs, const float* cosT,
+                            const float* sinT, int hk, hipStream_t st) {
+  return attn_bwd_launch(q, k, v, o, dout, lse, mask, delta_ws, dq, dk, dv, B, nh, S, hd, scale, dscale, in_bs, in_hs,
+                         in_rs, out_bs, out_hs, out_rs, cosT, sinT, hk, nullptr, nullptr, st);
+}
+DLT_API int dlt_attn_bwd_doc(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o, const bf16_t* dout,
+                             const float* lse, const uint32_t* mask, float* delta_ws, bf16_t* dq, bf16_t* dk,
+                             bf16_t* dv, int B, int nh, int S, int hd, float scale, float dscale, long in_bs,
+                             int in_hs, int in_rs, long out_bs, int out_hs, int out_rs, const float* cosT,
+                             const float* sinT, int hk, const int* lo, const int* hi, hipStream_t st) {
+  return attn_bwd_launch(q, k, v, o, dout, lse, mask, delta_ws, dq, dk, dv, B, nh, S, hd, scale, dscale, in_bs, in_hs,
+                         in_rs, out_bs, out_hs, out_rs, cosT, sinT, hk, lo, hi, st);
 }
 
 DLT_API int dlt_attn_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o, const bf16_t* dout,

@@ -87,6 +87,13 @@ _SIGS = {
     "dlt_attn_bwd_ex": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                         c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, ctypes.c_long, c_int, c_int,
                         ctypes.c_long, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
+    # the _ex launchers with the document mask's bounds (lo; lo, hi) before the stream
+    "dlt_attn_fwd_doc": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                         c_float, c_uint32, c_uint32, c_float, c_int, ctypes.c_long, c_int, c_int, c_int, c_void_p,
+                         c_void_p],
+    "dlt_attn_bwd_doc": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                         c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, ctypes.c_long, c_int, c_int,
+                         ctypes.c_long, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
     "dlt_rope_qk_inplace": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "dlt_dec_norm_qkv": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                          c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
@@ -495,22 +502,49 @@ def attention_dropout_mask(B, nh, S, p, key, device=None):
     return mask
 
 
-def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=None, scale=None):
+def doc_bounds(ids: torch.Tensor, sep: int):
+    """Document bounds (lo, hi), int32 [B, S], of packed sequences -- see
+    ``reference.doc_bounds``.  Torch ops on ``ids``' device: plumbing over B*S ints on the
+    current stream, not a kernel of the hot path."""
+    from .reference import doc_bounds as db
+    return db(ids, sep)
+
+
+def _req_doc(doc, B: int, S: int, device, name: str):
+    """(lo, hi) of :func:`doc_bounds` for a [B, S] batch on ``device``; (None, None) for None."""
+    if doc is None:
+        return None, None
+    if not isinstance(doc, (tuple, list)) or len(doc) != 2:
+        raise TypeError(f"{name}: doc must be None or (lo, hi)")
+    for t, n in zip(doc, ("lo", "hi")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}.doc.{n}: expected a tensor")
+        _req(t, torch.int32, f"{name}.doc.{n}", B * S)
+        if tuple(t.shape) != (B, S):
+            raise ValueError(f"{name}.doc.{n}: expected shape [{B}, {S}], got {list(t.shape)}")
+        if t.device != device:
+            raise ValueError(f"{name}.doc.{n}: expected device {device}, got {t.device}")
+    return doc[0], doc[1]
+
+
+def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=None, scale=None, doc=None):
     """Returns (o [B*S, nh*hd] bf16, aux).  With dropout on, the keep bits are written
     to a bitmask consumed by attention_bwd (no re-hashing in the backward); pass
     ``mask`` from ``attention_dropout_mask`` to skip generating it here.  ``scale``:
     the score scale (default 1/sqrt(hd); ops/attn_gemm.py runs zero-padded heads with
-    the unpadded head_dim's)."""
+    the unpadded head_dim's).  ``doc`` = (lo, hi) from :func:`doc_bounds`: the
+    intra-document mask of packed sequences (DOC kernels of attention.hip)."""
     if q.dtype == torch.float32:
         from . import hip_f32
         if scale is not None:
             raise NotImplementedError("fp32 attention: the score scale is 1/sqrt(head_dim)")
-        return hip_f32.attention_fwd(q, k, v, p, key, causal, store_mask=store_mask, out=out, mask=mask)
+        return hip_f32.attention_fwd(q, k, v, p, key, causal, store_mask=store_mask, out=out, mask=mask, doc=doc)
     if not causal:
         raise NotImplementedError("only causal attention is implemented (the model is a causal LM)")
     B, nh, S, hd = q.shape
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
         hk = _req_act(t, q.dtype, "attn." + n, B * nh * S * hd)
+    lo, _ = _req_doc(doc, B, S, q.device, "attn")
     if hd not in ATTN_HEAD_DIMS:
         raise NotImplementedError(f"attention kernels take head_dim {ATTN_HEAD_DIMS} (got {hd})")
     o = torch.empty(B * S, nh * hd, dtype=q.dtype, device=q.device) if out is None else out
@@ -528,9 +562,14 @@ def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=
         # [0] row layout (lane = query), [1] transposed (lane = key) -- see attention.hip;
         # with store_mask=False it only lives for this call (the backward regenerates it)
         mask = torch.empty(2, B * nh, (S + 31) // 32, S, dtype=torch.int32, device=q.device)
-    _chk(lib().dlt_attn_fwd(_p(q), _p(k), _p(v), _p(o), _p(lse), _p(mask), B, nh, S, hd,
-                            1.0 / math.sqrt(hd) if scale is None else float(scale),
-                            key & 0xFFFFFFFF, thr, dscale, gen, hk, _stream()), "attn_fwd")
+    sc = 1.0 / math.sqrt(hd) if scale is None else float(scale)
+    if doc is None:
+        _chk(lib().dlt_attn_fwd(_p(q), _p(k), _p(v), _p(o), _p(lse), _p(mask), B, nh, S, hd, sc,
+                                key & 0xFFFFFFFF, thr, dscale, gen, hk, _stream()), "attn_fwd")
+    else:
+        _chk(lib().dlt_attn_fwd_doc(_p(q), _p(k), _p(v), _p(o), _p(lse), _p(mask), B, nh, S, hd, sc,
+                                    key & 0xFFFFFFFF, thr, dscale, gen, nh * S * hd, S * hd, hd, hk, _p(lo),
+                                    _stream()), "attn_fwd_doc")
     return o, AttnAux((lse, mask if (store_mask or gen == 0) else None))
 
 
@@ -545,13 +584,15 @@ def _packed_dims(qkv, B, S, nh):
     return M, nh * hd, hd
 
 
-def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=True):
+def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=True, doc=None):
     """Causal attention reading q/k/v straight from the packed (roped) [B*S, 3H] QKV.
     Returns (o [B*S, H] bf16, aux) like :func:`attention_fwd`."""
     if qkv.dtype == torch.float32:
         from . import hip_f32
-        return hip_f32.attention_fwd_packed(qkv, B, S, nh, p, key, out=out, mask=mask, store_mask=store_mask)
+        return hip_f32.attention_fwd_packed(qkv, B, S, nh, p, key, out=out, mask=mask, store_mask=store_mask,
+                                            doc=doc)
     M, H, hd = _packed_dims(qkv, B, S, nh)
+    lo, _ = _req_doc(doc, B, S, qkv.device, "attn")
     hk = _HK[qkv.dtype]
     o = torch.empty(M, H, dtype=qkv.dtype, device=qkv.device) if out is None else out
     _req(o, qkv.dtype, "attn.o", M * H)
@@ -566,20 +607,26 @@ def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=
         gen = 0
     else:  # with store_mask=False it only lives for this call (the backward regenerates it)
         mask = torch.empty(2, B * nh, (S + 31) // 32, S, dtype=torch.int32, device=qkv.device)
-    _chk(lib().dlt_attn_fwd_ex(_p(qkv), _off(qkv, H), _off(qkv, 2 * H), _p(o), _p(lse), _p(mask), B, nh, S, hd,
-                               1.0 / math.sqrt(hd), key & 0xFFFFFFFF, thr, dscale, gen, S * 3 * H, hd, 3 * H, hk,
-                               _stream()), "attn_fwd_packed")
+    if doc is None:
+        _chk(lib().dlt_attn_fwd_ex(_p(qkv), _off(qkv, H), _off(qkv, 2 * H), _p(o), _p(lse), _p(mask), B, nh, S, hd,
+                                   1.0 / math.sqrt(hd), key & 0xFFFFFFFF, thr, dscale, gen, S * 3 * H, hd, 3 * H, hk,
+                                   _stream()), "attn_fwd_packed")
+    else:
+        _chk(lib().dlt_attn_fwd_doc(_p(qkv), _off(qkv, H), _off(qkv, 2 * H), _p(o), _p(lse), _p(mask), B, nh, S, hd,
+                                    1.0 / math.sqrt(hd), key & 0xFFFFFFFF, thr, dscale, gen, S * 3 * H, hd, 3 * H, hk,
+                                    _p(lo), _stream()), "attn_fwd_packed_doc")
     return o, AttnAux((lse, mask if (store_mask or gen == 0) else None))
 
 
-def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None):
+def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, doc=None):
     """Backward of :func:`attention_fwd_packed` + the in-place RoPE: returns dqkv
     [B*S, 3H] (gradient w.r.t. the pre-rotation QKV GEMM output); dq/dk/dv are written
     into it by the attention kernels with the inverse rotation in their epilogue."""
     if qkv.dtype == torch.float32:
         from . import hip_f32
-        return hip_f32.attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=out)
+        return hip_f32.attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=out, doc=doc)
     M, H, hd = _packed_dims(qkv, B, S, nh)
+    lo, hi = _req_doc(doc, B, S, qkv.device, "attn_bwd")
     hk = _HK[qkv.dtype]
     for t, nm in ((o, "o"), (do, "do")):
         _req(t, qkv.dtype, "attn_bwd." + nm, M * H)
@@ -599,22 +646,29 @@ def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None):
     delta = torch.empty(B, nh, S, dtype=torch.float32, device=qkv.device)
     dscale = 1.0 / (1.0 - p) if thr else 1.0
     st = S * 3 * H
-    _chk(lib().dlt_attn_bwd_ex(_p(qkv), _off(qkv, H), _off(qkv, 2 * H), _p(o), _p(do), _p(lse), _p(mask), _p(delta),
-                               _p(dqkv), _off(dqkv, H), _off(dqkv, 2 * H), B, nh, S, hd, 1.0 / math.sqrt(hd), dscale,
-                               st, hd, 3 * H, st, hd, 3 * H, _p(cos), _p(sin), hk, _stream()), "attn_bwd_packed")
+    if doc is None:
+        _chk(lib().dlt_attn_bwd_ex(_p(qkv), _off(qkv, H), _off(qkv, 2 * H), _p(o), _p(do), _p(lse), _p(mask), _p(delta),
+                                   _p(dqkv), _off(dqkv, H), _off(dqkv, 2 * H), B, nh, S, hd, 1.0 / math.sqrt(hd), dscale,
+                                   st, hd, 3 * H, st, hd, 3 * H, _p(cos), _p(sin), hk, _stream()), "attn_bwd_packed")
+    else:
+        _chk(lib().dlt_attn_bwd_doc(_p(qkv), _off(qkv, H), _off(qkv, 2 * H), _p(o), _p(do), _p(lse), _p(mask),
+                                    _p(delta), _p(dqkv), _off(dqkv, H), _off(dqkv, 2 * H), B, nh, S, hd,
+                                    1.0 / math.sqrt(hd), dscale, st, hd, 3 * H, st, hd, 3 * H, _p(cos), _p(sin), hk,
+                                    _p(lo), _p(hi), _stream()), "attn_bwd_packed_doc")
     return dqkv
 
 
-def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, scale=None):
+def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, scale=None, doc=None):
     if q.dtype == torch.float32:
         from . import hip_f32
         if scale is not None:
             raise NotImplementedError("fp32 attention: the score scale is 1/sqrt(head_dim)")
-        return hip_f32.attention_bwd(q, k, v, o, do, aux, p, key, causal)
+        return hip_f32.attention_bwd(q, k, v, o, do, aux, p, key, causal, doc=doc)
     B, nh, S, hd = q.shape
     n = B * nh * S * hd
     for t, nm in ((q, "q"), (k, "k"), (v, "v"), (o, "o"), (do, "do")):
         hk = _req_act(t, q.dtype, "attn_bwd." + nm, n)
+    lo, hi = _req_doc(doc, B, S, q.device, "attn_bwd")
     if isinstance(aux, tuple):
         lse, mask = aux
     else:
@@ -630,9 +684,15 @@ def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, scale=None):
     dk = torch.empty_like(k)
     dv = torch.empty_like(v)
     dscale = 1.0 / (1.0 - p) if thr else 1.0
-    _chk(lib().dlt_attn_bwd(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(mask), _p(delta), _p(dq), _p(dk), _p(dv),
-                            B, nh, S, hd, 1.0 / math.sqrt(hd) if scale is None else float(scale), dscale, hk,
-                            _stream()), "attn_bwd")
+    sc = 1.0 / math.sqrt(hd) if scale is None else float(scale)
+    if doc is None:
+        _chk(lib().dlt_attn_bwd(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(mask), _p(delta), _p(dq), _p(dk),
+                                _p(dv), B, nh, S, hd, sc, dscale, hk, _stream()), "attn_bwd")
+    else:
+        bs, hs = nh * S * hd, S * hd
+        _chk(lib().dlt_attn_bwd_doc(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(mask), _p(delta), _p(dq), _p(dk),
+                                    _p(dv), B, nh, S, hd, sc, dscale, bs, hs, hd, bs, hs, hd, None, None, hk, _p(lo),
+                                    _p(hi), _stream()), "attn_bwd_doc")
     return dq, dk, dv
 
 

@@ -158,17 +158,18 @@ def _split_packed(qkv, B, S, nh):
     return tuple(t[:, :, j].transpose(1, 2).contiguous() for j in range(3))
 
 
-def attention_fwd_packed(qkv: torch.Tensor, B: int, S: int, nh: int, p: float, key: int, out=None, mask=None):
+def attention_fwd_packed(qkv: torch.Tensor, B: int, S: int, nh: int, p: float, key: int, out=None, mask=None,
+                         doc=None):
     """Causal attention straight on the (already roped) packed [B*S, 3H] QKV."""
     q, k, v = _split_packed(qkv, B, S, nh)
-    return attention_fwd(q, k, v, p, key, True, out=out)
+    return attention_fwd(q, k, v, p, key, True, out=out, doc=doc)
 
 
 def attention_bwd_packed(qkv, o, do, lse, p: float, key: int, B: int, S: int, nh: int,
-                         cos: torch.Tensor, sin: torch.Tensor, out=None) -> torch.Tensor:
+                         cos: torch.Tensor, sin: torch.Tensor, out=None, doc=None) -> torch.Tensor:
     """Backward of attention_fwd_packed + the in-place RoPE: dqkv [B*S, 3H] (pre-RoPE)."""
     q, k, v = _split_packed(qkv, B, S, nh)
-    dq, dk, dv = attention_bwd(q, k, v, o, do, lse, p, key, True)
+    dq, dk, dv = attention_bwd(q, k, v, o, do, lse, p, key, True, doc=doc)
     res = rope_qkv_bwd(dq.float(), dk.float(), dv.float(), cos, sin).to(qkv.dtype)
     if out is not None:
         out.copy_(res)
@@ -177,14 +178,66 @@ def attention_bwd_packed(qkv, o, do, lse, p: float, key: int, B: int, S: int, nh
 
 
 # -------------------------------------------------------------- attention
+def doc_bounds(ids: torch.Tensor, sep: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Document bounds of packed sequences ``ids`` [B, S]: token ``sep`` ends a document
+    and belongs to it.  Returns int32 ``(lo, hi)`` [B, S]: the first and the last position
+    of each token's document (``lo[i]`` = 1 + the last separator before i, or 0;
+    ``hi[i]`` = the first separator at or after i, or S - 1).  Both are non-decreasing
+    along S, and ``lo <= i <= hi``."""
+    if ids.dim() != 2:
+        raise ValueError("doc_bounds: ids must be [B, S]")
+    S = ids.shape[1]
+    pos = torch.arange(S, device=ids.device, dtype=torch.int64).expand_as(ids)
+    is_sep = ids == sep
+    # lo: running max of (separator position + 1), shifted right by one token
+    after = torch.where(is_sep, pos + 1, torch.zeros_like(pos))
+    lo = torch.zeros_like(pos)
+    if S > 1:
+        lo[:, 1:] = torch.cummax(after, dim=1).values[:, :-1]
+    # hi: running min from the right of the separator positions
+    at = torch.where(is_sep, pos, torch.full_like(pos, S - 1))
+    hi = torch.cummin(at.flip(1), dim=1).values.flip(1)
+    return lo.to(torch.int32).contiguous(), hi.to(torch.int32).contiguous()
+
+
+def _check_doc(doc, B: int, S: int, device, name: str):
+    """``doc`` = (lo, hi) of :func:`doc_bounds`: int32, contiguous, [B, S], on ``device``."""
+    if not isinstance(doc, (tuple, list)) or len(doc) != 2:
+        raise TypeError(f"{name}: doc must be None or (lo, hi)")
+    for t, n in zip(doc, ("lo", "hi")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+            raise TypeError(f"{name}.doc.{n}: expected an int32 tensor")
+        if tuple(t.shape) != (B, S):
+            raise ValueError(f"{name}.doc.{n}: expected shape [{B}, {S}], got {list(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}.doc.{n}: must be contiguous")
+        if t.device != torch.device(device):
+            raise ValueError(f"{name}.doc.{n}: expected device {device}, got {t.device}")
+    return doc
+
+
+def _masked_out(S: int, device, causal: bool, doc, B: int, name: str) -> Optional[torch.Tensor]:
+    """Dense boolean mask of the scores a query must not see ([S, S], or [B, 1, S, S] with
+    a document mask: key k is visible to query q iff lo[q] <= k <= q)."""
+    mask = torch.triu(torch.ones(S, S, dtype=torch.bool, device=device), diagonal=1) if causal else None
+    if doc is None:
+        return mask
+    if not causal:
+        raise NotImplementedError("the document mask is defined for causal attention")
+    lo, _ = _check_doc(doc, B, S, device, name)
+    kpos = torch.arange(S, device=device).view(1, 1, 1, S)
+    return mask | (kpos < lo.view(B, 1, S, 1))
+
+
 def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, p: float, key: int,
-                  causal: bool = True, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """q,k,v [B, nh, S, hd] -> o [B*S, nh*hd] (q dtype), lse [B, nh, S] fp32."""
+                  causal: bool = True, out=None, doc=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """q,k,v [B, nh, S, hd] -> o [B*S, nh*hd] (q dtype), lse [B, nh, S] fp32.
+    ``doc`` = (lo, hi) from :func:`doc_bounds` adds the intra-document mask."""
     B, nh, S, hd = q.shape
     scale = 1.0 / math.sqrt(hd)
     s = torch.matmul(q.float(), k.float().transpose(-2, -1)) * scale
-    if causal:
-        mask = torch.triu(torch.ones(S, S, dtype=torch.bool, device=q.device), diagonal=1)
+    mask = _masked_out(S, q.device, causal, doc, B, "attn")
+    if mask is not None:
         s = s.masked_fill(mask, float("-inf"))
     lse = torch.logsumexp(s, dim=-1)
     prob = torch.exp(s - lse.unsqueeze(-1))
@@ -199,7 +252,7 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, p: float, k
     return o, lse
 
 
-def attention_bwd(q, k, v, o, do, lse, p: float, key: int, causal: bool = True):
+def attention_bwd(q, k, v, o, do, lse, p: float, key: int, causal: bool = True, doc=None):
     """Flash-style backward from (o, lse).  do/o are [B*S, H]; returns dq, dk, dv [B,nh,S,hd]."""
     B, nh, S, hd = q.shape
     scale = 1.0 / math.sqrt(hd)
@@ -207,8 +260,8 @@ def attention_bwd(q, k, v, o, do, lse, p: float, key: int, causal: bool = True):
     of = o.float().view(B, S, nh, hd).transpose(1, 2)
     dof = do.float().view(B, S, nh, hd).transpose(1, 2)
     s = torch.matmul(qf, kf.transpose(-2, -1)) * scale
-    if causal:
-        mask = torch.triu(torch.ones(S, S, dtype=torch.bool, device=q.device), diagonal=1)
+    mask = _masked_out(S, q.device, causal, doc, B, "attn_bwd")
+    if mask is not None:
         s = s.masked_fill(mask, float("-inf"))
     prob = torch.exp(s - lse.unsqueeze(-1))
     if p > 0.0:

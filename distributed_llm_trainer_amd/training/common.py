@@ -207,6 +207,13 @@ def add_eval_args(p) -> None:
                    help="held-out data for tinystories / openwebtext (same formats as --data_path)")
 
 
+def add_doc_mask_args(p) -> None:
+    p.add_argument("--doc_sep_token", type=int, default=None, metavar="ID",
+                   help="intra-document attention masking for packed sequences: token ID ends a document "
+                        "(GPT-2: 50256) and a token attends only within its own document; training and "
+                        "--eval_batches evaluation both use it (default: plain causal attention)")
+
+
 def unwrap_batch(batch):
     if isinstance(batch, dict):
         return batch["input_ids"]

@@ -69,6 +69,10 @@ class TrainingConfig:
     # held-out evaluation every eval_interval steps and once after the last step, over this
     # many batches of batch_size sequences per rank; 0 = off (--eval_batches)
     eval_batches: int = 0
+    # intra-document attention masking for packed sequences: this token id ends a document
+    # (GPT-2: 50256) and a token attends only within its own document; None = plain causal
+    # (--doc_sep_token; GPT.set_doc_separator).  Training and evaluation use the same value.
+    doc_sep_token: Optional[int] = None
 
 
 @dataclass
@@ -97,6 +101,7 @@ class FSDPTrainingConfig:
     # per-micro-step reduce-scatter (Q15 parity) then runs once per chain -- the same sum
     micro_step_fusion: int = 0
     eval_batches: int = 0              # held-out batches per rank and evaluation, 0 = off (as TrainingConfig)
+    doc_sep_token: Optional[int] = None  # document separator id for intra-document masking (as TrainingConfig)
 
 
 @dataclass

@@ -40,7 +40,7 @@ from ..parallel.flat import FlatParamStore
 from ..utils import checkpoint as ckpt
 from ..utils import debug as dbg
 from ..utils.profiling import Profiler, range_push, range_pop
-from .common import EVAL_SEED_OFFSET, HeldOutBatches, add_eval_args, cosine_lr, evaluate_held_out, gemm_plan_hook, global_mean_loss, held_out_of, log_evaluation, memory_stats, micro_step_fusion, seed_all, select_device, setup_distributed, unwrap_batch
+from .common import EVAL_SEED_OFFSET, HeldOutBatches, add_doc_mask_args, add_eval_args, cosine_lr, evaluate_held_out, gemm_plan_hook, global_mean_loss, held_out_of, log_evaluation, memory_stats, micro_step_fusion, seed_all, select_device, setup_distributed, unwrap_batch
 from .configs import TrainingConfig
 from .optim import flat_store_optimizer
 
@@ -111,6 +111,8 @@ class DistributedTrainer:
         self.model = model.to(self.device)
         if self.is_main_process:
             print(f"Model parameters: {count_parameters(self.model):,}")
+        # before the engine exists, so a route without the mask is refused when it is enabled
+        self.model.set_doc_separator(getattr(self.training_config, "doc_sep_token", None))
         if self.use_engine:
             act = self.dtype if self.device.type == "cuda" else None
             eng = self.model.enable_engine(seed=self.training_config.seed + 1000003 * self.rank, act_dtype=act)
@@ -399,6 +401,7 @@ def build_parser() -> argparse.ArgumentParser:
                         "chain runs its own (no [GA*M, N] slot buffers, no window-wide dlogits; lm_head in row "
                         "chunks): ~56 %% of the default peak memory at -3 %% tok/s")
     add_eval_args(p)
+    add_doc_mask_args(p)
     return p
 
 
@@ -451,7 +454,7 @@ def main(argv=None):
         tc.defer_roles = LEAN_DEFER_ROLES
     if args.memory_first:
         tc.memory_first = True
-    for k in ("eval_interval", "eval_batches"):
+    for k in ("eval_interval", "eval_batches", "doc_sep_token"):
         if getattr(args, k) is not None:
             setattr(tc, k, getattr(args, k))
     if tc.eval_batches > 0:

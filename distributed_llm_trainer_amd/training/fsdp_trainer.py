@@ -33,7 +33,7 @@ from ..parallel.fsdp import FSDPRuntime
 from ..utils import checkpoint as ckpt
 from ..utils import debug as dbg
 from ..utils.profiling import Profiler
-from .common import (EVAL_SEED_OFFSET, HeldOutBatches, add_eval_args, cosine_lr, evaluate_held_out, gemm_plan_hook,
+from .common import (EVAL_SEED_OFFSET, HeldOutBatches, add_doc_mask_args, add_eval_args, cosine_lr, evaluate_held_out, gemm_plan_hook,
                      global_mean_loss, held_out_of, log_evaluation, memory_stats, micro_step_fusion, seed_all, select_device, setup_distributed, unwrap_batch)
 from .configs import FSDPConfig, FSDPTrainingConfig
 from .optim import FlatAdamW
@@ -92,6 +92,8 @@ class FSDPTrainer:
                                    sync_every_micro_step=fc.sync_every_micro_step)
         self.model = model.to(self.device)
         self.model.gradient_checkpointing = bool(fc.activation_checkpointing)
+        # before the engine exists, so a route without the mask is refused when it is enabled
+        self.model.set_doc_separator(getattr(tc, "doc_sep_token", None))
         self.model.enable_engine(provider=self.runtime, act_dtype=self.compute_dtype,
                                  seed=tc.seed + 1000003 * self.rank)
         if self.is_main_process:
@@ -422,6 +424,7 @@ def build_parser():
                    help="full: reference FULL_STATE_DICT file (rank-0 gather); sharded: per-rank shard "
                         "directory, no gather (resume with --resume_from DIR)")
     add_eval_args(p)  # (--eval_data_path: this trainer reads the dummy stream only)
+    add_doc_mask_args(p)
     return p
 
 
@@ -457,7 +460,7 @@ def main(argv=None):
         fc.reduce_dtype = args.reduce_dtype
     if args.seq_len:
         model_config.max_seq_len = args.seq_len
-    for k in ("eval_interval", "eval_batches"):
+    for k in ("eval_interval", "eval_batches", "doc_sep_token"):
         if getattr(args, k) is not None:
             setattr(tc, k, getattr(args, k))
     if tc.eval_batches > 0 and tc.eval_interval <= 0:

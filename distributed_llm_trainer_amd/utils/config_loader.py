@@ -69,6 +69,8 @@ def load_yaml_config(path: str, model_cfg: GPTConfig, train_cfg, fsdp_cfg=None, 
     t = y.get("training", {}) or {}
     for yk, ak in _TRAIN_MAP.items():
         _set(train_cfg, ak, t.get(yk))
+    if t.get("doc_sep_token") is not None and hasattr(train_cfg, "doc_sep_token"):
+        train_cfg.doc_sep_token = int(t["doc_sep_token"])  # Optional[int]: _set cannot infer the type from None
     d = y.get("distributed", {}) or {}
     _set(train_cfg, "mixed_precision", d.get("mixed_precision"))
     if fsdp_cfg is not None:

@@ -1,0 +1,413 @@
+"""Document-masked attention for packed sequences, CPU side: ``doc_bounds``, the reference
+ops' dense mask against an independent softmax attention and its autograd, the eager
+model's isolation between documents, the engine on reference ops against plain autograd
+with the same dropout masks, and the trainers' ``doc_sep_token`` setting."""
+import copy
+import json
+import math
+import os
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from distributed_llm_trainer_amd.models import GPT, GPTConfig
+from distributed_llm_trainer_amd.models.engine import shift_targets
+from distributed_llm_trainer_amd.ops import reference as ref, rng
+
+SEP = 7
+
+
+# ------------------------------------------------------------------ 1. doc_bounds
+def _bounds_by_hand(row, sep):
+    S = len(row)
+    lo, hi = [], []
+    for i in range(S):
+        prev = [j for j in range(i) if row[j] == sep]
+        nxt = [j for j in range(i, S) if row[j] == sep]
+        lo.append(prev[-1] + 1 if prev else 0)
+        hi.append(nxt[0] if nxt else S - 1)
+    return lo, hi
+
+
+@pytest.mark.parametrize("row", [
+    [SEP, 1, 2, 3, 4, 5],        # a separator at position 0
+    [1, 2, 3, 4, 5, SEP],        # a separator at S - 1
+    [1, 2, SEP, SEP, 3, 4],      # two adjacent separators
+    [1, 2, 3, 4, 5, 6],          # no separator
+    [SEP, SEP, SEP, 1, SEP, 2],  # one-token documents
+])
+def test_doc_bounds_hand_written(row):
+    ids = torch.tensor([row, list(reversed(row))])
+    lo, hi = ref.doc_bounds(ids, SEP)
+    assert lo.dtype == hi.dtype == torch.int32 and lo.shape == hi.shape == ids.shape
+    assert lo.is_contiguous() and hi.is_contiguous()
+    S = ids.shape[1]
+    pos = torch.arange(S, dtype=torch.int32)
+    for b in range(2):
+        want_lo, want_hi = _bounds_by_hand(ids[b].tolist(), SEP)
+        assert lo[b].tolist() == want_lo and hi[b].tolist() == want_hi
+        assert (lo[b][1:] >= lo[b][:-1]).all() and (hi[b][1:] >= hi[b][:-1]).all(), "bounds must be monotone"
+        assert (lo[b] <= pos).all() and (pos <= hi[b]).all()
+    # the two forms of the mask are the same set: lo[q] <= k <= q  <=>  k <= q <= hi[k]
+    q = pos.view(1, S, 1)
+    k = pos.view(1, 1, S)
+    by_lo = (lo.unsqueeze(2) <= k) & (k <= q)
+    by_hi = (k <= q) & (q <= hi.unsqueeze(1))
+    assert torch.equal(by_lo, by_hi)
+
+
+def test_doc_bounds_is_exposed_by_every_backend():
+    from distributed_llm_trainer_amd import ops
+    from distributed_llm_trainer_amd.ops import hip
+    ids = torch.tensor([[1, SEP, 2, 3]])
+    for fn in (ops.CPU_OPS.doc_bounds, hip.doc_bounds):
+        lo, hi = fn(ids, SEP)
+        assert lo.tolist() == [[0, 0, 2, 2]] and hi.tolist() == [[1, 1, 3, 3]]
+
+
+def test_doc_argument_is_validated():
+    q = torch.randn(2, 2, 8, 4)
+    ids = torch.randint(0, 5, (2, 8))
+    lo, hi = ref.doc_bounds(ids, 1)
+    ref.attention_fwd(q, q, q, 0.0, 0, doc=(lo, hi))
+    with pytest.raises(TypeError):
+        ref.attention_fwd(q, q, q, 0.0, 0, doc=(lo.long(), hi))
+    with pytest.raises(ValueError):
+        ref.attention_fwd(q, q, q, 0.0, 0, doc=(lo[:1], hi[:1]))
+    with pytest.raises(ValueError):
+        ref.attention_fwd(q, q, q, 0.0, 0, doc=(lo.t().contiguous().t(), hi))
+    with pytest.raises(TypeError):
+        ref.attention_fwd(q, q, q, 0.0, 0, doc=lo)
+
+
+# ------------------------------------------------ 2. reference ops vs a dense softmax
+def _dense_attention(q, k, v, allowed, keep, p):
+    """Independent few-line attention: softmax over the allowed keys, dropout by ``keep``."""
+    s = (q @ k.transpose(-2, -1)) / math.sqrt(q.shape[-1])
+    prob = torch.softmax(s.masked_fill(~allowed, float("-inf")), dim=-1)
+    if keep is not None:
+        prob = prob * keep / (1.0 - p)
+    return prob @ v
+
+
+def _ids_with_seps(B, S, seps_per_row, sep=SEP):
+    ids = torch.randint(sep + 1, 200, (B, S))
+    for b, seps in enumerate(seps_per_row):
+        for j in seps:
+            ids[b, j] = sep
+    return ids
+
+
+@pytest.mark.parametrize("p", [0.0, 0.2])
+def test_reference_attention_matches_dense_mask_autograd(p):
+    torch.manual_seed(0)
+    B, nh, S, hd = 2, 2, 24, 8
+    ids = _ids_with_seps(B, S, [[0, 5, 6, 17], []])
+    lo, hi = ref.doc_bounds(ids, SEP)
+    q, k, v = (torch.randn(B, nh, S, hd, requires_grad=True) for _ in range(3))
+    key = rng.site_key(3, 1, 0, rng.SITE_ATTN)
+    pos = torch.arange(S)
+    allowed = ((pos.view(1, 1, 1, S) <= pos.view(1, 1, S, 1))
+               & (pos.view(1, 1, 1, S) >= lo.view(B, 1, S, 1))).expand(B, nh, S, S)
+    keep = rng.attn_keep_mask(B * nh, S, S, key, p).view(B, nh, S, S) if p > 0 else None
+    want = _dense_attention(q, k, v, allowed, keep, p)
+    do = torch.randn(B, nh, S, hd)
+    gq, gk, gv = torch.autograd.grad(want, (q, k, v), do)
+
+    o, lse = ref.attention_fwd(q.detach(), k.detach(), v.detach(), p, key, doc=(lo, hi))
+    assert torch.isfinite(o).all() and torch.isfinite(lse).all()
+    assert torch.allclose(o.view(B, S, nh, hd).transpose(1, 2), want, atol=1e-5, rtol=1e-4)
+    s = (q @ k.transpose(-2, -1)).detach() / math.sqrt(hd)
+    assert torch.allclose(lse, torch.logsumexp(s.masked_fill(~allowed, float("-inf")), -1), atol=1e-5)
+    do_rows = do.transpose(1, 2).reshape(B * S, nh * hd)
+    dq, dk, dv = ref.attention_bwd(q.detach(), k.detach(), v.detach(), o, do_rows, lse, p, key, doc=(lo, hi))
+    for a, b, n in ((dq, gq, "dq"), (dk, gk, "dk"), (dv, gv, "dv")):
+        assert torch.allclose(a, b, atol=1e-5, rtol=1e-4), n
+    # the row without a separator is plain causal attention, bit for bit
+    o0, lse0 = ref.attention_fwd(q.detach(), k.detach(), v.detach(), p, key)
+    assert torch.equal(o.view(B, S, -1)[1], o0.view(B, S, -1)[1]) and torch.equal(lse[1], lse0[1])
+    assert not torch.equal(o.view(B, S, -1)[0], o0.view(B, S, -1)[0])
+
+
+def test_reference_packed_path_takes_doc():
+    torch.manual_seed(1)
+    B, nh, S, hd = 2, 2, 16, 8
+    H = nh * hd
+    ids = _ids_with_seps(B, S, [[3, 9], []])
+    doc = ref.doc_bounds(ids, SEP)
+    qkv = torch.randn(B * S, 3 * H)
+    cos, sin = ref.rope_tables(hd, S)
+    q, k, v = ref._split_packed(qkv, B, S, nh)
+    o1, lse1 = ref.attention_fwd(q, k, v, 0.1, 5, doc=doc)
+    o2, lse2 = ref.attention_fwd_packed(qkv, B, S, nh, 0.1, 5, doc=doc)
+    assert torch.equal(o1, o2) and torch.equal(lse1, lse2)
+    do = torch.randn(B * S, H)
+    dq, dk, dv = ref.attention_bwd(q, k, v, o1, do, lse1, 0.1, 5, doc=doc)
+    want = ref.rope_qkv_bwd(dq, dk, dv, cos, sin)
+    got = ref.attention_bwd_packed(qkv, o2, do, lse2, 0.1, 5, B, S, nh, cos, sin, doc=doc)
+    assert torch.equal(got, want)
+
+
+# ------------------------------------------------------------------ 3. eager model
+def tiny(**kw):
+    d = dict(vocab_size=256, hidden_size=64, num_layers=2, num_heads=4, max_seq_len=32, dropout=0.0,
+             attention_dropout=0.0)
+    d.update(kw)
+    return GPTConfig(**d)
+
+
+@pytest.mark.parametrize("flash", [False, True])
+def test_eager_documents_are_isolated(flash):
+    torch.manual_seed(2)
+    m = GPT(tiny(use_flash_attention=flash)).eval()
+    S, cut = 32, 11  # the first document is [0, cut], separator at cut
+    ids = _ids_with_seps(2, S, [[cut, 20], [cut]])
+    edited = ids.clone()
+    edited[:, :cut] = torch.randint(SEP + 1, 200, (2, cut))
+    with torch.no_grad():
+        m.set_doc_separator(SEP)
+        a, _ = m(ids)
+        b, _ = m(edited)
+        assert torch.equal(a[:, cut + 1:], b[:, cut + 1:]), "later documents must not see the first one"
+        assert not torch.equal(a[:, :cut + 1], b[:, :cut + 1])
+        m.set_doc_separator(None)
+        c, _ = m(ids)
+        d, _ = m(edited)
+        assert not torch.equal(c[:, cut + 1:], d[:, cut + 1:]), "without the mask the edit reaches later tokens"
+        # trivial bounds: no separator in the batch -> the unmasked model, bit for bit
+        plain = torch.randint(SEP + 1, 200, (2, S))
+        e, _ = m(plain)
+        m.set_doc_separator(SEP)
+        f, _ = m(plain)
+        assert torch.equal(e, f)
+
+
+def test_doc_separator_is_not_a_config_field():
+    m = GPT(tiny())
+    m.set_doc_separator(SEP)
+    assert m.doc_sep_token == SEP and not hasattr(m.config, "doc_sep_token")
+    assert "doc" not in " ".join(m.state_dict().keys())
+    assert "not" in GPT.generate.__doc__ and "document mask" in GPT.generate.__doc__
+
+
+# ------------------------------------------------- 4. engine (reference ops) vs autograd
+def _rot(x, cos, sin):
+    half = x.shape[-1] // 2
+    x1, x2 = x[..., :half], x[..., half:]
+    return torch.cat([x1 * cos - x2 * sin, x2 * cos + x1 * sin], dim=-1)
+
+
+def _autograd_loss(m, ids, seed, micro, sep, p_attn, p_hidden):
+    """The model as plain autograd ops over ``m``'s parameters, with the engine's
+    counter-hash dropout masks (ops/rng.py) and the dense document mask."""
+    cfg = m.config
+    B, S = ids.shape
+    nh, hd, H = cfg.num_heads, cfg.head_dim, cfg.hidden_size
+    lo, _ = ref.doc_bounds(ids, sep)
+    pos = torch.arange(S)
+    allowed = (pos.view(1, 1, 1, S) <= pos.view(1, 1, S, 1)) & (pos.view(1, 1, 1, S) >= lo.view(B, 1, S, 1))
+    cos, sin = ref.rope_tables(hd, S)
+    cos, sin = cos.view(1, 1, S, hd // 2), sin.view(1, 1, S, hd // 2)
+
+    def drop(x, key, p):
+        return x * rng.keep_mask(x.shape, key, p) / (1.0 - p) if p > 0 else x
+
+    def norm(x, w):
+        return x * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + 1e-6) * w
+
+    x = m.embed_tokens.weight[ids.reshape(-1)]
+    for i, layer in enumerate(m.layers):
+        k_attn, k_resid, k_mlp = (rng.site_key(seed, micro, i, s) for s in (rng.SITE_ATTN, rng.SITE_RESID, rng.SITE_MLP))
+        at = layer.attention
+        n1 = norm(x, layer.input_layernorm.weight)
+        q, k, v = ((n1 @ w.weight.t()).view(B, S, nh, hd).transpose(1, 2) for w in (at.q_proj, at.k_proj, at.v_proj))
+        q, k = _rot(q, cos, sin), _rot(k, cos, sin)
+        keep = rng.attn_keep_mask(B * nh, S, S, k_attn, p_attn).view(B, nh, S, S) if p_attn > 0 else None
+        o = _dense_attention(q, k, v, allowed.expand(B, nh, S, S), keep, p_attn)
+        a = o.transpose(1, 2).reshape(B * S, H) @ at.o_proj.weight.t()
+        x = x + drop(a, k_resid, p_hidden)
+        n2 = norm(x, layer.post_attention_layernorm.weight)
+        mlp = layer.mlp
+        d = (F.silu(n2 @ mlp.gate_proj.weight.t()) * (n2 @ mlp.up_proj.weight.t())) @ mlp.down_proj.weight.t()
+        x = x + drop(d, k_mlp, p_hidden)
+    logits = norm(x, m.norm.weight) @ m.embed_tokens.weight.t()
+    return F.cross_entropy(logits, shift_targets(ids), ignore_index=-100)
+
+
+def _doc_batch(B, S):
+    return _ids_with_seps(B, S, [[4, 5, 19], []] + [[S - 1]] * (B - 2))
+
+
+@pytest.mark.parametrize("recompute,selective", [(False, True), (True, True), (True, False)])
+def test_engine_matches_autograd_with_separator(recompute, selective):
+    torch.manual_seed(3)
+    cfg = tiny(dropout=0.1, attention_dropout=0.1)
+    m1 = GPT(cfg)
+    m2 = copy.deepcopy(m1)
+    ids = _doc_batch(3, 32)
+    l1 = _autograd_loss(m1, ids, seed=21, micro=0, sep=SEP, p_attn=0.1, p_hidden=0.1)
+    l1.backward()
+    m2.set_doc_separator(SEP)  # before the engine exists: enable_engine hands it on
+    eng = m2.enable_engine(seed=21)
+    assert eng.doc_sep_token == SEP
+    eng.selective_recompute = selective
+    m2.gradient_checkpointing = recompute
+    m2.train()
+    _, l2 = m2(ids, labels=ids)
+    l2.backward()
+    assert abs(l1.item() - l2.item()) < 1e-5
+    for (n, p1), (_, p2) in zip(m1.named_parameters(), m2.named_parameters()):
+        assert torch.allclose(p1.grad, p2.grad, atol=1e-6, rtol=1e-4), n
+    # the mask is live: the same step without it gives another loss
+    m3 = copy.deepcopy(m1)
+    m3.zero_grad()
+    m3.enable_engine(seed=21).micro_counter = 0
+    m3.train()
+    _, l3 = m3(ids, labels=ids)
+    assert abs(l3.item() - l2.item()) > 1e-4
+
+
+def test_engine_split_qkv_path_takes_doc():
+    torch.manual_seed(4)
+    cfg = tiny(dropout=0.1, attention_dropout=0.1)
+    base = GPT(cfg)
+    ids = _doc_batch(2, 32)
+    grads = []
+    for packed in (True, False):
+        m = copy.deepcopy(base)
+        e = m.enable_engine(seed=2)
+        m.set_doc_separator(SEP)  # after the engine exists
+        e.packed_qkv = packed and e.packed_qkv
+        m.train()
+        _, loss = m(ids, labels=ids)
+        loss.backward()
+        grads.append([p.grad.clone() for p in m.parameters()])
+    for a, b in zip(*grads):
+        assert torch.allclose(a, b, atol=1e-6, rtol=1e-4)
+
+
+@pytest.mark.parametrize("recompute", [False, True])
+def test_train_window_matches_sequential_with_separator(recompute):
+    torch.manual_seed(5)
+    GA = 2
+    m1 = GPT(tiny(dropout=0.1, attention_dropout=0.1))
+    m1.set_doc_separator(SEP)
+    m2 = copy.deepcopy(m1)
+    e1 = m1.enable_engine(seed=5)
+    e2 = m2.enable_engine(seed=5)
+    m1.gradient_checkpointing = m2.gradient_checkpointing = recompute
+    m1.train()
+    m2.train()
+    data = [_doc_batch(2, 32) for _ in range(GA)]
+    seq = []
+    for j in range(GA):
+        e1.set_accumulation(j, GA, defer=True)
+        _, loss = m1(data[j], labels=data[j])
+        (loss / GA).backward()
+        seq.append(loss.detach())
+    win = e2.train_window(data, [shift_targets(d) for d in data], torch.full((), 1.0 / GA), recompute=recompute)
+    for a, b in zip(seq, win):
+        assert torch.equal(a, b)
+    for (n, p1), (_, p2) in zip(m1.named_parameters(), m2.named_parameters()):
+        assert torch.allclose(p1.grad, p2.grad, atol=1e-7, rtol=1e-6), n
+
+
+def test_eval_loss_applies_the_mask():
+    torch.manual_seed(6)
+    m1 = GPT(tiny())
+    m2 = copy.deepcopy(m1)
+    ids = _doc_batch(2, 32)
+    m1.set_doc_separator(SEP)
+    m2.set_doc_separator(SEP)
+    m2.enable_engine()
+    m1.eval()
+    with torch.no_grad():
+        _, want = m1(ids, labels=ids)
+    got = m2.eval_loss(ids)
+    assert abs(got.item() - want.item()) < 1e-5
+    m2.set_doc_separator(None)
+    assert abs(m2.eval_loss(ids).item() - want.item()) > 1e-5
+
+
+def test_routes_without_the_mask_say_so():
+    """The choice is made from (device, head_dim, dtype) alone, so it needs no GPU."""
+    from distributed_llm_trainer_amd import ops
+    ops.check_doc_mask("cpu", 160, torch.float32)       # reference ops mask densely
+    ops.check_doc_mask("cuda", 64, torch.bfloat16)
+    ops.check_doc_mask("cuda", 128, torch.float16)
+    ops.check_doc_mask("cuda", 96, torch.bfloat16)      # zero-padded onto the flash kernels
+    with pytest.raises(NotImplementedError, match="GEMM-formulated"):
+        ops.check_doc_mask("cuda", 160, torch.bfloat16)
+    with pytest.raises(NotImplementedError, match="fp32"):
+        ops.check_doc_mask("cuda", 64, torch.float32)
+    with pytest.raises(NotImplementedError, match="fp32"):
+        ops.check_doc_mask("cuda", 96, torch.float32)
+
+
+# ------------------------------------------------------------------ 5. configuration
+def test_cli_yaml_precedence(tmp_path):
+    from distributed_llm_trainer_amd.training import ddp_trainer, fsdp_trainer
+    from distributed_llm_trainer_amd.training.configs import FSDPTrainingConfig, TrainingConfig
+    from distributed_llm_trainer_amd.utils.config_loader import load_yaml_config
+    assert TrainingConfig().doc_sep_token is None and FSDPTrainingConfig().doc_sep_token is None
+    y = tmp_path / "c.yaml"
+    y.write_text("training:\n  doc_sep_token: 50256\n  max_steps: 3\n")
+    for mod, cfg_cls in ((ddp_trainer, TrainingConfig), (fsdp_trainer, FSDPTrainingConfig)):
+        parser = mod.build_parser()
+        assert parser.parse_args([]).doc_sep_token is None
+        assert parser.parse_args(["--doc_sep_token", "10"]).doc_sep_token == 10
+        _, tc, _, _ = load_yaml_config(str(y), GPTConfig.from_preset("small"), cfg_cls(), None)
+        assert tc.doc_sep_token == 50256 and isinstance(tc.doc_sep_token, int)
+    y2 = tmp_path / "d.yaml"
+    y2.write_text("training:\n  max_steps: 3\n")
+    _, tc, _, _ = load_yaml_config(str(y2), GPTConfig.from_preset("small"), TrainingConfig(), None)
+    assert tc.doc_sep_token is None
+
+
+TINY = """
+model:
+  vocab_size: 256
+  hidden_size: 64
+  num_layers: 2
+  num_heads: 2
+  max_seq_len: 32
+training:
+  batch_size: 2
+  gradient_accumulation_steps: 2
+  learning_rate: 0.001
+  warmup_steps: 2
+  log_interval: 1
+  doc_sep_token: 33
+"""
+
+
+def test_ddp_trainer_cli_with_separator(tmp_path):
+    """Three steps on a small text file with the byte tokenizer and separator = newline
+    (10): the YAML names another id and the CLI flag wins; the loss is finite and
+    --eval_batches evaluates with the same setting."""
+    from distributed_llm_trainer_amd.training import ddp_trainer
+    text = tmp_path / "train.txt"
+    text.write_text("".join(f"story {i}: the cat sat on mat number {i * 7}.\n" for i in range(300)))
+    held = tmp_path / "held.txt"
+    held.write_text("".join(f"tale {i}: a dog ran to park number {i * 3}.\n" for i in range(150)))
+    y = tmp_path / "c.yaml"
+    y.write_text(TINY)
+    mj = str(tmp_path / "m.jsonl")
+    common = ["--config", str(y), "--dataset", "tinystories", "--data_path", str(text), "--tokenizer", "byte",
+              "--max_steps", "3", "--eval_batches", "1", "--eval_interval", "2", "--eval_data_path", str(held),
+              "--no_final_save", "--checkpoint_dir", str(tmp_path / "ck")]
+    tr = ddp_trainer.main(common + ["--doc_sep_token", "10", "--metrics_jsonl", mj])
+    assert tr.training_config.doc_sep_token == 10 and tr.model.doc_sep_token == 10
+    assert tr.model.engine is None or tr.model.engine.doc_sep_token == 10
+    recs = [json.loads(line) for line in open(mj)]
+    losses = [r["loss"] for r in recs if "loss" in r]
+    vals = [r["val_loss"] for r in recs if "val_loss" in r]
+    assert len(losses) == 3 and all(math.isfinite(x) for x in losses)
+    assert vals and all(math.isfinite(x) for x in vals)
+    # YAML alone: its value is used; and it changes what the model computes
+    mj2 = str(tmp_path / "m2.jsonl")
+    tr2 = ddp_trainer.main(common + ["--metrics_jsonl", mj2])
+    assert tr2.training_config.doc_sep_token == 33 and tr2.model.doc_sep_token == 33
+    losses2 = [r["loss"] for r in map(json.loads, open(mj2)) if "loss" in r]
+    assert losses2[0] != losses[0]

@@ -1,5 +1,13 @@
-"""Micro-benchmark of the attention kernels at the headline shape (B8 nh12 S1024 hd64)."""
+"""Micro-benchmark of the attention kernels at the headline shape (B8 nh12 S1024 hd64).
+
+``--doc_len N`` also times the document-masked kernels (``doc=``) in the same run: a
+separator every N tokens (N >= S: no boundary inside the sequence, i.e. trivial bounds --
+the cost of the DOC instantiations themselves), or ``rand:N``: seeded geometric document
+lengths with mean N, different in every batch row.  The backward is one call (dQ then
+dK/dV); a kernel trace of this tool (``tools/ab/prof_step.sh`` style: ``rocprofv3
+--kernel-trace --stats``) splits it per kernel."""
 import argparse
+import math
 import os
 import sys
 
@@ -7,6 +15,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from distributed_llm_trainer_amd.ops import hip, rng  # noqa: E402
+
+SEP = 0  # separator id of the synthetic token rows (every other token is 1)
 
 
 def timeit(fn, iters=20):
@@ -22,6 +32,35 @@ def timeit(fn, iters=20):
     return s.elapsed_time(e) / iters * 1e3  # us
 
 
+def doc_ids(spec: str, B: int, S: int, seed: int = 0) -> torch.Tensor:
+    """Token rows [B, S] whose separators realise ``spec`` (``N`` or ``rand:N``)."""
+    ids = torch.ones(B, S, dtype=torch.int64)
+    if spec.startswith("rand:"):
+        mean = float(spec[5:])
+        g = torch.Generator().manual_seed(seed)
+        for b in range(B):
+            pos = -1
+            while True:  # geometric lengths >= 1 with the given mean
+                u = torch.rand((), generator=g).item()
+                pos += 1 + (int(math.log1p(-u) / math.log1p(-1.0 / mean)) if mean > 1 else 0)
+                if pos >= S:
+                    break
+                ids[b, pos] = SEP
+    else:
+        n = int(spec)
+        if n < 1:
+            raise ValueError("--doc_len must be >= 1")
+        ids[:, n - 1::n] = SEP
+    return ids
+
+
+def attended_fraction(doc, S: int) -> float:
+    """Scores inside the mask, relative to the causal triangle."""
+    lo = doc[0].long()
+    q = torch.arange(S, device=lo.device)
+    return float((q - lo + 1).sum()) / (lo.shape[0] * S * (S + 1) / 2)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=8)
@@ -31,30 +70,47 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--packed", action="store_true", help="attention on the packed [B*S, 3H] QKV (engine default)")
     ap.add_argument("--dtype", default="bf16", choices=("bf16", "fp16"))
+    ap.add_argument("--doc_len", default=None, metavar="N|rand:N",
+                    help="also time the document-masked kernels: a separator every N tokens, or seeded geometric "
+                         "lengths with mean N (rand:N); N >= S gives trivial bounds")
+    ap.add_argument("--only", default="both", choices=("both", "off", "doc"),
+                    help="which variants to run (a kernel trace of one variant: --only off / --only doc)")
     a = ap.parse_args()
     dt = torch.bfloat16 if a.dtype == "bf16" else torch.float16
     torch.manual_seed(0)
     q, k, v = (torch.randn(a.B, a.nh, a.S, 64, device="cuda").to(dt) for _ in range(3))
     key = rng.site_key(1, 2, 3, rng.SITE_ATTN)
-    if a.packed:
-        qkv = torch.randn(a.B * a.S, 3 * a.nh * 64, device="cuda").to(dt)
-        cos, sin = hip.rope_tables(64, a.S, device="cuda")
-        o, aux = hip.attention_fwd_packed(qkv, a.B, a.S, a.nh, a.p, key)
-        do = torch.randn_like(o)
-        t_f = timeit(lambda: hip.attention_fwd_packed(qkv, a.B, a.S, a.nh, a.p, key), a.iters)
-        t_b = timeit(lambda: hip.attention_bwd_packed(qkv, o, do, aux, a.p, key, a.B, a.S, a.nh, cos, sin), a.iters)
-        if a.p > 0:  # the forward kernel alone (keep bits already generated) -> bits kernel time
-            m = aux[1]
-            if m is not None:
-                t_k = timeit(lambda: hip.attention_fwd_packed(qkv, a.B, a.S, a.nh, a.p, key, mask=m), a.iters)
-                print(f"fwd kernel {t_k:.1f} us, keep-bit kernel {t_f - t_k:.1f} us")
-    else:
-        o, aux = hip.attention_fwd(q, k, v, a.p, key)
-        do = torch.randn_like(o)
-        t_f = timeit(lambda: hip.attention_fwd(q, k, v, a.p, key), a.iters)
-        t_b = timeit(lambda: hip.attention_bwd(q, k, v, o, do, aux, a.p, key), a.iters)
+    variants = []
+    if a.only != "doc" or a.doc_len is None:
+        variants.append(("causal", {}))
+    if a.doc_len is not None and a.only != "off":
+        doc = hip.doc_bounds(doc_ids(a.doc_len, a.B, a.S).cuda(), SEP)
+        variants.append((f"doc_len {a.doc_len} ({100 * attended_fraction(doc, a.S):.1f} % of the causal scores)",
+                         {"doc": doc}))
     fl = 4 * a.B * a.nh * a.S * a.S / 2 * 64
-    print(f"fwd {t_f:.1f} us ({fl / t_f / 1e6:.1f} TF/s)  bwd {t_b:.1f} us ({2.5 * fl / t_b / 1e6:.1f} TF/s)")
+    for name, kw in variants:
+        tag = f"[{name}] " if a.doc_len is not None else ""  # the plain run prints what it always has
+        if a.packed:
+            qkv = torch.randn(a.B * a.S, 3 * a.nh * 64, device="cuda").to(dt)
+            cos, sin = hip.rope_tables(64, a.S, device="cuda")
+            o, aux = hip.attention_fwd_packed(qkv, a.B, a.S, a.nh, a.p, key, **kw)
+            do = torch.randn_like(o)
+            t_f = timeit(lambda: hip.attention_fwd_packed(qkv, a.B, a.S, a.nh, a.p, key, **kw), a.iters)
+            t_b = timeit(lambda: hip.attention_bwd_packed(qkv, o, do, aux, a.p, key, a.B, a.S, a.nh, cos, sin, **kw),
+                         a.iters)
+            if a.p > 0:  # the forward kernel alone (keep bits already generated) -> bits kernel time
+                m = aux[1]
+                if m is not None:
+                    t_k = timeit(lambda: hip.attention_fwd_packed(qkv, a.B, a.S, a.nh, a.p, key, mask=m, **kw),
+                                 a.iters)
+                    print(f"{tag}fwd kernel {t_k:.1f} us, keep-bit kernel {t_f - t_k:.1f} us")
+        else:
+            o, aux = hip.attention_fwd(q, k, v, a.p, key, **kw)
+            do = torch.randn_like(o)
+            t_f = timeit(lambda: hip.attention_fwd(q, k, v, a.p, key, **kw), a.iters)
+            t_b = timeit(lambda: hip.attention_bwd(q, k, v, o, do, aux, a.p, key, **kw), a.iters)
+        # TF/s by the causal FLOP count for every variant, so the rows compare as times do
+        print(f"{tag}fwd {t_f:.1f} us ({fl / t_f / 1e6:.1f} TF/s)  bwd {t_b:.1f} us ({2.5 * fl / t_b / 1e6:.1f} TF/s)")
 
 
 if __name__ == "__main__":
