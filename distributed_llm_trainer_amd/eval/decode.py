@@ -24,7 +24,8 @@ import torch.nn.functional as F
 
 class KVCache:
     def __init__(self, cfg, B: int, device, dtype):
-        self.k = [torch.zeros(B, cfg.num_heads, cfg.max_seq_len, cfg.head_dim, device=device, dtype=dtype)
+        # grouped-query attention: the cache holds the num_kv_heads K/V heads (not repeated)
+        self.k = [torch.zeros(B, cfg.num_kv_heads, cfg.max_seq_len, cfg.head_dim, device=device, dtype=dtype)
                   for _ in range(cfg.num_layers)]
         self.v = [torch.zeros_like(t) for t in self.k]
         self.len = 0
@@ -41,6 +42,24 @@ def _rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Tensor
     c, s = cos[None, :, None, :], sin[None, :, None, :]
     x1, x2 = x[..., :half], x[..., half:]
     return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1)
+
+
+def _split_qkv(qkv: torch.Tensor, cfg):
+    """Packed projection [B, T, H + 2*KV] fp32 -> q [B, T, nh, hd], k, v [B, T, nkv, hd]."""
+    B, T, _ = qkv.shape
+    nh, nkv, hd = cfg.num_heads, cfg.num_kv_heads, cfg.head_dim
+    if nkv == nh:
+        t = qkv.view(B, T, 3, nh, hd)
+        return t[:, :, 0], t[:, :, 1], t[:, :, 2]
+    H, KV = nh * hd, nkv * hd
+    return (qkv[..., :H].view(B, T, nh, hd), qkv[..., H:H + KV].view(B, T, nkv, hd),
+            qkv[..., H + KV:].view(B, T, nkv, hd))
+
+
+def _rep_kv(t: torch.Tensor, cfg) -> torch.Tensor:
+    """Cached K or V [B, nkv, S, hd] repeated over each group's query heads."""
+    G = cfg.num_heads // cfg.num_kv_heads
+    return t if G == 1 else t.repeat_interleave(G, dim=1)
 
 
 @torch.no_grad()
@@ -63,14 +82,13 @@ def forward_cached(model, ids: torch.Tensor, cache: KVCache) -> torch.Tensor:
         prov.pre_forward(i)
         w = prov.layer(i)
         n1 = _rms(h, w.ln1, eng.eps).to(dt)
-        qkv = torch.matmul(n1, w.wqkv.t()).float().view(B, T, 3, nh, hd)
-        q = _rope(qkv[:, :, 0], cos, sin)
-        k = _rope(qkv[:, :, 1], cos, sin)
-        v = qkv[:, :, 2]
+        q, k, v = _split_qkv(torch.matmul(n1, w.wqkv.t()).float(), cfg)
+        q = _rope(q, cos, sin)
+        k = _rope(k, cos, sin)
         cache.k[i][:, :, p0:p0 + T] = k.transpose(1, 2).to(dt)
         cache.v[i][:, :, p0:p0 + T] = v.transpose(1, 2).to(dt)
-        K = cache.k[i][:, :, :p0 + T].float()
-        Vv = cache.v[i][:, :, :p0 + T].float()
+        K = _rep_kv(cache.k[i][:, :, :p0 + T].float(), cfg)
+        Vv = _rep_kv(cache.v[i][:, :, :p0 + T].float(), cfg)
         qh = q.to(dt).float().transpose(1, 2)  # [B, nh, T, hd]
         s = torch.matmul(qh, K.transpose(-2, -1)) * scale
         if T > 1:
@@ -187,15 +205,15 @@ class DecodeGraph:
         for i in range(cfg.num_layers):
             w = prov.layer(i)
             n1 = _rms(h, w.ln1, eng.eps).to(dt)
-            qkv = torch.matmul(n1, w.wqkv.t()).float().view(B, 1, 3, nh, hd)
-            q = _rope(qkv[:, :, 0], cos, sin)
-            k = _rope(qkv[:, :, 1], cos, sin)
+            q, k, v = _split_qkv(torch.matmul(n1, w.wqkv.t()).float(), cfg)
+            q = _rope(q, cos, sin)
+            k = _rope(k, cos, sin)
             cache.k[i].index_copy_(2, self.pos, k.transpose(1, 2).to(dt))
-            cache.v[i].index_copy_(2, self.pos, qkv[:, :, 2].transpose(1, 2).to(dt))
+            cache.v[i].index_copy_(2, self.pos, v.transpose(1, 2).to(dt))
             qh = q.to(dt).transpose(1, 2)  # [B, nh, 1, hd]; bf16 GEMVs straight on the bf16 cache
-            s_ = torch.matmul(qh, cache.k[i].transpose(-2, -1)).float() * scale
+            s_ = torch.matmul(qh, _rep_kv(cache.k[i], cfg).transpose(-2, -1)).float() * scale
             pr = torch.softmax(s_.masked_fill(masked, float("-inf")), dim=-1)
-            o = torch.matmul(pr.to(dt), cache.v[i]).transpose(1, 2).reshape(B, 1, nh * hd)
+            o = torch.matmul(pr.to(dt), _rep_kv(cache.v[i], cfg)).transpose(1, 2).reshape(B, 1, nh * hd)
             h = h + torch.matmul(o, w.wo.t()).float()
             n2 = _rms(h, w.ln2, eng.eps).to(dt)
             gu = torch.matmul(n2, w.wgu.t()).float()
@@ -222,9 +240,12 @@ def _fused_ok(model, B: int) -> bool:
     the LDS its kernels need fits one CU: ``k_dec_attn`` keeps all ``max_seq_len``
     scores of a (batch, head) in LDS (maxS * 4 + 1056 B: max_seq_len <= ~40.7k), the
     norm + GEMV kernels one normed bf16 row per batch entry (``dec_lds`` in decode.hip).
-    Beyond that ``DecodeGraph`` captures the ATen step instead."""
+    Beyond that ``DecodeGraph`` captures the ATen step instead.  The fused kernels are
+    multi-head only: a grouped-query model (num_kv_heads < num_heads) takes the ATen step."""
     ops = model.engine.ops
     cfg = model.config
+    if cfg.num_kv_heads != cfg.num_heads:
+        return False
     attn_lds = cfg.max_seq_len * 4 + 8 * 4 + 4 * 64 * 4
     norm_lds = B * cfg.hidden_size * 2 + B * 4 * 4 + B * 16 * 4
     return (hasattr(ops, "dec_norm_qkv") and B in getattr(ops, "DECODE_BATCHES", ())

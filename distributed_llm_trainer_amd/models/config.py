@@ -48,12 +48,21 @@ class GPTConfig:
     use_flash_attention: bool = False
     gradient_checkpointing: bool = False
 
+    # Grouped-query attention: K/V heads (None = num_heads, plain multi-head attention;
+    # 1 = multi-query).  Query head h attends with kv head h // (num_heads // num_kv_heads).
+    num_kv_heads: Optional[int] = None
+
     def __post_init__(self) -> None:
         if self.intermediate_size is None:
             self.intermediate_size = 4 * self.hidden_size
         assert self.hidden_size % self.num_heads == 0, (
             f"hidden_size ({self.hidden_size}) must be divisible by num_heads ({self.num_heads})"
         )
+        if self.num_kv_heads is None:
+            self.num_kv_heads = self.num_heads
+        if self.num_kv_heads < 1 or self.num_heads % self.num_kv_heads != 0:
+            raise ValueError(
+                f"num_kv_heads ({self.num_kv_heads}) must divide num_heads ({self.num_heads})")
 
     # ------------------------------------------------------------------ presets
     @classmethod
@@ -94,10 +103,15 @@ class GPTConfig:
     def vocab_size_padded(self) -> int:
         return ((self.vocab_size + 63) // 64) * 64
 
+    @property
+    def kv_size(self) -> int:
+        """Width of the K (and of the V) projection: num_kv_heads * head_dim."""
+        return self.num_kv_heads * self.head_dim
+
     def num_parameters(self) -> int:
         """True trainable parameter count (tied embedding counted once)."""
         h, i = self.hidden_size, self.intermediate_size
-        per_layer = 4 * h * h + 3 * h * i + 2 * h
+        per_layer = 2 * h * h + 2 * self.kv_size * h + 3 * h * i + 2 * h
         return self.vocab_size * h + self.num_layers * per_layer + h
 
     def num_parameters_legacy(self) -> int:
@@ -115,14 +129,30 @@ class GPTConfig:
         """
         s = seq_len or self.max_seq_len
         h, i, L, v = self.hidden_size, self.intermediate_size, self.num_layers, self.vocab_size
-        dense = 2 * (4 * h * h + 3 * h * i) * L + 2 * h * v
+        dense = 2 * (2 * h * h + 2 * self.kv_size * h + 3 * h * i) * L + 2 * h * v
         attn = 2 * 2 * s * h * L * (0.5 if causal else 1.0)
         fwd = dense + attn
         return fwd * (4.0 if recompute else 3.0)
 
     # ------------------------------------------------------------- (de)serialise
     def to_dict(self) -> Dict[str, Any]:
-        return asdict(self)
+        d = asdict(self)
+        if self.num_kv_heads == self.num_heads:  # MHA configs stay what they were
+            del d["num_kv_heads"]
+        return d
+
+    # Pickled configs (checkpoints) follow to_dict(): an MHA config carries no num_kv_heads,
+    # so its pickle is what it was before the field existed and older pickles load.
+    def __getstate__(self) -> Dict[str, Any]:
+        state = dict(self.__dict__)
+        if state.get("num_kv_heads") == state.get("num_heads"):
+            state.pop("num_kv_heads", None)
+        return state
+
+    def __setstate__(self, state: Dict[str, Any]) -> None:
+        self.__dict__.update(state)
+        if self.__dict__.get("num_kv_heads") is None:
+            self.num_kv_heads = self.num_heads
 
     @classmethod
     def from_dict(cls, d: Dict[str, Any]) -> "GPTConfig":

@@ -66,7 +66,7 @@ def _drain(gen):
 
 @dataclass
 class LayerWeights:
-    wqkv: torch.Tensor   # [3H, H] compute dtype (rows: q | k | v)
+    wqkv: torch.Tensor   # [H + 2*KV, H] compute dtype (rows: q | k | v; KV = H without GQA)
     wo: torch.Tensor     # [H, H]
     wgu: torch.Tensor    # [2I, H] (rows: gate | up)
     wdown: torch.Tensor  # [H, I]
@@ -245,6 +245,18 @@ class GPTEngine:
         # inverse RoPE in the backward epilogue); DLT_PACKED_QKV=0 -> split q/k/v copies
         self.packed_qkv = (hasattr(ops, "attention_fwd_packed")
                            and os.environ.get("DLT_PACKED_QKV", "1") != "0")
+        # grouped-query attention (cfg.num_kv_heads < num_heads): the packed QKV is
+        # [M, H + 2*KV], and the attention-side ops take nkv=.  MHA passes no keyword,
+        # so its calls are what they were.
+        self.qkv_width = cfg.hidden_size + 2 * cfg.kv_size
+        self.gqa = cfg.num_kv_heads != cfg.num_heads
+        self.gqa_kw = {"nkv": cfg.num_kv_heads} if self.gqa else {}
+        if self.gqa and getattr(ops, "backend", "") == "hip":
+            from ..ops import check_gqa
+            check_gqa("cuda", cfg.head_dim, act_dtype)
+            if not self.packed_qkv:
+                raise NotImplementedError("grouped-query attention on the GPU runs on the packed QKV layout "
+                                          "(DLT_PACKED_QKV=0 is not supported with num_kv_heads < num_heads)")
         # last layers of the deferred-wgrad backward whose weight gradients run on the
         # current stream instead of the side stream (see _backward_gen)
         self.main_wgrad_layers = int(os.environ.get("DLT_MAIN_WGRAD_LAYERS", "1"))
@@ -453,7 +465,7 @@ class GPTEngine:
             return False, False, False
         cfg = self.cfg
         per_layer_chains = cfg.num_layers * 2 * (2 if self.act_dtype == torch.bfloat16 else 4)
-        qkv = M * 3 * cfg.hidden_size * per_layer_chains
+        qkv = M * (cfg.hidden_size + 2 * cfg.kv_size) * per_layer_chains
         gu = M * 2 * cfg.intermediate_size * per_layer_chains
         rest = M * (2 * cfg.hidden_size + cfg.intermediate_size) * per_layer_chains
         keep_qkv = qkv <= self.ac_budget
@@ -479,7 +491,7 @@ class GPTEngine:
         mask, mask_ev = self._attn_mask_async(B, S, pa, k_attn, dv)
         x, n1, rstd1 = ops.add_dropout_rmsnorm_fwd(r, d, w.ln1, self.eps, p_d, key_d, self.act_dtype,
                                                    y_out=sb("n1", H))
-        fused_rope = self.packed_qkv and hasattr(gm, "linear_rope")
+        fused_rope = self.packed_qkv and hasattr(gm, "linear_rope") and not self.gqa
         if fused_rope:  # QKV GEMM with RoPE on q/k in its epilogue (when that races faster)
             qkv = gm.linear_rope(n1, w.wqkv, B, S, cfg.num_heads, cos, sin, ops)
         else:
@@ -504,11 +516,12 @@ class GPTEngine:
             kw["store_mask"] = keep
         if self.packed_qkv:
             if not fused_rope:
-                ops.rope_qk_inplace(qkv, B, S, cfg.num_heads, cos, sin)
-            o, lse = ops.attention_fwd_packed(qkv, B, S, cfg.num_heads, pa, k_attn, out=sb("o", H), **kw)
+                ops.rope_qk_inplace(qkv, B, S, cfg.num_heads, cos, sin, **self.gqa_kw)
+            o, lse = ops.attention_fwd_packed(qkv, B, S, cfg.num_heads, pa, k_attn, out=sb("o", H), **kw,
+                                              **self.gqa_kw)
             q, k, v = qkv, None, None
         else:
-            q, k, v = ops.rope_qkv_fwd(qkv, B, S, cfg.num_heads, cos, sin)
+            q, k, v = ops.rope_qkv_fwd(qkv, B, S, cfg.num_heads, cos, sin, **self.gqa_kw)
             o, lse = ops.attention_fwd(q, k, v, pa, k_attn, True, out=sb("o", H), **kw)
         del qkv
         a = gm.linear(o, w.wo)
@@ -566,16 +579,16 @@ class GPTEngine:
         if c.q is not None:  # QKV output kept by the forward (_ac_keep)
             qkv = c.q
             q, k, v = qkv, None, None
-        elif self.packed_qkv and hasattr(gm, "linear_rope"):
+        elif self.packed_qkv and hasattr(gm, "linear_rope") and not self.gqa:
             qkv = gm.linear_rope(n1, w.wqkv, B, S, cfg.num_heads, cos, sin, ops)
             q, k, v = qkv, None, None
         elif self.packed_qkv:
             qkv = gm.linear(n1, w.wqkv)
-            ops.rope_qk_inplace(qkv, B, S, cfg.num_heads, cos, sin)
+            ops.rope_qk_inplace(qkv, B, S, cfg.num_heads, cos, sin, **self.gqa_kw)
             q, k, v = qkv, None, None
         else:
             qkv = gm.linear(n1, w.wqkv)
-            q, k, v = ops.rope_qkv_fwd(qkv, B, S, cfg.num_heads, cos, sin)
+            q, k, v = ops.rope_qkv_fwd(qkv, B, S, cfg.num_heads, cos, sin, **self.gqa_kw)
         del qkv
         _, n2, rstd2 = ops.add_dropout_rmsnorm_fwd(c.x2, None, w.ln2, self.eps, 0.0, 0, self.act_dtype,
                                                    y_out=sb("n2", H))
@@ -1045,12 +1058,12 @@ class GPTEngine:
             do = gm.linear_dgrad(da, w.wo)
             if c.k is None:  # packed: dq/dk/dv land in [M, 3H] with the inverse RoPE applied
                 dqkv = ops.attention_bwd_packed(c.q, c.o, do, c.lse, pa, k_attn, B, S, cfg.num_heads, cos, sin,
-                                                out=sb(i, "dqkv", 3 * H), **dkw)
+                                                out=sb(i, "dqkv", self.qkv_width), **dkw, **self.gqa_kw)
                 del do
             else:
                 dq, dk, dv = ops.attention_bwd(c.q, c.k, c.v, c.o, do, c.lse, pa, k_attn, True, **dkw)
                 del do
-                dqkv = ops.rope_qkv_bwd(dq, dk, dv, cos, sin, out=sb(i, "dqkv", 3 * H))
+                dqkv = ops.rope_qkv_bwd(dq, dk, dv, cos, sin, out=sb(i, "dqkv", self.qkv_width))
                 del dq, dk, dv
             dn1 = gm.linear_dgrad(dqkv, w.wqkv)
             key_prev = self._keys(st.micro, i - 1)[2] if i > 0 else 0
@@ -1088,7 +1101,7 @@ class GPTEngine:
                 if dfl["o"]:
                     grp.append((gr.wo, full(i, "da", H), full(i, "o", H)))
                 if dfl["qkv"]:
-                    grp.append((gr.wqkv, full(i, "dqkv", 3 * H), full(i, "n1", H)))
+                    grp.append((gr.wqkv, full(i, "dqkv", self.qkv_width), full(i, "n1", H)))
                 _wgrad_group(gm, grp)
                 if self._ring:
                     ev = torch.cuda.Event()

@@ -84,10 +84,13 @@ class CausalSelfAttention(nn.Module):
         self.config = config
         self.num_heads = config.num_heads
         self.head_dim = config.hidden_size // config.num_heads
-        h = config.hidden_size
+        # grouped-query attention: num_kv_heads K/V heads, each shared by a group of
+        # num_heads // num_kv_heads consecutive query heads (num_kv_heads == num_heads: MHA)
+        self.num_kv_heads = config.num_kv_heads
+        h, kv = config.hidden_size, config.num_kv_heads * self.head_dim
         self.q_proj = nn.Linear(h, h, bias=False)
-        self.k_proj = nn.Linear(h, h, bias=False)
-        self.v_proj = nn.Linear(h, h, bias=False)
+        self.k_proj = nn.Linear(h, kv, bias=False)
+        self.v_proj = nn.Linear(h, kv, bias=False)
         self.o_proj = nn.Linear(h, h, bias=False)
         self.attn_dropout = nn.Dropout(config.attention_dropout)
         self.resid_dropout = nn.Dropout(config.dropout)
@@ -101,10 +104,14 @@ class CausalSelfAttention(nn.Module):
         the causal mask in both the naive and the SDPA setting."""
         B, S, _ = hidden_states.shape
         q = self.q_proj(hidden_states).view(B, S, self.num_heads, self.head_dim).transpose(1, 2)
-        k = self.k_proj(hidden_states).view(B, S, self.num_heads, self.head_dim).transpose(1, 2)
-        v = self.v_proj(hidden_states).view(B, S, self.num_heads, self.head_dim).transpose(1, 2)
+        k = self.k_proj(hidden_states).view(B, S, self.num_kv_heads, self.head_dim).transpose(1, 2)
+        v = self.v_proj(hidden_states).view(B, S, self.num_kv_heads, self.head_dim).transpose(1, 2)
         cos, sin = self.rotary_emb(q, S)
         q, k = apply_rotary_pos_emb(q, k, cos[None, None], sin[None, None])
+        if self.num_kv_heads != self.num_heads:  # query head h uses kv head h // G
+            G = self.num_heads // self.num_kv_heads
+            k = k.repeat_interleave(G, dim=1)
+            v = v.repeat_interleave(G, dim=1)
         if self.use_flash and doc_hidden is not None:
             causal = torch.tril(torch.ones(S, S, device=hidden_states.device, dtype=torch.bool))
             out = F.scaled_dot_product_attention(
@@ -217,6 +224,8 @@ class GPT(nn.Module):
             act_dtype = torch.bfloat16 if dev.type == "cuda" else torch.float32
         if compute_dtype is None:
             compute_dtype = act_dtype
+        if self.config.num_kv_heads != self.config.num_heads and (ops is None or ops.backend == "hip"):
+            ops_mod.check_gqa(dev, self.config.head_dim, act_dtype)  # before anything is re-homed
         if provider is None:
             from ..parallel.flat import FlatParamStore
             provider = FlatParamStore(self, dev, compute_dtype=compute_dtype)

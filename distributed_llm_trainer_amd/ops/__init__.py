@@ -65,6 +65,24 @@ def check_doc_mask(device, head_dim: int = 64, act_dtype=torch.bfloat16) -> None
         hip_f32._no_doc(True)
 
 
+def check_gqa(device, head_dim: int = 64, act_dtype=torch.bfloat16) -> None:
+    """Raises NotImplementedError when the attention route :func:`for_device` picks for
+    this model has no grouped-query attention (``nkv=``): on the GPU only the 16-bit flash
+    kernels at their native head_dims 64 / 128 implement it; the zero-padded heads, the
+    GEMM-formulated route and the fp32 kernels do not.  Called when the engine is enabled,
+    so the error comes before the first step, not inside it."""
+    if torch.device(device).type != "cuda" or os.environ.get("DLT_ALLOW_REFERENCE_ON_GPU") == "1":
+        return
+    from .hip import ATTN_HEAD_DIMS
+    if act_dtype == torch.float32:
+        raise NotImplementedError("grouped-query attention (num_kv_heads < num_heads) is not implemented for fp32 "
+                                  "activations on the GPU: use bf16 or fp16")
+    if head_dim not in ATTN_HEAD_DIMS:
+        raise NotImplementedError(f"grouped-query attention (num_kv_heads < num_heads) needs head_dim in "
+                                  f"{tuple(ATTN_HEAD_DIMS)} on the GPU; head_dim {head_dim} would run zero-padded "
+                                  f"or as GEMMs, which have no grouped K/V")
+
+
 def for_device(device, head_dim: int = 64, act_dtype=torch.bfloat16) -> types.SimpleNamespace:
     """Op namespace for ``device``.  On the GPU every op is a HIP kernel: bf16 / fp16
     activations on the 16-bit kernels, fp32 (``--mixed_precision fp32``) on the fp32

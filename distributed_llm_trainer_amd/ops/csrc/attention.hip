@@ -33,6 +33,12 @@
 //    item starts at the tile of its smallest lo, the Q/dO loop of dK/dV ends at the tile
 //    of its largest hi, and only tiles that straddle a bound take the masked kind.
 //
+//  * Grouped-query attention (GQA instantiations): nkv = nh / G K/V heads, query head h
+//    uses kv head h / G.  Forward and dQ only move the K/V base (the per-query-head
+//    arithmetic is the MHA kernel's); a dK/dV work item is 64 keys of one KV head and
+//    runs the Q/dO tile pipeline once per query head of the group, in fixed order, with
+//    dK/dV staying in registers -- no atomics, bitwise reproducible.
+//
 // Layouts: q, k, v, dq, dk, dv: strided views -- head-major [B*nh, S, 64] or the
 // packed [B*S, 3, nh, 64] QKV GEMM output (see dlt_attn_fwd_ex); o, do: [B, S, nh, 64]
 // bf16 (= the [M, H] GEMM layout);  lse, delta: [B*nh, S] fp32 (natural-log lse).
@@ -610,13 +616,15 @@ __device__ __forceinline__ void doc_k_range(const int* __restrict__ hrow, int kb
 // so its instantiation may take the whole 512-register file (one wave per SIMD).
 #define ATTN_WAVES(D) __attribute__((amdgpu_waves_per_eu(D == 64 ? 2 : 1, 2)))
 // DOC: dlo = lo [B, S] of the document mask (see the header); unused otherwise.
-template <bool DROP, int HK, int D, bool DOC = false>
+// GQA: k / v have nh / G heads with their own strides (kv_bs, kv_hs, kv_rs); unused otherwise.
+template <bool DROP, int HK, int D, bool DOC = false, bool GQA = false>
 __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_fwd(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                     const bf16_t* __restrict__ v, bf16_t* __restrict__ o,
                                                     float* __restrict__ lse, const uint32_t* __restrict__ mask,
                                                     int S, int nh, float c_log2, float dscale, long in_bs,
                                                     int in_hs, int in_rs, int xcd_map,
-                                                    const int* __restrict__ dlo = nullptr) {
+                                                    const int* __restrict__ dlo = nullptr, int G = 1,
+                                                    long kv_bs = 0, int kv_hs = 0, int kv_rs = 0) {
   __shared__ __attribute__((aligned(16))) bf16_t lds[2 * 2 * KVB * D];  // [buf][K|V][64][D]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -626,6 +634,9 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_fwd(const bf16_t* __r
   const bool lpt = work_item(nrb, xcd_map, bh, pair);
   const int b = bh / nh, head = bh % nh;
   const size_t hin = (size_t)b * in_bs + (size_t)head * in_hs;  // (b, head) base of q / k / v
+  // GQA: k / v base of kv head head / G; everything else stays per query head
+  const size_t hkv = GQA ? (size_t)b * kv_bs + (size_t)(head / G) * kv_hs : hin;
+  const int krs = GQA ? kv_rs : in_rs;
   const int W = (S + 31) >> 5;
   using B0 = std::integral_constant<int, 0>;
   using B1 = std::integral_constant<int, 1>;
@@ -666,8 +677,8 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_fwd(const bf16_t* __r
     }
 
     const int nkv = (min(S, qb * RB + RB) + KVB - 1) / KVB;  // = qb + 1 except at a ragged end
-    glds_tile<D>(k + hin, ks * KVB, S, in_rs, lds, wid, lane);
-    glds_tile<D>(v + hin, ks * KVB, S, in_rs, lds + KVB * D, wid, lane);
+    glds_tile<D>(k + hkv, ks * KVB, S, krs, lds, wid, lane);
+    glds_tile<D>(v + hkv, ks * KVB, S, krs, lds + KVB * D, wid, lane);
     __syncthreads();
 
     // One K/V tile per step.  BUF is a compile-time LDS buffer index and MASKED a
@@ -686,8 +697,8 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_fwd(const bf16_t* __r
       const bool more = kb + 1 < nkv;
       if (more) {  // next tile straight into the other buffer (read by nobody since the last barrier)
         bf16_t* Kn = lds + (BUF ^ 1) * 2 * KVB * D;
-        glds_tile<D>(k + hin, (kb + 1) * KVB, S, in_rs, Kn, wid, lane);
-        glds_tile<D>(v + hin, (kb + 1) * KVB, S, in_rs, Kn + KVB * D, wid, lane);
+        glds_tile<D>(k + hkv, (kb + 1) * KVB, S, krs, Kn, wid, lane);
+        glds_tile<D>(v + hkv, (kb + 1) * KVB, S, krs, Kn + KVB * D, wid, lane);
         if (DROP) mw_next = make_uint2(mrow[(size_t)(2 * (kb + 1)) * S], 2 * (kb + 1) + 1 < W ? mrow[(size_t)(2 * (kb + 1) + 1) * S] : 0u);
       }
       const bf16_t* Kt = lds + BUF * 2 * KVB * D;
@@ -1021,6 +1032,185 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_bwd_dkdv(const bf16_t
   }
 }
 
+// ---------------------------------------------------------------- dK / dV, grouped-query
+// The kernel above with a loop over the query heads that share the item's KV head.  It is a
+// kernel of its own, not a template flag of k_attn_bwd_dkdv: that kernel sits at the VGPR
+// limit, and any edit of its source -- even one that is dead code without GQA -- changed
+// hipcc's register allocation of the MHA instantiations.
+// The grid runs over the B * nh / G KV heads.  k / v use (kv_bs, kv_hs, kv_rs), dk / dv
+// the out strides; q, dO, lse, delta and the keep bits are those of query head kvh * G + g,
+// g = 0 .. G-1 in this fixed order, all adding into the same dka / dva registers, stored
+// once at the end.  The double-buffered Q/dO pipeline does not drain between heads: the
+// last tile step of head g prefetches the first tile of head g + 1 into the other buffer
+// (the tile order, and so every sum, is that of G restarted pipelines; with a restart
+// inside the loop the D = 64 instantiations spilled 50-90 bytes per lane).
+template <bool DROP, int HK, int D, bool DOC = false>
+__global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_bwd_dkdv_gqa(
+    const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
+    const bf16_t* __restrict__ dout, const float* __restrict__ lse, const float* __restrict__ delta,
+    const uint32_t* __restrict__ maskT, bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, int S, int nh, float c_log2,
+    float scale, float dscale, long in_bs, int in_hs, int in_rs, long out_bs, int out_hs, int out_rs,
+    const float* __restrict__ cosT, const float* __restrict__ sinT, int xcd_map, const int* __restrict__ dhi, int G,
+    long kv_bs, int kv_hs, int kv_rs) {
+  // one LDS object (avoids hipcc's extra vmcnt waits with several __shared__ arrays)
+  __shared__ __attribute__((aligned(16))) char smem[2 * 2 * QSTEP * D * 2 + 2 * 2 * QSTEP * 4];
+  bf16_t* lds = reinterpret_cast<bf16_t*>(smem);                              // [buf][Q|dO][64][D]
+  float* rowc = reinterpret_cast<float*>(smem + 2 * 2 * QSTEP * D * 2);       // [buf][lse2|delta][64]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int h = lane >> 5, kl = lane & 31;
+  ATTN_STAMP(0);
+  const int nrb = (S + RB - 1) / RB;
+  int bh, pair;
+  const bool lpt = work_item(nrb, xcd_map, bh, pair);
+  // `head` is the KV head and hq0 the group's first query head (g = 0); the q-side bases
+  // below are those of hq0 and move on by one query head per pass
+  const int nhk = nh / G;
+  const int b = bh / nhk, head = bh % nhk;
+  const int hq0 = head * G;
+  const int bhq0 = b * nh + hq0;                                   // row of lse / delta / the keep bits
+  const size_t hin = (size_t)b * in_bs + (size_t)hq0 * in_hs;      // q
+  const size_t hout = (size_t)b * out_bs + (size_t)head * out_hs;  // dk / dv
+  const size_t hkv = (size_t)b * kv_bs + (size_t)head * kv_hs;     // k / v
+  const int krs = kv_rs;
+  const int rstride = nh * D;
+  const int W = (S + 31) >> 5;
+  const int nqt = (S + QSTEP - 1) / QSTEP;
+  const bf16_t* dob0 = dout + ((size_t)b * S * nh + hq0) * D;
+  const float inv_dscale = 1.f / dscale;
+  using UNM = std::integral_constant<bool, false>;
+  using MSK = std::integral_constant<bool, true>;
+
+#pragma unroll 1
+  for (int it = 0; it < 2; ++it) {
+    const int kblk = (lpt || it == 0) ? pair : nrb - 1 - pair;  // long item (early keys) first
+    if (it == 1 && (lpt || kblk <= pair)) break;                 // odd nrb: middle item once
+    const int k0 = kblk * RB + wid * 32;  // wave-uniform
+    const int ka = k0 + kl;
+    // this lane's key column of the transposed keep-bit mask: one word per 32 queries
+    const uint32_t* mcol0 = DROP ? maskT + (size_t)bhq0 * W * S + min(ka, S - 1) : nullptr;  // word j at mcol[j*S]
+
+    bf16x8_t kf[D / 16], vf[D / 16];
+    const int kc = min(ka, S - 1);
+#pragma unroll
+    for (int s = 0; s < D / 16; ++s) {
+      kf[s] = load_row8(k + hkv + (size_t)kc * krs + 16 * s + 8 * h, ka < S);
+      vf[s] = load_row8(v + hkv + (size_t)kc * krs + 16 * s + 8 * h, ka < S);
+    }
+    floatx16_t dka[D / 32], dva[D / 32];
+#pragma unroll
+    for (int dt = 0; dt < D / 32; ++dt) dka[dt] = dva[dt] = zero16();
+
+    const int qt_begin = kblk;  // the 64-query tile holding this item's diagonal
+    // DOC: this lane's bound, the wave's largest (its last key's), and the item's tile
+    // range: the loop ends before tile nqe, tiles from t_unm on reach past some key's bound
+    int hi_k = 0, hi_w = 0, nqe_doc = 0, t_unm = 0;
+    if constexpr (DOC) {
+      const int* hrow = dhi + (size_t)b * S;
+      hi_k = hrow[kc];
+      hi_w = __builtin_amdgcn_readlane(hi_k, 31);
+      doc_k_range(hrow, kblk, S, nqt, nqe_doc, t_unm);
+    }
+    const int nqe = DOC ? nqe_doc : nqt;
+    // q-side bases of the head whose tiles are being LOADED (one tile ahead of the compute);
+    // par = LDS buffer of the tile being computed
+    {
+      int bhq = bhq0;
+      const bf16_t* qb = q + hin;
+      const bf16_t* dob = dob0;
+      const uint32_t* mcol = mcol0;
+      int par = 0;
+      float rl = 0.f, rd = 0.f;
+      uint2 mw_cur = make_uint2(0u, 0u), mw_next = make_uint2(0u, 0u);
+      auto load_rows = [&](int t, int buf) {  // Q / dO tiles by LDS-DMA, row stats via registers
+        glds_tile64<D>(qb, t * QSTEP, S, in_rs, lds + buf * 2 * QSTEP * D, wid, lane);
+        glds_tile64<D>(dob, t * QSTEP, S, rstride, lds + buf * 2 * QSTEP * D + QSTEP * D, wid, lane);
+        if (DROP) {  // this lane's two 32-query keep words of tile t (consumed one tile later)
+          const int w0 = (t * QSTEP) >> 5;
+          mw_next = make_uint2(mcol[(size_t)w0 * S], (w0 + 1 < W) ? mcol[(size_t)(w0 + 1) * S] : 0u);
+        }
+        if (tid < QSTEP) {
+          const int qq = min(t * QSTEP + tid, S - 1);
+          const bool ok = t * QSTEP + tid < S;
+          rl = ok ? lse[(size_t)bhq * S + qq] * LOG2E : 0.f;
+          rd = ok ? delta[(size_t)bhq * S + qq] * (DROP ? inv_dscale : 1.f) : 0.f;  // Delta / s (dkdv_subtile)
+        }
+      };
+      auto store_rows = [&](int buf) {
+        if (tid < QSTEP) {
+          rowc[buf * 2 * QSTEP + tid] = rl;
+          rowc[buf * 2 * QSTEP + QSTEP + tid] = rd;
+        }
+      };
+      load_rows(qt_begin, 0);
+      store_rows(0);
+      mw_cur = mw_next;
+      __syncthreads();
+      ATTN_STAMP(1);
+
+      // Tile qt_begin holds every diagonal sub-tile of the item (masked kind, fully
+      // masked sub-tiles skipped); later full tiles are straight-line unmasked; a ragged
+      // last tile (S % 64) is masked again.
+      auto step = [&](auto maskc, int t, int g) {
+        constexpr bool MASKED = decltype(maskc)::value;
+        const int cur = par;
+        const bool wrap = t + 1 >= nqe;  // the head's last tile: the next one is the next head's first
+        const bool more = !wrap || g + 1 < G;
+        const uint32_t mw0 = mw_cur.x, mw1 = mw_cur.y;
+        if (more) {
+          if (wrap) {
+            ++bhq;
+            qb += in_hs;
+            dob += D;
+            if (DROP) mcol += (size_t)W * S;
+          }
+          load_rows(wrap ? qt_begin : t + 1, cur ^ 1);
+        }
+        const bf16_t* Qt = lds + cur * 2 * QSTEP * D;
+        const bf16_t* Dt = Qt + QSTEP * D;
+        const float* rlp = rowc + cur * 2 * QSTEP;
+        const float* rdp = rlp + QSTEP;
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) {
+          const int qs = t * QSTEP + 32 * qt;
+          const bf16_t* Qs = Qt + 32 * qt * D;
+          const bf16_t* Ds = Dt + 32 * qt * D;
+          const uint32_t mw = (qt ? mw1 : mw0) >> (4 * h);
+          if (!MASKED)
+            dkdv_subtile<false, DROP, HK, D>(dka, dva, Qs, Ds, rlp + 32 * qt, rdp + 32 * qt, mw, kf, vf, qs, ka, S,
+                                             lane, c_log2, dscale);
+          else if (qs + 31 >= k0 && (!DOC || qs <= hi_w))  // DOC: not wholly past this wave's documents
+            dkdv_subtile<true, DROP, HK, D, DOC>(dka, dva, Qs, Ds, rlp + 32 * qt, rdp + 32 * qt, mw, kf, vf, qs, ka, S,
+                                                 lane, c_log2, dscale, hi_k);
+        }
+        if (more) store_rows(cur ^ 1);
+        mw_cur = mw_next;
+        par ^= 1;
+        tile_barrier();
+      };
+      const int t_full = DOC ? t_unm : S / QSTEP;  // DOC: the first tile past the item's smallest hi
+#pragma unroll 1
+      for (int g = 0; g < G; ++g) {
+        int t = qt_begin;
+        if (t < nqe) step(MSK{}, t++, g);
+        for (; t < t_full; ++t) step(UNM{}, t, g);
+        for (; t < nqe; ++t) step(MSK{}, t, g);
+      }
+      ATTN_STAMP(3);
+    }
+
+    if (ka < S) {
+      store_head_row<HK, D>(dk + hout + (size_t)ka * out_rs, dka, DROP ? scale * dscale : scale, h, cosT, sinT, ka);
+      store_head_row<HK, D>(dv + hout + (size_t)ka * out_rs, dva, DROP ? dscale : 1.f, h, nullptr, nullptr, 0);
+    }
+#ifdef DLT_ATTN_TIMING
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    ATTN_STAMP(4);
+    if (lane == 0) g_attn_tim[((size_t)blockIdx.x * 2 + wid) * 8 + 5] = (unsigned long long)(nqt - qt_begin);
+#endif
+  }
+}
+
 // ---------------------------------------------------------------------- dQ
 template <bool MASK, bool DROP, int HK, int D, bool DOC = false>
 __device__ __forceinline__ void dq_tile(floatx16_t (&dqa)[D / 32], const bf16_t* Kt, const bf16_t* Vt,
@@ -1089,7 +1279,8 @@ __device__ __forceinline__ void dq_tile(floatx16_t (&dqa)[D / 32], const bf16_t*
 }
 
 // DOC: dlo = lo [B, S] of the document mask, as in the forward; unused otherwise.
-template <bool DROP, int HK, int D, bool DOC = false>
+// GQA: k / v strides as in the forward; dq, delta and the keep bits stay per query head.
+template <bool DROP, int HK, int D, bool DOC = false, bool GQA = false>
 __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_bwd_dq(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                        const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
                                                        const bf16_t* __restrict__ o,
@@ -1100,7 +1291,8 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_bwd_dq(const bf16_t* 
                                                        long in_bs, int in_hs, int in_rs, long out_bs, int out_hs,
                                                        int out_rs, const float* __restrict__ cosT,
                                                        const float* __restrict__ sinT, int xcd_map,
-                                                       const int* __restrict__ dlo = nullptr) {
+                                                       const int* __restrict__ dlo = nullptr, int G = 1,
+                                                       long kv_bs = 0, int kv_hs = 0, int kv_rs = 0) {
   __shared__ __attribute__((aligned(16))) bf16_t lds[2 * 2 * KVB * D];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1111,6 +1303,8 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_bwd_dq(const bf16_t* 
   const int b = bh / nh, head = bh % nh;
   const size_t hin = (size_t)b * in_bs + (size_t)head * in_hs;     // q / k / v
   const size_t hout = (size_t)b * out_bs + (size_t)head * out_hs;  // dq
+  const size_t hkv = GQA ? (size_t)b * kv_bs + (size_t)(head / G) * kv_hs : hin;  // k / v of kv head head / G
+  const int krs = GQA ? kv_rs : in_rs;
   const int W = (S + 31) >> 5;
   using B0 = std::integral_constant<int, 0>;
   using B1 = std::integral_constant<int, 1>;
@@ -1154,8 +1348,8 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_bwd_dq(const bf16_t* 
     }
 
     const int nkv = (min(S, qb * RB + RB) + KVB - 1) / KVB;
-    glds_tile<D>(k + hin, ks * KVB, S, in_rs, lds, wid, lane);
-    glds_tile<D>(v + hin, ks * KVB, S, in_rs, lds + KVB * D, wid, lane);
+    glds_tile<D>(k + hkv, ks * KVB, S, krs, lds, wid, lane);
+    glds_tile<D>(v + hkv, ks * KVB, S, krs, lds + KVB * D, wid, lane);
     __syncthreads();
 
     // Same loop structure as the forward: straight-line unmasked tiles (static LDS
@@ -1171,8 +1365,8 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_bwd_dq(const bf16_t* 
       const bool more = kb + 1 < nkv;
       if (more) {  // next tile straight into the other buffer (read by nobody since the last barrier)
         bf16_t* Kn = lds + (BUF ^ 1) * 2 * KVB * D;
-        glds_tile<D>(k + hin, (kb + 1) * KVB, S, in_rs, Kn, wid, lane);
-        glds_tile<D>(v + hin, (kb + 1) * KVB, S, in_rs, Kn + KVB * D, wid, lane);
+        glds_tile<D>(k + hkv, (kb + 1) * KVB, S, krs, Kn, wid, lane);
+        glds_tile<D>(v + hkv, (kb + 1) * KVB, S, krs, Kn + KVB * D, wid, lane);
         if (DROP) mw_next = make_uint2(mrow[(size_t)(2 * (kb + 1)) * S], 2 * (kb + 1) + 1 < W ? mrow[(size_t)(2 * (kb + 1) + 1) * S] : 0u);
       }
       const bf16_t* Kt = lds + BUF * 2 * KVB * D;
@@ -1239,6 +1433,17 @@ static inline bool attn_hd_ok(int hd) { return hd == 64 || hd == 128; }
       __VA_ARGS__;                 \
     }                              \
   } while (0)
+// grouped-query dispatch: GQAC = true for the entry points that take nkv (any nkv, also nkv == nh)
+#define DLT_GQA_DISPATCH(on, ...)  \
+  do {                             \
+    if (on) {                      \
+      constexpr bool GQAC = true;  \
+      __VA_ARGS__;                 \
+    } else {                       \
+      constexpr bool GQAC = false; \
+      __VA_ARGS__;                 \
+    }                              \
+  } while (0)
 // XCD-aware work map on by default; DLT_ATTN_XCD=0 restores the natural order (A/B).
 static int xcd_map_enabled() {
   static int v = -1;
@@ -1277,8 +1482,12 @@ DLT_API int dlt_attn_dropout_mask(uint32_t* mask, int B, int nh, int S, uint32_t
 // dlt_attn_fwd_doc: the same with the document mask's lo [B, S] (int32; null = causal only).
 static int attn_fwd_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse, uint32_t* mask,
                            int B, int nh, int S, int hd, float scale, uint32_t key, uint32_t thr, float dscale,
-                           int gen_mask, long in_bs, int in_hs, int in_rs, int hk, const int* lo, hipStream_t st) {
+                           int gen_mask, long in_bs, int in_hs, int in_rs, int hk, const int* lo, hipStream_t st,
+                           int nkv = 0, long kv_bs = 0, int kv_hs = 0, int kv_rs = 0) {
+  // nkv > 0: the GQA kernels, k / v with nkv heads and their own strides (dlt_attn_fwd_gqa)
   if (!attn_hd_ok(hd) || S <= 0 || in_rs % 8 || in_hs % 8 || in_bs % 8) return -1;
+  if (nkv < 0 || (nkv && (nh % nkv || kv_rs % 8 || kv_hs % 8 || kv_bs % 8))) return -5;
+  const int G = nkv ? nh / nkv : 1;
   if (thr && !mask) return -2;  // dropout needs the keep-bit buffer
   const int nrb = (S + RB - 1) / RB;
   const int xm = xcd_map_enabled();
@@ -1289,11 +1498,15 @@ static int attn_fwd_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf
       const int rc = dlt_attn_dropout_mask(mask, B, nh, S, key, thr, st);
       if (rc) return rc;
     }
-    DLT_DOC_DISPATCH(lo, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_fwd<true, HKC, HDC, DOCC><<<grid, NT, 0, st>>>(
-                                                q, k, v, o, lse, mask, S, nh, c_log2, dscale, in_bs, in_hs, in_rs, xm, lo))));
+    DLT_GQA_DISPATCH(nkv, DLT_DOC_DISPATCH(lo, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk,
+                         k_attn_fwd<true, HKC, HDC, DOCC, GQAC><<<grid, NT, 0, st>>>(
+                             q, k, v, o, lse, mask, S, nh, c_log2, dscale, in_bs, in_hs, in_rs, xm, lo, G, kv_bs, kv_hs,
+                             kv_rs)))));
   } else {
-    DLT_DOC_DISPATCH(lo, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_fwd<false, HKC, HDC, DOCC><<<grid, NT, 0, st>>>(
-                                                q, k, v, o, lse, nullptr, S, nh, c_log2, dscale, in_bs, in_hs, in_rs, xm, lo))));
+    DLT_GQA_DISPATCH(nkv, DLT_DOC_DISPATCH(lo, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk,
+                         k_attn_fwd<false, HKC, HDC, DOCC, GQAC><<<grid, NT, 0, st>>>(
+                             q, k, v, o, lse, nullptr, S, nh, c_log2, dscale, in_bs, in_hs, in_rs, xm, lo, G, kv_bs,
+                             kv_hs, kv_rs)))));
   }
   DLT_CHECK_LAUNCH();
 }
@@ -1308,6 +1521,17 @@ DLT_API int dlt_attn_fwd_doc(const bf16_t* q, const bf16_t* k, const bf16_t* v, 
                              int gen_mask, long in_bs, int in_hs, int in_rs, int hk, const int* lo, hipStream_t st) {
   return attn_fwd_launch(q, k, v, o, lse, mask, B, nh, S, hd, scale, key, thr, dscale, gen_mask, in_bs, in_hs, in_rs, hk,
                          lo, st);
+}
+// Grouped-query attention: k / v hold nkv heads (nkv divides nh; query head h reads kv head
+// h / (nh / nkv)) at base + b*kv_bs + kvh*kv_hs + row*kv_rs.  lo: the document mask's lower
+// bounds, or null.  o, lse and the keep bits are per query head, as above.
+DLT_API int dlt_attn_fwd_gqa(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse, uint32_t* mask,
+                             int B, int nh, int nkv, int S, int hd, float scale, uint32_t key, uint32_t thr,
+                             float dscale, int gen_mask, long in_bs, int in_hs, int in_rs, long kv_bs, int kv_hs,
+                             int kv_rs, int hk, const int* lo, hipStream_t st) {
+  if (nkv <= 0) return -5;
+  return attn_fwd_launch(q, k, v, o, lse, mask, B, nh, S, hd, scale, key, thr, dscale, gen_mask, in_bs, in_hs, in_rs, hk,
+                         lo, st, nkv, kv_bs, kv_hs, kv_rs);
 }
 
 DLT_API int dlt_attn_fwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse, uint32_t* mask,
@@ -1326,32 +1550,51 @@ static int attn_bwd_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, co
                            const float* lse, const uint32_t* mask, float* delta_ws, bf16_t* dq, bf16_t* dk,
                            bf16_t* dv, int B, int nh, int S, int hd, float scale, float dscale, long in_bs,
                            int in_hs, int in_rs, long out_bs, int out_hs, int out_rs, const float* cosT,
-                           const float* sinT, int hk, const int* lo, const int* hi, hipStream_t st) {
+                           const float* sinT, int hk, const int* lo, const int* hi, hipStream_t st, int nkv = 0,
+                           long kv_bs = 0, int kv_hs = 0, int kv_rs = 0, long kvo_bs = 0, int kvo_hs = 0,
+                           int kvo_rs = 0) {
+  // nkv > 0: the GQA kernels (dlt_attn_bwd_gqa) -- k / v read with the kv strides, dk / dv
+  // written with the kvo strides, dK/dV grid over the B * nkv KV heads
   if ((lo == nullptr) != (hi == nullptr)) return -4;
+  if (nkv < 0 || (nkv && (nh % nkv || kv_rs % 8 || kv_hs % 8 || kv_bs % 8 || kvo_rs % 4 || kvo_hs % 4 || kvo_bs % 4)))
+    return -5;
+  const int G = nkv ? nh / nkv : 1;
   if (!attn_hd_ok(hd) || S <= 0 || in_rs % 8 || in_hs % 8 || in_bs % 8 || out_rs % 4 || out_hs % 4 || out_bs % 4)
     return -1;
   if ((cosT == nullptr) != (sinT == nullptr)) return -3;
   const float c_log2 = scale * LOG2E;
   const int nrb = (S + RB - 1) / RB;
   const int xm = xcd_map_enabled();
-  const dim3 gk(attn_grid(nrb, B * nh, xm)), gq(attn_grid(nrb, B * nh, xm));  // work items, see work_item()
+  const dim3 gk(attn_grid(nrb, B * (nkv ? nkv : nh), xm)), gq(attn_grid(nrb, B * nh, xm));  // work items, see work_item()
   // dQ first: it also produces Delta = rowsum(dO * O) (no separate kernel), which
   // dK/dV then reads.
   if (mask) {
     const uint32_t* maskT = mask + (size_t)B * nh * S * ((S + 31) / 32);
-    DLT_DOC_DISPATCH(lo, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_bwd_dq<true, HKC, HDC, DOCC><<<gq, NT, 0, st>>>(
-                            q, k, v, dout, o, lse, delta_ws, mask, dq, S, nh, c_log2, scale, dscale, in_bs, in_hs,
-                            in_rs, out_bs, out_hs, out_rs, cosT, sinT, xm, lo))));
-    DLT_DOC_DISPATCH(hi, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_bwd_dkdv<true, HKC, HDC, DOCC><<<gk, NT, 0, st>>>(
-                            q, k, v, dout, lse, delta_ws, maskT, dk, dv, S, nh, c_log2, scale, dscale, in_bs, in_hs,
-                            in_rs, out_bs, out_hs, out_rs, cosT, sinT, xm, hi))));
+    DLT_GQA_DISPATCH(nkv, DLT_DOC_DISPATCH(lo, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk,
+                         k_attn_bwd_dq<true, HKC, HDC, DOCC, GQAC><<<gq, NT, 0, st>>>(
+                             q, k, v, dout, o, lse, delta_ws, mask, dq, S, nh, c_log2, scale, dscale, in_bs, in_hs, in_rs,
+                             out_bs, out_hs, out_rs, cosT, sinT, xm, lo, G, kv_bs, kv_hs, kv_rs)))));
+    if (nkv)
+      DLT_DOC_DISPATCH(hi, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_bwd_dkdv_gqa<true, HKC, HDC, DOCC><<<gk, NT, 0, st>>>(
+                              q, k, v, dout, lse, delta_ws, maskT, dk, dv, S, nh, c_log2, scale, dscale, in_bs, in_hs,
+                              in_rs, kvo_bs, kvo_hs, kvo_rs, cosT, sinT, xm, hi, G, kv_bs, kv_hs, kv_rs))));
+    else
+      DLT_DOC_DISPATCH(hi, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_bwd_dkdv<true, HKC, HDC, DOCC><<<gk, NT, 0, st>>>(
+                              q, k, v, dout, lse, delta_ws, maskT, dk, dv, S, nh, c_log2, scale, dscale, in_bs, in_hs,
+                              in_rs, out_bs, out_hs, out_rs, cosT, sinT, xm, hi))));
   } else {
-    DLT_DOC_DISPATCH(lo, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_bwd_dq<false, HKC, HDC, DOCC><<<gq, NT, 0, st>>>(
-                            q, k, v, dout, o, lse, delta_ws, mask, dq, S, nh, c_log2, scale, dscale, in_bs, in_hs,
-                            in_rs, out_bs, out_hs, out_rs, cosT, sinT, xm, lo))));
-    DLT_DOC_DISPATCH(hi, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_bwd_dkdv<false, HKC, HDC, DOCC><<<gk, NT, 0, st>>>(
-                            q, k, v, dout, lse, delta_ws, mask, dk, dv, S, nh, c_log2, scale, dscale, in_bs, in_hs,
-                            in_rs, out_bs, out_hs, out_rs, cosT, sinT, xm, hi))));
+    DLT_GQA_DISPATCH(nkv, DLT_DOC_DISPATCH(lo, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk,
+                         k_attn_bwd_dq<false, HKC, HDC, DOCC, GQAC><<<gq, NT, 0, st>>>(
+                             q, k, v, dout, o, lse, delta_ws, mask, dq, S, nh, c_log2, scale, dscale, in_bs, in_hs, in_rs,
+                             out_bs, out_hs, out_rs, cosT, sinT, xm, lo, G, kv_bs, kv_hs, kv_rs)))));
+    if (nkv)
+      DLT_DOC_DISPATCH(hi, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_bwd_dkdv_gqa<false, HKC, HDC, DOCC><<<gk, NT, 0, st>>>(
+                              q, k, v, dout, lse, delta_ws, mask, dk, dv, S, nh, c_log2, scale, dscale, in_bs, in_hs,
+                              in_rs, kvo_bs, kvo_hs, kvo_rs, cosT, sinT, xm, hi, G, kv_bs, kv_hs, kv_rs))));
+    else
+      DLT_DOC_DISPATCH(hi, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_bwd_dkdv<false, HKC, HDC, DOCC><<<gk, NT, 0, st>>>(
+                              q, k, v, dout, lse, delta_ws, mask, dk, dv, S, nh, c_log2, scale, dscale, in_bs, in_hs,
+                              in_rs, out_bs, out_hs, out_rs, cosT, sinT, xm, hi))));
   }
   DLT_CHECK_LAUNCH();
 }
@@ -1370,6 +1613,19 @@ DLT_API int dlt_attn_bwd_doc(const bf16_t* q, const bf16_t* k, const bf16_t* v, 
                              const float* sinT, int hk, const int* lo, const int* hi, hipStream_t st) {
   return attn_bwd_launch(q, k, v, o, dout, lse, mask, delta_ws, dq, dk, dv, B, nh, S, hd, scale, dscale, in_bs, in_hs,
                          in_rs, out_bs, out_hs, out_rs, cosT, sinT, hk, lo, hi, st);
+}
+// Grouped-query backward: k / v as in dlt_attn_fwd_gqa; dq uses (out_bs, out_hs, out_rs), dk / dv
+// (nkv heads) use (kvo_bs, kvo_hs, kvo_rs).  lo / hi: the document mask's bounds, both or neither.
+DLT_API int dlt_attn_bwd_gqa(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o, const bf16_t* dout,
+                             const float* lse, const uint32_t* mask, float* delta_ws, bf16_t* dq, bf16_t* dk,
+                             bf16_t* dv, int B, int nh, int nkv, int S, int hd, float scale, float dscale, long in_bs,
+                             int in_hs, int in_rs, long kv_bs, int kv_hs, int kv_rs, long out_bs, int out_hs,
+                             int out_rs, long kvo_bs, int kvo_hs, int kvo_rs, const float* cosT, const float* sinT,
+                             int hk, const int* lo, const int* hi, hipStream_t st) {
+  if (nkv <= 0) return -5;
+  return attn_bwd_launch(q, k, v, o, dout, lse, mask, delta_ws, dq, dk, dv, B, nh, S, hd, scale, dscale, in_bs, in_hs,
+                         in_rs, out_bs, out_hs, out_rs, cosT, sinT, hk, lo, hi, st, nkv, kv_bs, kv_hs, kv_rs, kvo_bs,
+                         kvo_hs, kvo_rs);
 }
 
 DLT_API int dlt_attn_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o, const bf16_t* dout,

@@ -281,6 +281,43 @@ __global__ __launch_bounds__(256) void k_rope_qk_inplace(bf16_t* __restrict__ qk
   }
 }
 
+// Grouped-query form: the row is [q: nh heads | k: nkv heads | v: nkv heads], so the
+// rotated part is still one contiguous run of hq = nh + nkv heads at the row start; only
+// the head count and the row stride rs = (nh + 2 nkv) * hd differ from the kernel above.
+template <int HK = 0>
+__global__ __launch_bounds__(256) void k_rope_qk_inplace_gqa(bf16_t* __restrict__ qkv, const float* __restrict__ cosT,
+                                                             const float* __restrict__ sinT, int M, int S, int hq,
+                                                             int rs, int hd) {
+  const int half = hd >> 1;
+  const int cpr = half >> 3;  // 8-wide chunks per rotation half
+  const int total = M * hq * cpr;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const int j = (i % cpr) * 8;
+    const int r = i / cpr;
+    const int hh = r % hq;
+    const int m = r / hq;
+    const int s = m % S;
+    bf16_t* p = qkv + (size_t)m * rs + hh * hd;
+    const u16x8 a = *reinterpret_cast<const u16x8*>(p + j);
+    const u16x8 c = *reinterpret_cast<const u16x8*>(p + half + j);
+    const float* cp = cosT + s * half + j;
+    const float* sp = sinT + s * half + j;
+    const float4 c0 = *reinterpret_cast<const float4*>(cp), c1 = *reinterpret_cast<const float4*>(cp + 4);
+    const float4 s0 = *reinterpret_cast<const float4*>(sp), s1 = *reinterpret_cast<const float4*>(sp + 4);
+    const float cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+    const float ss[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+    u16x8 o1, o2;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float x1 = h2f<HK>(a.v[e]), x2 = h2f<HK>(c.v[e]);
+      o1.v[e] = f2h<HK>(x1 * cc[e] - x2 * ss[e]);
+      o2.v[e] = f2h<HK>(x2 * cc[e] + x1 * ss[e]);
+    }
+    *reinterpret_cast<u16x8*>(p + j) = o1;
+    *reinterpret_cast<u16x8*>(p + half + j) = o2;
+  }
+}
+
 static inline int ew_blocks(size_t total) {
   size_t b = (total + 255) / 256;
   return (int)(b > 16384 ? 16384 : (b == 0 ? 1 : b));
@@ -299,6 +336,18 @@ DLT_API int dlt_rope_qk_inplace(bf16_t* qkv, const float* cosT, const float* sin
   if (hd % 16 || S <= 0 || M % S || (long)M * 3 * nh * hd >= (1L << 31)) return -1;
   const size_t total = (size_t)M * 2 * nh * (hd / 16);
   DLT_HK_DISPATCH(hk, k_rope_qk_inplace<HKC><<<ew_blocks(total), 256, 0, st>>>(qkv, cosT, sinT, M, S, nh, hd));
+  DLT_CHECK_LAUNCH();
+}
+
+// packed [M, (nh + 2 nkv) * hd] rows: q (nh heads) | k (nkv heads) | v (nkv heads)
+DLT_API int dlt_rope_qk_inplace_gqa(bf16_t* qkv, const float* cosT, const float* sinT, int M, int S, int nh, int nkv,
+                                    int hd, int hk, hipStream_t st) {
+  if (hd % 16 || S <= 0 || M % S || nkv <= 0 || nh <= 0 || nh % nkv ||
+      (long)M * (nh + 2 * nkv) * hd >= (1L << 31))
+    return -1;
+  const size_t total = (size_t)M * (nh + nkv) * (hd / 16);
+  DLT_HK_DISPATCH(hk, k_rope_qk_inplace_gqa<HKC><<<ew_blocks(total), 256, 0, st>>>(qkv, cosT, sinT, M, S, nh + nkv,
+                                                                                  (nh + 2 * nkv) * hd, hd));
   DLT_CHECK_LAUNCH();
 }
 

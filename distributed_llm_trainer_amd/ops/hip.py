@@ -95,6 +95,16 @@ _SIGS = {
                          c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, ctypes.c_long, c_int, c_int,
                          ctypes.c_long, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
     "dlt_rope_qk_inplace": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    # grouped-query attention: nkv after nh, the k / v strides after q's (backward: then dq's and
+    # dk / dv's output strides), the document bounds (or null) before the stream
+    "dlt_attn_fwd_gqa": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                         c_float, c_uint32, c_uint32, c_float, c_int, ctypes.c_long, c_int, c_int, ctypes.c_long,
+                         c_int, c_int, c_int, c_void_p, c_void_p],
+    "dlt_attn_bwd_gqa": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                         c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
+                         ctypes.c_long, c_int, c_int, ctypes.c_long, c_int, c_int, ctypes.c_long, c_int, c_int,
+                         ctypes.c_long, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+    "dlt_rope_qk_inplace_gqa": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "dlt_dec_norm_qkv": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                          c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "dlt_dec_attn": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p],
@@ -420,7 +430,14 @@ def rmsnorm_bwd(dy, x, rstd, weight, dres, dweight, p_prev, key_prev, dy_scale=N
 
 
 # ------------------------------------------------------------------- RoPE
-def rope_qkv_fwd(qkv, B, S, nh, cos, sin):
+def _no_split_gqa(name: str):
+    raise NotImplementedError(f"{name}: grouped-query attention runs on the packed QKV layout "
+                              "(rope_qk_inplace + attention_fwd_packed / attention_bwd_packed with nkv=)")
+
+
+def rope_qkv_fwd(qkv, B, S, nh, cos, sin, nkv=None):
+    if nkv is not None and nkv != nh:
+        _no_split_gqa("rope_qkv_fwd")
     if qkv.dtype == torch.float32:
         from . import hip_f32
         return hip_f32.rope_qkv_fwd(qkv, B, S, nh, cos, sin)
@@ -444,6 +461,8 @@ def rope_qkv_bwd(dq, dk, dv, cos, sin, out=None):
         from . import hip_f32
         return hip_f32.rope_qkv_bwd(dq, dk, dv, cos, sin, out=out)
     B, nh, S, hd = dk.shape
+    if dq.dim() == 4 and dq.shape[1] != nh:
+        _no_split_gqa("rope_qkv_bwd")
     act = dk.dtype
     for t, n in ((dk, "dk"), (dv, "dv")):
         hk = _req_act(t, act, "rope_bwd." + n, B * nh * S * hd)
@@ -459,8 +478,38 @@ def rope_qkv_bwd(dq, dk, dv, cos, sin, out=None):
     return out
 
 
-def rope_qk_inplace(qkv, B, S, nh, cos, sin):
-    """Rotate the q and k column blocks of the packed [B*S, 3H] QKV in place."""
+def _req_nkv(nh: int, nkv, name: str) -> int:
+    """Validated number of K/V heads of a grouped-query call."""
+    if isinstance(nkv, bool) or not isinstance(nkv, int):
+        raise TypeError(f"{name}: nkv must be an int or None, got {type(nkv).__name__}")
+    if nkv < 1 or nh % nkv:
+        raise ValueError(f"{name}: nkv ({nkv}) must divide nh ({nh})")
+    return nkv
+
+
+def _no_gqa_f32(name: str):
+    raise NotImplementedError(f"{name}: grouped-query attention (nkv=) is not implemented for fp32 activations")
+
+
+def rope_qk_inplace(qkv, B, S, nh, cos, sin, nkv=None):
+    """Rotate the q and k column blocks of the packed [B*S, 3H] QKV in place.  With ``nkv``
+    (grouped-query attention) the row is [B*S, H + 2*KV]: nh q heads | nkv k heads | nkv v heads."""
+    if nkv is not None:
+        nkv = _req_nkv(nh, nkv, "rope_qk_inplace")
+        if qkv.dtype == torch.float32:
+            _no_gqa_f32("rope_qk_inplace")
+        M, Wd = qkv.shape
+        hd = Wd // (nh + 2 * nkv)
+        if M != B * S or hd * (nh + 2 * nkv) != Wd or hd % 16:
+            raise ValueError("rope_qk_inplace: qkv must be [B*S, (nh + 2*nkv)*hd] with hd % 16 == 0")
+        hk = _req_act(qkv, qkv.dtype, "rope_qk.qkv")
+        if cos.shape[0] < S or cos.shape[1] != hd // 2 or sin.shape != cos.shape:
+            raise ValueError("rope tables too short")
+        _req(cos, torch.float32, "rope_qk.cos")
+        _req(sin, torch.float32, "rope_qk.sin")
+        _chk(lib().dlt_rope_qk_inplace_gqa(_p(qkv), _p(cos), _p(sin), M, S, nh, nkv, hd, hk, _stream()),
+             "rope_qk_inplace_gqa")
+        return qkv
     if qkv.dtype == torch.float32:
         from . import hip_f32
         return hip_f32.rope_qk_inplace(qkv, B, S, nh, cos, sin)
@@ -527,13 +576,34 @@ def _req_doc(doc, B: int, S: int, device, name: str):
     return doc[0], doc[1]
 
 
-def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=None, scale=None, doc=None):
+def _head_major_nkv(q, k, v, nkv, name: str):
+    """Number of K/V heads when the grouped-query kernels run a head-major call (``nkv``
+    given, or k / v with fewer heads than q), else None: the MHA entry points."""
+    nh = q.shape[1]
+    if k.dim() != 4 or k.shape != v.shape:
+        raise ValueError(f"{name}: k {list(k.shape)} and v {list(v.shape)} must have the same 4-d shape")
+    if nkv is None and k.shape[1] == nh:
+        return None
+    nkv = _req_nkv(nh, k.shape[1] if nkv is None else nkv, name)
+    if tuple(k.shape) != (q.shape[0], nkv, q.shape[2], q.shape[3]):
+        raise ValueError(f"{name}: k / v must be [B, nkv, S, hd] = {[q.shape[0], nkv, q.shape[2], q.shape[3]]}, "
+                         f"got {list(k.shape)}")
+    if q.dtype == torch.float32:
+        _no_gqa_f32(name)
+    return nkv
+
+
+def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=None, scale=None, doc=None,
+                  nkv=None):
     """Returns (o [B*S, nh*hd] bf16, aux).  With dropout on, the keep bits are written
     to a bitmask consumed by attention_bwd (no re-hashing in the backward); pass
     ``mask`` from ``attention_dropout_mask`` to skip generating it here.  ``scale``:
     the score scale (default 1/sqrt(hd); ops/attn_gemm.py runs zero-padded heads with
     the unpadded head_dim's).  ``doc`` = (lo, hi) from :func:`doc_bounds`: the
-    intra-document mask of packed sequences (DOC kernels of attention.hip)."""
+    intra-document mask of packed sequences (DOC kernels of attention.hip).  Grouped-query
+    attention: k, v [B, nkv, S, hd] with nkv dividing nh (or ``nkv=`` given: the GQA kernels
+    also for nkv == nh)."""
+    nkv = _head_major_nkv(q, k, v, nkv, "attn")
     if q.dtype == torch.float32:
         from . import hip_f32
         if scale is not None:
@@ -542,8 +612,8 @@ def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=
     if not causal:
         raise NotImplementedError("only causal attention is implemented (the model is a causal LM)")
     B, nh, S, hd = q.shape
-    for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        hk = _req_act(t, q.dtype, "attn." + n, B * nh * S * hd)
+    for t, n, hh in ((q, "q", nh), (k, "k", nkv or nh), (v, "v", nkv or nh)):
+        hk = _req_act(t, q.dtype, "attn." + n, B * hh * S * hd)
     lo, _ = _req_doc(doc, B, S, q.device, "attn")
     if hd not in ATTN_HEAD_DIMS:
         raise NotImplementedError(f"attention kernels take head_dim {ATTN_HEAD_DIMS} (got {hd})")
@@ -563,7 +633,11 @@ def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=
         # with store_mask=False it only lives for this call (the backward regenerates it)
         mask = torch.empty(2, B * nh, (S + 31) // 32, S, dtype=torch.int32, device=q.device)
     sc = 1.0 / math.sqrt(hd) if scale is None else float(scale)
-    if doc is None:
+    if nkv is not None:
+        _chk(lib().dlt_attn_fwd_gqa(_p(q), _p(k), _p(v), _p(o), _p(lse), _p(mask), B, nh, nkv, S, hd, sc,
+                                    key & 0xFFFFFFFF, thr, dscale, gen, nh * S * hd, S * hd, hd, nkv * S * hd, S * hd,
+                                    hd, hk, _p(lo), _stream()), "attn_fwd_gqa")
+    elif doc is None:
         _chk(lib().dlt_attn_fwd(_p(q), _p(k), _p(v), _p(o), _p(lse), _p(mask), B, nh, S, hd, sc,
                                 key & 0xFFFFFFFF, thr, dscale, gen, hk, _stream()), "attn_fwd")
     else:
@@ -573,25 +647,37 @@ def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=
     return o, AttnAux((lse, mask if (store_mask or gen == 0) else None))
 
 
-def _packed_dims(qkv, B, S, nh):
-    M, threeH = qkv.shape
-    hd = threeH // (3 * nh)
-    if M != B * S or hd * 3 * nh != threeH:
-        raise ValueError("packed attention: qkv must be [B*S, 3*nh*hd]")
+def _packed_dims(qkv, B, S, nh, nkv=None):
+    """(M, H, hd) of the packed QKV; with ``nkv`` its rows are [H + 2*KV] and KV = nkv * hd
+    is returned too."""
+    M, Wd = qkv.shape
+    nk = nh if nkv is None else _req_nkv(nh, nkv, "packed attention")
+    hd = Wd // (nh + 2 * nk)
+    if M != B * S or hd * (nh + 2 * nk) != Wd:
+        raise ValueError("packed attention: qkv must be [B*S, 3*nh*hd]" if nkv is None else
+                         "packed attention: qkv must be [B*S, (nh + 2*nkv)*hd]")
     if hd not in ATTN_HEAD_DIMS:
         raise NotImplementedError(f"attention kernels take head_dim {ATTN_HEAD_DIMS} (got {hd})")
     _req_act(qkv, qkv.dtype, "attn.qkv")
-    return M, nh * hd, hd
+    if nkv is None:
+        return M, nh * hd, hd
+    return M, nh * hd, hd, nk * hd
 
 
-def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=True, doc=None):
+def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=True, doc=None, nkv=None):
     """Causal attention reading q/k/v straight from the packed (roped) [B*S, 3H] QKV.
-    Returns (o [B*S, H] bf16, aux) like :func:`attention_fwd`."""
+    Returns (o [B*S, H] bf16, aux) like :func:`attention_fwd`.  With ``nkv`` (grouped-query
+    attention) the packed row is [H + 2*KV]; lse and the keep bits stay per query head."""
     if qkv.dtype == torch.float32:
+        if nkv is not None:
+            _no_gqa_f32("attention_fwd_packed")
         from . import hip_f32
         return hip_f32.attention_fwd_packed(qkv, B, S, nh, p, key, out=out, mask=mask, store_mask=store_mask,
                                             doc=doc)
-    M, H, hd = _packed_dims(qkv, B, S, nh)
+    if nkv is None:
+        M, H, hd = _packed_dims(qkv, B, S, nh)
+    else:
+        M, H, hd, KV = _packed_dims(qkv, B, S, nh, nkv)
     lo, _ = _req_doc(doc, B, S, qkv.device, "attn")
     hk = _HK[qkv.dtype]
     o = torch.empty(M, H, dtype=qkv.dtype, device=qkv.device) if out is None else out
@@ -607,7 +693,12 @@ def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=
         gen = 0
     else:  # with store_mask=False it only lives for this call (the backward regenerates it)
         mask = torch.empty(2, B * nh, (S + 31) // 32, S, dtype=torch.int32, device=qkv.device)
-    if doc is None:
+    if nkv is not None:
+        Wd = H + 2 * KV
+        _chk(lib().dlt_attn_fwd_gqa(_p(qkv), _off(qkv, H), _off(qkv, H + KV), _p(o), _p(lse), _p(mask), B, nh, nkv, S,
+                                    hd, 1.0 / math.sqrt(hd), key & 0xFFFFFFFF, thr, dscale, gen, S * Wd, hd, Wd,
+                                    S * Wd, hd, Wd, hk, _p(lo), _stream()), "attn_fwd_packed_gqa")
+    elif doc is None:
         _chk(lib().dlt_attn_fwd_ex(_p(qkv), _off(qkv, H), _off(qkv, 2 * H), _p(o), _p(lse), _p(mask), B, nh, S, hd,
                                    1.0 / math.sqrt(hd), key & 0xFFFFFFFF, thr, dscale, gen, S * 3 * H, hd, 3 * H, hk,
                                    _stream()), "attn_fwd_packed")
@@ -618,14 +709,23 @@ def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=
     return o, AttnAux((lse, mask if (store_mask or gen == 0) else None))
 
 
-def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, doc=None):
+def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, doc=None, nkv=None):
     """Backward of :func:`attention_fwd_packed` + the in-place RoPE: returns dqkv
     [B*S, 3H] (gradient w.r.t. the pre-rotation QKV GEMM output); dq/dk/dv are written
-    into it by the attention kernels with the inverse rotation in their epilogue."""
+    into it by the attention kernels with the inverse rotation in their epilogue.  With
+    ``nkv`` qkv and dqkv are [B*S, H + 2*KV]; dk / dv are summed over each group's query
+    heads in registers, in a fixed order."""
     if qkv.dtype == torch.float32:
+        if nkv is not None:
+            _no_gqa_f32("attention_bwd_packed")
         from . import hip_f32
         return hip_f32.attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=out, doc=doc)
-    M, H, hd = _packed_dims(qkv, B, S, nh)
+    if nkv is None:
+        M, H, hd = _packed_dims(qkv, B, S, nh)
+        KV = H
+    else:
+        M, H, hd, KV = _packed_dims(qkv, B, S, nh, nkv)
+    Wd = H + 2 * KV
     lo, hi = _req_doc(doc, B, S, qkv.device, "attn_bwd")
     hk = _HK[qkv.dtype]
     for t, nm in ((o, "o"), (do, "do")):
@@ -641,12 +741,18 @@ def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, 
         mask = attention_dropout_mask(B, nh, S, p, key, device=qkv.device)
     if not thr:
         mask = None
-    dqkv = torch.empty(M, 3 * H, dtype=qkv.dtype, device=qkv.device) if out is None else out
-    _req(dqkv, qkv.dtype, "attn_bwd.dqkv", M * 3 * H)
+    dqkv = torch.empty(M, Wd, dtype=qkv.dtype, device=qkv.device) if out is None else out
+    _req(dqkv, qkv.dtype, "attn_bwd.dqkv", M * Wd)
     delta = torch.empty(B, nh, S, dtype=torch.float32, device=qkv.device)
     dscale = 1.0 / (1.0 - p) if thr else 1.0
     st = S * 3 * H
-    if doc is None:
+    if nkv is not None:
+        st = S * Wd
+        _chk(lib().dlt_attn_bwd_gqa(_p(qkv), _off(qkv, H), _off(qkv, H + KV), _p(o), _p(do), _p(lse), _p(mask),
+                                    _p(delta), _p(dqkv), _off(dqkv, H), _off(dqkv, H + KV), B, nh, nkv, S, hd,
+                                    1.0 / math.sqrt(hd), dscale, st, hd, Wd, st, hd, Wd, st, hd, Wd, st, hd, Wd,
+                                    _p(cos), _p(sin), hk, _p(lo), _p(hi), _stream()), "attn_bwd_packed_gqa")
+    elif doc is None:
         _chk(lib().dlt_attn_bwd_ex(_p(qkv), _off(qkv, H), _off(qkv, 2 * H), _p(o), _p(do), _p(lse), _p(mask), _p(delta),
                                    _p(dqkv), _off(dqkv, H), _off(dqkv, 2 * H), B, nh, S, hd, 1.0 / math.sqrt(hd), dscale,
                                    st, hd, 3 * H, st, hd, 3 * H, _p(cos), _p(sin), hk, _stream()), "attn_bwd_packed")
@@ -658,7 +764,10 @@ def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, 
     return dqkv
 
 
-def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, scale=None, doc=None):
+def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, scale=None, doc=None, nkv=None):
+    """Returns dq [B, nh, S, hd] and dk, dv in k's shape ([B, nkv, S, hd] under grouped-query
+    attention, see :func:`attention_fwd`)."""
+    nkv = _head_major_nkv(q, k, v, nkv, "attn_bwd")
     if q.dtype == torch.float32:
         from . import hip_f32
         if scale is not None:
@@ -666,8 +775,9 @@ def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, scale=None, doc=None
         return hip_f32.attention_bwd(q, k, v, o, do, aux, p, key, causal, doc=doc)
     B, nh, S, hd = q.shape
     n = B * nh * S * hd
-    for t, nm in ((q, "q"), (k, "k"), (v, "v"), (o, "o"), (do, "do")):
-        hk = _req_act(t, q.dtype, "attn_bwd." + nm, n)
+    nk = B * (nkv or nh) * S * hd
+    for t, nm, cnt in ((q, "q", n), (k, "k", nk), (v, "v", nk), (o, "o", n), (do, "do", n)):
+        hk = _req_act(t, q.dtype, "attn_bwd." + nm, cnt)
     lo, hi = _req_doc(doc, B, S, q.device, "attn_bwd")
     if isinstance(aux, tuple):
         lse, mask = aux
@@ -685,7 +795,12 @@ def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, scale=None, doc=None
     dv = torch.empty_like(v)
     dscale = 1.0 / (1.0 - p) if thr else 1.0
     sc = 1.0 / math.sqrt(hd) if scale is None else float(scale)
-    if doc is None:
+    if nkv is not None:
+        bs, hs, kbs = nh * S * hd, S * hd, nkv * S * hd
+        _chk(lib().dlt_attn_bwd_gqa(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(mask), _p(delta), _p(dq), _p(dk),
+                                    _p(dv), B, nh, nkv, S, hd, sc, dscale, bs, hs, hd, kbs, hs, hd, bs, hs, hd, kbs, hs,
+                                    hd, None, None, hk, _p(lo), _p(hi), _stream()), "attn_bwd_gqa")
+    elif doc is None:
         _chk(lib().dlt_attn_bwd(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(mask), _p(delta), _p(dq), _p(dk),
                                 _p(dv), B, nh, S, hd, sc, dscale, hk, _stream()), "attn_bwd")
     else:

@@ -109,66 +109,79 @@ def _rot(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Tensor:
     return torch.cat([x1 * cos - x2 * sin, x2 * cos + x1 * sin], dim=-1)
 
 
-def rope_qkv_fwd(qkv: torch.Tensor, B: int, S: int, nh: int, cos: torch.Tensor, sin: torch.Tensor):
-    """qkv [B*S, 3H] -> q, k, v [B, nh, S, hd] bf16 (q,k rotated in fp32)."""
-    hd = qkv.shape[-1] // (3 * nh)
-    t = qkv.view(B, S, 3, nh, hd).float()
+def _packed_dims(qkv: torch.Tensor, nh: int, nkv=None):
+    """(nkv, hd, H, KV) of a packed [M, H + 2*KV] QKV row: q (nh heads) | k | v (nkv heads each)."""
+    nkv = nh if nkv is None else int(nkv)
+    if nkv < 1 or nh % nkv:
+        raise ValueError(f"nkv ({nkv}) must divide nh ({nh})")
+    W = qkv.shape[-1]
+    if W % (nh + 2 * nkv):
+        raise ValueError(f"packed QKV width {W} is no multiple of nh + 2*nkv = {nh + 2 * nkv}")
+    hd = W // (nh + 2 * nkv)
+    return nkv, hd, nh * hd, nkv * hd
+
+
+def _qkv_views(qkv: torch.Tensor, B: int, S: int, nh: int, nkv=None):
+    """Views q [B, S, nh, hd], k, v [B, S, nkv, hd] into the packed QKV, and hd."""
+    nkv, hd, H, KV = _packed_dims(qkv, nh, nkv)
+    t = qkv.view(B, S, H + 2 * KV)
+    return (t[..., :H].view(B, S, nh, hd), t[..., H:H + KV].view(B, S, nkv, hd),
+            t[..., H + KV:].view(B, S, nkv, hd)), hd
+
+
+def rope_qkv_fwd(qkv: torch.Tensor, B: int, S: int, nh: int, cos: torch.Tensor, sin: torch.Tensor, nkv=None):
+    """qkv [B*S, H + 2*KV] -> q [B, nh, S, hd], k, v [B, nkv, S, hd] (q,k rotated in fp32)."""
+    (tq, tk, tv), hd = _qkv_views(qkv, B, S, nh, nkv)
     c = cos[:S].view(1, S, 1, hd // 2)
     s = sin[:S].view(1, S, 1, hd // 2)
-    q = _rot(t[:, :, 0], c, s).transpose(1, 2)
-    k = _rot(t[:, :, 1], c, s).transpose(1, 2)
-    v = t[:, :, 2].transpose(1, 2)
+    q = _rot(tq.float(), c, s).transpose(1, 2)
+    k = _rot(tk.float(), c, s).transpose(1, 2)
+    v = tv.float().transpose(1, 2)
     dt = qkv.dtype
     return q.to(dt).contiguous(), k.to(dt).contiguous(), v.to(dt).contiguous()
 
 
 def rope_qkv_bwd(dq: torch.Tensor, dk: torch.Tensor, dv: torch.Tensor,
                  cos: torch.Tensor, sin: torch.Tensor, out=None) -> torch.Tensor:
-    """Inverse rotation; returns dqkv [B*S, 3H] in dq's dtype."""
+    """Inverse rotation; returns dqkv [B*S, H + 2*KV] in dq's dtype (dk, dv: [B, nkv, S, hd])."""
     B, nh, S, hd = dq.shape
     c = cos[:S].view(1, 1, S, hd // 2)
     s = sin[:S].view(1, 1, S, hd // 2)
     gq = _rot(dq.float(), c, -s)
     gk = _rot(dk.float(), c, -s)
-    res = torch.stack([gq, gk, dv.float()], dim=0).permute(1, 3, 0, 2, 4).reshape(B * S, 3 * nh * hd).to(dq.dtype)
+    res = torch.cat([t.transpose(1, 2).reshape(B * S, -1) for t in (gq, gk, dv.float())], dim=1).to(dq.dtype)
     if out is not None:
         out.copy_(res)
         return out
     return res
 
 
-def _qkv_views(qkv: torch.Tensor, B: int, S: int, nh: int):
-    hd = qkv.shape[-1] // (3 * nh)
-    t = qkv.view(B, S, 3, nh, hd)
-    return t, hd
-
-
-def rope_qk_inplace(qkv: torch.Tensor, B: int, S: int, nh: int, cos: torch.Tensor, sin: torch.Tensor):
-    """Rotate the q and k column blocks of the packed [B*S, 3H] QKV in place."""
-    t, hd = _qkv_views(qkv, B, S, nh)
+def rope_qk_inplace(qkv: torch.Tensor, B: int, S: int, nh: int, cos: torch.Tensor, sin: torch.Tensor, nkv=None):
+    """Rotate the q and k column blocks of the packed [B*S, H + 2*KV] QKV in place."""
+    (tq, tk, _), hd = _qkv_views(qkv, B, S, nh, nkv)
     c = cos[:S].view(1, S, 1, hd // 2)
     s = sin[:S].view(1, S, 1, hd // 2)
-    for j in (0, 1):
-        t[:, :, j] = _rot(t[:, :, j].float(), c, s).to(qkv.dtype)
+    for t in (tq, tk):
+        t.copy_(_rot(t.float(), c, s).to(qkv.dtype))
     return qkv
 
 
-def _split_packed(qkv, B, S, nh):
-    t, _ = _qkv_views(qkv, B, S, nh)
-    return tuple(t[:, :, j].transpose(1, 2).contiguous() for j in range(3))
+def _split_packed(qkv, B, S, nh, nkv=None):
+    views, _ = _qkv_views(qkv, B, S, nh, nkv)
+    return tuple(t.transpose(1, 2).contiguous() for t in views)
 
 
 def attention_fwd_packed(qkv: torch.Tensor, B: int, S: int, nh: int, p: float, key: int, out=None, mask=None,
-                         doc=None):
-    """Causal attention straight on the (already roped) packed [B*S, 3H] QKV."""
-    q, k, v = _split_packed(qkv, B, S, nh)
+                         doc=None, nkv=None):
+    """Causal attention straight on the (already roped) packed [B*S, H + 2*KV] QKV."""
+    q, k, v = _split_packed(qkv, B, S, nh, nkv)
     return attention_fwd(q, k, v, p, key, True, out=out, doc=doc)
 
 
 def attention_bwd_packed(qkv, o, do, lse, p: float, key: int, B: int, S: int, nh: int,
-                         cos: torch.Tensor, sin: torch.Tensor, out=None, doc=None) -> torch.Tensor:
-    """Backward of attention_fwd_packed + the in-place RoPE: dqkv [B*S, 3H] (pre-RoPE)."""
-    q, k, v = _split_packed(qkv, B, S, nh)
+                         cos: torch.Tensor, sin: torch.Tensor, out=None, doc=None, nkv=None) -> torch.Tensor:
+    """Backward of attention_fwd_packed + the in-place RoPE: dqkv [B*S, H + 2*KV] (pre-RoPE)."""
+    q, k, v = _split_packed(qkv, B, S, nh, nkv)
     dq, dk, dv = attention_bwd(q, k, v, o, do, lse, p, key, True, doc=doc)
     res = rope_qkv_bwd(dq.float(), dk.float(), dv.float(), cos, sin).to(qkv.dtype)
     if out is not None:
@@ -229,13 +242,32 @@ def _masked_out(S: int, device, causal: bool, doc, B: int, name: str) -> Optiona
     return mask | (kpos < lo.view(B, 1, S, 1))
 
 
+def _kv_group(q, k, v, name: str) -> int:
+    """Group size G = nh // nkv of q [B, nh, S, hd] with k, v [B, nkv, S, hd]."""
+    B, nh, S, hd = q.shape
+    if k.shape != v.shape or k.dim() != 4:
+        raise ValueError(f"{name}: k {list(k.shape)} and v {list(v.shape)} must have the same 4-d shape")
+    nkv = k.shape[1]
+    if (k.shape[0], k.shape[2], k.shape[3]) != (B, S, hd) or nkv < 1 or nh % nkv:
+        raise ValueError(f"{name}: k/v shape {list(k.shape)} does not fit q {list(q.shape)} "
+                         f"(expected [B, nkv, S, hd] with nkv dividing nh)")
+    return nh // nkv
+
+
+def _rep_kv(t: torch.Tensor, G: int) -> torch.Tensor:
+    return t if G == 1 else t.repeat_interleave(G, dim=1)
+
+
 def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, p: float, key: int,
                   causal: bool = True, out=None, doc=None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """q,k,v [B, nh, S, hd] -> o [B*S, nh*hd] (q dtype), lse [B, nh, S] fp32.
-    ``doc`` = (lo, hi) from :func:`doc_bounds` adds the intra-document mask."""
+    """q [B, nh, S, hd], k, v [B, nkv, S, hd] -> o [B*S, nh*hd] (q dtype), lse [B, nh, S] fp32.
+    ``doc`` = (lo, hi) from :func:`doc_bounds` adds the intra-document mask.  nkv < nh is
+    grouped-query attention: query head h attends with kv head h // (nh // nkv)."""
     B, nh, S, hd = q.shape
+    G = _kv_group(q, k, v, "attn")
     scale = 1.0 / math.sqrt(hd)
-    s = torch.matmul(q.float(), k.float().transpose(-2, -1)) * scale
+    k, v = _rep_kv(k.float(), G), _rep_kv(v.float(), G)
+    s = torch.matmul(q.float(), k.transpose(-2, -1)) * scale
     mask = _masked_out(S, q.device, causal, doc, B, "attn")
     if mask is not None:
         s = s.masked_fill(mask, float("-inf"))
@@ -253,10 +285,12 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, p: float, k
 
 
 def attention_bwd(q, k, v, o, do, lse, p: float, key: int, causal: bool = True, doc=None):
-    """Flash-style backward from (o, lse).  do/o are [B*S, H]; returns dq, dk, dv [B,nh,S,hd]."""
+    """Flash-style backward from (o, lse).  do/o are [B*S, H]; returns dq [B,nh,S,hd] and
+    dk, dv in k's shape [B,nkv,S,hd] (summed over each kv head's query group in fp32)."""
     B, nh, S, hd = q.shape
+    G = _kv_group(q, k, v, "attn_bwd")
     scale = 1.0 / math.sqrt(hd)
-    qf, kf, vf = q.float(), k.float(), v.float()
+    qf, kf, vf = q.float(), _rep_kv(k.float(), G), _rep_kv(v.float(), G)
     of = o.float().view(B, S, nh, hd).transpose(1, 2)
     dof = do.float().view(B, S, nh, hd).transpose(1, 2)
     s = torch.matmul(qf, kf.transpose(-2, -1)) * scale
@@ -276,6 +310,9 @@ def attention_bwd(q, k, v, o, do, lse, p: float, key: int, causal: bool = True, 
     ds = prob * (dp - delta)
     dq = torch.matmul(ds, kf) * scale
     dk = torch.matmul(ds.transpose(-2, -1), qf) * scale
+    if G > 1:
+        dk = dk.view(B, nh // G, G, S, hd).sum(dim=2)
+        dv = dv.view(B, nh // G, G, S, hd).sum(dim=2)
     dt = q.dtype
     return dq.to(dt), dk.to(dt), dv.to(dt)
 

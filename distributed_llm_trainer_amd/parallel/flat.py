@@ -5,7 +5,7 @@ weight to bf16 on every micro-step and lets the DDP Reducer c
 gradients into 25 MB buckets (K16).  Here every parameter is a *view* into one
 contiguous fp32 master buffer laid out so that
 
-* ``q|k|v`` rows of a layer are adjacent -> the packed ``[3H, H]`` QKV weight is a
+* ``q|k|v`` rows of a layer are adjacent -> the packed ``[H + 2*KV, H]`` QKV weight (``[3H, H]`` without grouped-query attention) is a
   free view, likewise ``gate|up`` -> ``[2I, H]`` (one GEMM each instead of 3 and 2);
 * a bf16 "shadow" buffer with the identical layout is written by the fused AdamW
   kernel, so GEMMs read bf16 weights with no per-step cast kernels;
@@ -42,6 +42,7 @@ class FlatLayout:
         self.cfg = cfg
         H, I, L = cfg.hidden_size, cfg.intermediate_size, cfg.num_layers
         V, Vp = cfg.vocab_size, cfg.vocab_size_padded
+        KV = cfg.kv_size  # num_kv_heads * head_dim (= H without grouped-query attention)
         segs: List[Segment] = []
         off = 0
 
@@ -58,8 +59,8 @@ class FlatLayout:
             start = off
             p = f"layers.{i}."
             add(p + "attention.q_proj.weight", (H, H))
-            add(p + "attention.k_proj.weight", (H, H))
-            add(p + "attention.v_proj.weight", (H, H))
+            add(p + "attention.k_proj.weight", (KV, H))
+            add(p + "attention.v_proj.weight", (KV, H))
             add(p + "attention.o_proj.weight", (H, H))
             add(p + "mlp.gate_proj.weight", (I, H))
             add(p + "mlp.up_proj.weight", (I, H))
@@ -122,6 +123,7 @@ class FlatParamStore(ParamProvider):
     def _build_views(self):
         lay, cfg = self.layout, self.cfg
         H, I, Vp = cfg.hidden_size, cfg.intermediate_size, cfg.vocab_size_padded
+        QKV = H + 2 * cfg.kv_size  # q | k | v rows, contiguous in the layout
         bn = lay.by_name
 
         def v(buf, name, rows, cols):
@@ -136,14 +138,14 @@ class FlatParamStore(ParamProvider):
         for i in range(cfg.num_layers):
             p = f"layers.{i}."
             self._layers.append(LayerWeights(
-                wqkv=v(self.shadow, p + "attention.q_proj.weight", 3 * H, H),
+                wqkv=v(self.shadow, p + "attention.q_proj.weight", QKV, H),
                 wo=v(self.shadow, p + "attention.o_proj.weight", H, H),
                 wgu=v(self.shadow, p + "mlp.gate_proj.weight", 2 * I, H),
                 wdown=v(self.shadow, p + "mlp.down_proj.weight", H, I),
                 ln1=vec(self.flat, p + "input_layernorm.weight"),
                 ln2=vec(self.flat, p + "post_attention_layernorm.weight")))
             self._lgrads.append(LayerGrads(
-                wqkv=v(self.grad, p + "attention.q_proj.weight", 3 * H, H),
+                wqkv=v(self.grad, p + "attention.q_proj.weight", QKV, H),
                 wo=v(self.grad, p + "attention.o_proj.weight", H, H),
                 wgu=v(self.grad, p + "mlp.gate_proj.weight", 2 * I, H),
                 wdown=v(self.grad, p + "mlp.down_proj.weight", H, I),

@@ -184,8 +184,8 @@ class FSDPRuntime(ParamProvider):
         else:
             p = f"layers.{uid}."
             add(p + "attention.q_proj.weight", (H, H))
-            add(p + "attention.k_proj.weight", (H, H))
-            add(p + "attention.v_proj.weight", (H, H))
+            add(p + "attention.k_proj.weight", (cfg.kv_size, H))
+            add(p + "attention.v_proj.weight", (cfg.kv_size, H))
             add(p + "attention.o_proj.weight", (H, H))
             add(p + "mlp.gate_proj.weight", (I, H))
             add(p + "mlp.up_proj.weight", (I, H))
@@ -403,7 +403,7 @@ class FSDPRuntime(ParamProvider):
         H, I = self.cfg.hidden_size, self.cfg.intermediate_size
         p = f"layers.{i}."
         f = u.full
-        return LayerWeights(wqkv=self._view(u, f, p + "attention.q_proj.weight", 3 * H, H),
+        return LayerWeights(wqkv=self._view(u, f, p + "attention.q_proj.weight", H + 2 * self.cfg.kv_size, H),
                             wo=self._view(u, f, p + "attention.o_proj.weight", H, H),
                             wgu=self._view(u, f, p + "mlp.gate_proj.weight", 2 * I, H),
                             wdown=self._view(u, f, p + "mlp.down_proj.weight", H, I),
@@ -428,7 +428,7 @@ class FSDPRuntime(ParamProvider):
         else:
             ln1 = self._view(u, g, p + "input_layernorm.weight")
             ln2 = self._view(u, g, p + "post_attention_layernorm.weight")
-        return LayerGrads(wqkv=self._view(u, g, p + "attention.q_proj.weight", 3 * H, H),
+        return LayerGrads(wqkv=self._view(u, g, p + "attention.q_proj.weight", H + 2 * self.cfg.kv_size, H),
                           wo=self._view(u, g, p + "attention.o_proj.weight", H, H),
                           wgu=self._view(u, g, p + "mlp.gate_proj.weight", 2 * I, H),
                           wdown=self._view(u, g, p + "mlp.down_proj.weight", H, I),

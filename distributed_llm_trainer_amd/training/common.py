@@ -214,6 +214,22 @@ def add_doc_mask_args(p) -> None:
                         "--eval_batches evaluation both use it (default: plain causal attention)")
 
 
+def add_model_args(p) -> None:
+    p.add_argument("--num_kv_heads", type=int, default=None, metavar="N",
+                   help="grouped-query attention: N key/value heads shared by groups of num_heads / N query "
+                        "heads (N must divide num_heads; 1 = multi-query).  Overrides the YAML's "
+                        "model.num_kv_heads and the preset (default: num_heads, plain multi-head attention)")
+
+
+def apply_model_args(args, model_config) -> None:
+    """CLI > YAML > preset for the model flags of :func:`add_model_args`."""
+    nkv = getattr(args, "num_kv_heads", None)
+    if nkv is not None:
+        if nkv < 1 or model_config.num_heads % nkv:
+            raise ValueError(f"--num_kv_heads {nkv} must divide num_heads ({model_config.num_heads})")
+        model_config.num_kv_heads = nkv
+
+
 def unwrap_batch(batch):
     if isinstance(batch, dict):
         return batch["input_ids"]

@@ -40,7 +40,7 @@ from ..parallel.flat import FlatParamStore
 from ..utils import checkpoint as ckpt
 from ..utils import debug as dbg
 from ..utils.profiling import Profiler, range_push, range_pop
-from .common import EVAL_SEED_OFFSET, HeldOutBatches, add_doc_mask_args, add_eval_args, cosine_lr, evaluate_held_out, gemm_plan_hook, global_mean_loss, held_out_of, log_evaluation, memory_stats, micro_step_fusion, seed_all, select_device, setup_distributed, unwrap_batch
+from .common import EVAL_SEED_OFFSET, HeldOutBatches, add_doc_mask_args, add_eval_args, add_model_args, apply_model_args, cosine_lr, evaluate_held_out, gemm_plan_hook, global_mean_loss, held_out_of, log_evaluation, memory_stats, micro_step_fusion, seed_all, select_device, setup_distributed, unwrap_batch
 from .configs import TrainingConfig
 from .optim import flat_store_optimizer
 
@@ -402,6 +402,7 @@ def build_parser() -> argparse.ArgumentParser:
                         "chunks): ~56 %% of the default peak memory at -3 %% tok/s")
     add_eval_args(p)
     add_doc_mask_args(p)
+    add_model_args(p)
     return p
 
 
@@ -450,6 +451,7 @@ def main(argv=None):
             setattr(tc, k, v)
     if args.seq_len:
         model_config.max_seq_len = args.seq_len
+    apply_model_args(args, model_config)
     if args.memory_lean:
         tc.defer_roles = LEAN_DEFER_ROLES
     if args.memory_first:

@@ -33,7 +33,7 @@ from ..parallel.fsdp import FSDPRuntime
 from ..utils import checkpoint as ckpt
 from ..utils import debug as dbg
 from ..utils.profiling import Profiler
-from .common import (EVAL_SEED_OFFSET, HeldOutBatches, add_doc_mask_args, add_eval_args, cosine_lr, evaluate_held_out, gemm_plan_hook,
+from .common import (EVAL_SEED_OFFSET, HeldOutBatches, add_doc_mask_args, add_eval_args, add_model_args, apply_model_args, cosine_lr, evaluate_held_out, gemm_plan_hook,
                      global_mean_loss, held_out_of, log_evaluation, memory_stats, micro_step_fusion, seed_all, select_device, setup_distributed, unwrap_batch)
 from .configs import FSDPConfig, FSDPTrainingConfig
 from .optim import FlatAdamW
@@ -425,6 +425,7 @@ def build_parser():
                         "directory, no gather (resume with --resume_from DIR)")
     add_eval_args(p)  # (--eval_data_path: this trainer reads the dummy stream only)
     add_doc_mask_args(p)
+    add_model_args(p)
     return p
 
 
@@ -460,6 +461,7 @@ def main(argv=None):
         fc.reduce_dtype = args.reduce_dtype
     if args.seq_len:
         model_config.max_seq_len = args.seq_len
+    apply_model_args(args, model_config)
     for k in ("eval_interval", "eval_batches", "doc_sep_token"):
         if getattr(args, k) is not None:
             setattr(tc, k, getattr(args, k))

@@ -307,6 +307,8 @@ def load_model_state(model: torch.nn.Module, sd: Dict[str, Any]) -> None:
 
 
 def config_to_dict(cfg) -> Dict[str, Any]:
+    if hasattr(cfg, "to_dict"):  # GPTConfig: leaves out fields an MHA config never had
+        return cfg.to_dict()
     if dataclasses.is_dataclass(cfg):
         return dataclasses.asdict(cfg)
     return dict(getattr(cfg, "__dict__", {}))

@@ -58,7 +58,7 @@ def load_yaml_config(path: str, model_cfg: GPTConfig, train_cfg, fsdp_cfg=None, 
         fields = {f.name for f in dataclasses.fields(GPTConfig)}
         kw = {k: v for k, v in m.items() if k in fields}
         if kw:
-            base = dataclasses.asdict(model_cfg)
+            base = model_cfg.to_dict()  # without num_kv_heads when it follows num_heads
             base.update(kw)
             if "hidden_size" in kw and "intermediate_size" not in kw:
                 base["intermediate_size"] = None

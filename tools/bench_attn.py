@@ -3,7 +3,9 @@
 ``--doc_len N`` also times the document-masked kernels (``doc=``) in the same run: a
 separator every N tokens (N >= S: no boundary inside the sequence, i.e. trivial bounds --
 the cost of the DOC instantiations themselves), or ``rand:N``: seeded geometric document
-lengths with mean N, different in every batch row.  The backward is one call (dQ then
+lengths with mean N, different in every batch row.  ``--kv_heads N`` times grouped-query
+attention: N K/V heads shared by groups of nh / N query heads (the GQA kernels; N == nh
+runs them with groups of one, no flag the MHA kernels).  The backward is one call (dQ then
 dK/dV); a kernel trace of this tool (``tools/ab/prof_step.sh`` style: ``rocprofv3
 --kernel-trace --stats``) splits it per kernel."""
 import argparse
@@ -73,12 +75,19 @@ def main():
     ap.add_argument("--doc_len", default=None, metavar="N|rand:N",
                     help="also time the document-masked kernels: a separator every N tokens, or seeded geometric "
                          "lengths with mean N (rand:N); N >= S gives trivial bounds")
+    ap.add_argument("--kv_heads", type=int, default=None, metavar="N",
+                    help="grouped-query attention with N K/V heads (must divide --nh); default: the MHA kernels")
     ap.add_argument("--only", default="both", choices=("both", "off", "doc"),
                     help="which variants to run (a kernel trace of one variant: --only off / --only doc)")
     a = ap.parse_args()
     dt = torch.bfloat16 if a.dtype == "bf16" else torch.float16
     torch.manual_seed(0)
-    q, k, v = (torch.randn(a.B, a.nh, a.S, 64, device="cuda").to(dt) for _ in range(3))
+    nkv = a.nh if a.kv_heads is None else a.kv_heads
+    if nkv < 1 or a.nh % nkv:
+        raise ValueError("--kv_heads must divide --nh")
+    gkw = {} if a.kv_heads is None else {"nkv": nkv}
+    q = torch.randn(a.B, a.nh, a.S, 64, device="cuda").to(dt)
+    k, v = (torch.randn(a.B, nkv, a.S, 64, device="cuda").to(dt) for _ in range(2))
     key = rng.site_key(1, 2, 3, rng.SITE_ATTN)
     variants = []
     if a.only != "doc" or a.doc_len is None:
@@ -88,10 +97,15 @@ def main():
         variants.append((f"doc_len {a.doc_len} ({100 * attended_fraction(doc, a.S):.1f} % of the causal scores)",
                          {"doc": doc}))
     fl = 4 * a.B * a.nh * a.S * a.S / 2 * 64
+    if a.kv_heads is not None:
+        nrb = (a.S + 63) // 64
+        print(f"kv_heads {nkv} (groups of {a.nh // nkv}): dK/dV runs {a.B * nkv * nrb} work items "
+              f"(MHA: {a.B * a.nh * nrb}), each over {a.nh // nkv} query heads")
     for name, kw in variants:
+        kw = dict(kw, **gkw)
         tag = f"[{name}] " if a.doc_len is not None else ""  # the plain run prints what it always has
         if a.packed:
-            qkv = torch.randn(a.B * a.S, 3 * a.nh * 64, device="cuda").to(dt)
+            qkv = torch.randn(a.B * a.S, (a.nh + 2 * nkv) * 64, device="cuda").to(dt)
             cos, sin = hip.rope_tables(64, a.S, device="cuda")
             o, aux = hip.attention_fwd_packed(qkv, a.B, a.S, a.nh, a.p, key, **kw)
             do = torch.randn_like(o)
