@@ -438,6 +438,16 @@ __device__ __forceinline__ float block_excl_scan(float v, float* scr, float* tot
   return base + incl - v;
 }
 
+// The draw's uniform: the hash's top 24 bits on the grid {0, 2^-24, ..., 1 - 2^-24}, every
+// point and the scaling exact in fp32 (the earlier (bits + 0.5) * 2^-24 rounded to 1.0 for
+// bits = 2^24 - 1).  The draw inverts the block's cumulative sum at u = draw_uniform * total:
+// thread t (own > 0) holds [before_t, before_t'), t' the next thread with own > 0, and the
+// last such thread holds [before_t, inf) -- the owner is the LAST thread with own > 0 and
+// before <= u.  The first thread with own > 0 has before == 0 <= u, so an owner exists for
+// every hash value, the intervals leave no gap whatever the rounding of the block scan, and
+// the owner picks one of its own kept elements: the id is always in the kept set.
+__device__ __forceinline__ float draw_uniform(uint32_t h) { return (float)(h >> 8) * (1.f / 16777216.f); }
+
 // The k-th largest key of the row (k >= 1): radix select over bit fields [31:20], [19:8],
 // [7:0]; key_at(j) returns this thread's j-th key (j < C), re-read from L2 each pass.
 template <typename KeyAt>
@@ -566,10 +576,12 @@ __device__ void sample_row(const float* __restrict__ logits, int V, float temper
   const float before = block_excl_scan(own, scr, &total);
   const long pos = posp[0];
   const uint32_t h = lowbias32(seed ^ lowbias32((uint32_t)pos * 0x9E3779B9u + (uint32_t)b));
-  const float u = ((h >> 8) + 0.5f) * (1.f / 16777216.f) * total;  // (0, total)
-  if (tid == 0) sel[0] = -1;
+  const float u = draw_uniform(h) * total;
+  if (tid == 0) sel[0] = sel[1] = -1;
   __syncthreads();
-  if (own > 0.f && before <= u && u < before + own) {
+  if (own > 0.f && before <= u) atomicMax(&sel[0], tid);  // the owner: see draw_uniform()
+  __syncthreads();
+  if (tid == sel[0]) {
     float cum = before;
     int pick = -1, last = -1;
     for (int j = 0; j < C; ++j) {
@@ -583,12 +595,12 @@ __device__ void sample_row(const float* __restrict__ logits, int V, float temper
         }
       }
     }
-    sel[0] = pick >= 0 ? pick : last;  // rounding at the slice end: its last kept value
+    sel[1] = pick >= 0 ? pick : last;  // u at or past the slice's own sum: its last kept value
   }
   __syncthreads();
   if (tid == 0) {
-    int pick = sel[0];
-    if (pick < 0) pick = 0;  // unreachable unless every probability underflowed
+    int pick = sel[1];
+    if (pick < 0) pick = 0;  // no owner: only a row without one finite logit (own is NaN everywhere)
     ids[b] = pick;
     const long t = pos + 1 - hist_base;  // the token that will sit at position pos + 1
     if (t >= 0 && t < hist_len) hist[(size_t)b * hist_len + t] = pick;
@@ -614,7 +626,7 @@ constexpr int SMP_NS = 16, SMP_MAXC = 128, SMP_SLICE = 4096;
 
 __global__ __launch_bounds__(SMP_NT) void k_dec_topk_slices(const float* __restrict__ logits, int V,
                                                             float temperature, int top_k, int* __restrict__ ws) {
-  __shared__ uint32_t keys[SMP_SLICE];
+  __shared__ __attribute__((aligned(16))) uint32_t keys[SMP_SLICE];
   __shared__ uint32_t bins[4096];
   __shared__ float scr[40];
   __shared__ int sel[2];
@@ -648,20 +660,32 @@ __global__ __launch_bounds__(SMP_NT) void k_dec_topk_slices(const float* __restr
     auto key_at = [&](int j) { return keys[tid + SMP_NT * j]; };
     lt = max(lt, kth_key(key_at, SMP_SLICE / SMP_NT, top_k, bins, scr, sel));
   }
-  if (tid == 0) sel[0] = 0;
-  __syncthreads();
-  for (int i = tid; i < n; i += SMP_NT) {
-    const uint32_t k = keys[i];
-    if (k >= lt) {
-      const int slot = atomicAdd(&sel[0], 1);
+  // The candidates go out in index order (thread t owns elements [8t, 8t + 8), slots from a
+  // block scan of the counts, exact in fp32 up to 2^24): k_dec_topk_draw walks them in slot
+  // order, so the sampled id is a pure function of (row, seed, pos).  Slots handed out by an
+  // atomic counter made the same call return different ids from run to run.
+  constexpr int PT = SMP_SLICE / SMP_NT;
+  static_assert(PT == 8, "two 16-byte LDS reads per thread");
+  uint32_t kk[PT];
+  *reinterpret_cast<uint4*>(&kk[0]) = *reinterpret_cast<const uint4*>(&keys[tid * PT]);
+  *reinterpret_cast<uint4*>(&kk[4]) = *reinterpret_cast<const uint4*>(&keys[tid * PT + 4]);
+  float mine = 0.f;
+#pragma unroll
+  for (int q = 0; q < PT; ++q) mine += tid * PT + q < n && kk[q] >= lt ? 1.f : 0.f;
+  float tot;
+  int slot = (int)block_excl_scan(mine, scr, &tot);
+#pragma unroll
+  for (int q = 0; q < PT; ++q) {
+    const int i = tid * PT + q;
+    if (i < n && kk[q] >= lt) {
       if (slot < SMP_MAXC) {
-        ck[slot] = (int)k;
+        ck[slot] = (int)kk[q];
         ci[slot] = lo + i;
       }
+      ++slot;
     }
   }
-  __syncthreads();
-  if (tid == 0) cnt[sl] = sel[0] <= SMP_MAXC ? sel[0] : -1;  // -1: overflow
+  if (tid == 0) cnt[sl] = (int)tot <= SMP_MAXC ? (int)tot : -1;  // -1: overflow
 }
 
 __global__ __launch_bounds__(SMP_NT) void k_dec_topk_draw(const int* __restrict__ ws, const float* __restrict__ logits,
@@ -697,7 +721,8 @@ __global__ __launch_bounds__(SMP_NT) void k_dec_topk_draw(const int* __restrict_
   __syncthreads();
   constexpr int PT = SMP_NS * SMP_MAXC / SMP_NT;  // candidates per thread: tid + SMP_NT * j
   auto key_at = [&](int j) { return ckey[tid + SMP_NT * j]; };
-  const uint32_t thr = max(1u, kth_key(key_at, PT, top_k, bins, scr, sel));
+  // as in sample_row: never keep -inf (fewer than top_k finite logits) or the 0 padding
+  const uint32_t thr = max(f2key(-INFINITY) + 1, kth_key(key_at, PT, top_k, bins, scr, sel));
   const float mx = key2f(kmax);
   float own = 0.f;
 #pragma unroll
@@ -709,10 +734,12 @@ __global__ __launch_bounds__(SMP_NT) void k_dec_topk_draw(const int* __restrict_
   const float before = block_excl_scan(own, scr, &total);
   const long pos = posp[0];
   const uint32_t h = lowbias32(seed ^ lowbias32((uint32_t)pos * 0x9E3779B9u + (uint32_t)b));
-  const float u = ((h >> 8) + 0.5f) * (1.f / 16777216.f) * total;
-  if (tid == 0) sel[0] = -1;
+  const float u = draw_uniform(h) * total;
+  if (tid == 0) sel[0] = sel[1] = -1;
   __syncthreads();
-  if (own > 0.f && before <= u && u < before + own) {
+  if (own > 0.f && before <= u) atomicMax(&sel[0], tid);  // the owner: see draw_uniform()
+  __syncthreads();
+  if (tid == sel[0]) {
     float cum = before;
     int pick = -1, last = -1;
 #pragma unroll
@@ -724,11 +751,11 @@ __global__ __launch_bounds__(SMP_NT) void k_dec_topk_draw(const int* __restrict_
         if (pick < 0 && u < cum) pick = last;
       }
     }
-    sel[0] = pick >= 0 ? pick : last;
+    sel[1] = pick >= 0 ? pick : last;
   }
   __syncthreads();
   if (tid == 0) {
-    const int pick = sel[0] < 0 ? 0 : sel[0];
+    const int pick = sel[1] < 0 ? 0 : sel[1];  // no owner: only a row without one finite logit
     ids[b] = pick;
     const long t = pos + 1 - hist_base;
     if (t >= 0 && t < hist_len) hist[(size_t)b * hist_len + t] = pick;
