@@ -40,7 +40,7 @@
 //    dK/dV staying in registers -- no atomics, bitwise reproducible.
 //
 // Layouts: q, k, v, dq, dk, dv: strided views -- head-major [B*nh, S, 64] or the
-// packed [B*S, 3, nh, 64] QKV GEMM output (see dlt_attn_fwd_ex); o, do: [B, S, nh, 64]
+// packed [B*S, 3, nh, 64] QKV GEMM output (see dlt_attn_stride); o, do: [B, S, nh, 64]
 // bf16 (= the [M, H] GEMM layout);  lse, delta: [B*nh, S] fp32 (natural-log lse).
 #include "common.h"
 
@@ -1422,27 +1422,16 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_bwd_dq(const bf16_t* 
     }                            \
   } while (0)
 static inline bool attn_hd_ok(int hd) { return hd == 64 || hd == 128; }
-// document mask dispatch: DOCC = true with the bound array, false (the causal-only kernels) without
-#define DLT_DOC_DISPATCH(ptr, ...) \
-  do {                             \
-    if (ptr) {                     \
-      constexpr bool DOCC = true;  \
-      __VA_ARGS__;                 \
-    } else {                       \
-      constexpr bool DOCC = false; \
-      __VA_ARGS__;                 \
-    }                              \
-  } while (0)
-// grouped-query dispatch: GQAC = true for the entry points that take nkv (any nkv, also nkv == nh)
-#define DLT_GQA_DISPATCH(on, ...)  \
-  do {                             \
-    if (on) {                      \
-      constexpr bool GQAC = true;  \
-      __VA_ARGS__;                 \
-    } else {                       \
-      constexpr bool GQAC = false; \
-      __VA_ARGS__;                 \
-    }                              \
+// boolean dispatch: defines `constexpr bool NAME` = (cond) inside the body
+#define DLT_BOOL_DISPATCH(NAME, cond, ...) \
+  do {                                     \
+    if (cond) {                            \
+      constexpr bool NAME = true;          \
+      __VA_ARGS__;                         \
+    } else {                               \
+      constexpr bool NAME = false;         \
+      __VA_ARGS__;                         \
+    }                                      \
   } while (0)
 // XCD-aware work map on by default; DLT_ATTN_XCD=0 restores the natural order (A/B).
 static int xcd_map_enabled() {
@@ -1475,163 +1464,105 @@ DLT_API int dlt_attn_dropout_mask(uint32_t* mask, int B, int nh, int S, uint32_t
   DLT_CHECK_LAUNCH();
 }
 
-// gen_mask = 0: the keep bits are already in `mask` (dlt_attn_dropout_mask).
-// q/k/v element (b, head, row, d) lives at base + b*in_bs + head*in_hs + row*in_rs + d:
-// head-major [B*nh, S, 64] (bs = nh*S*64, hs = S*64, rs = 64) or straight inside the
-// packed [B*S, 3H] QKV GEMM output (bs = S*3H, hs = 64, rs = 3H; k, v = q + H, q + 2H).
-// dlt_attn_fwd_doc: the same with the document mask's lo [B, S] (int32; null = causal only).
-static int attn_fwd_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse, uint32_t* mask,
-                           int B, int nh, int S, int hd, float scale, uint32_t key, uint32_t thr, float dscale,
-                           int gen_mask, long in_bs, int in_hs, int in_rs, int hk, const int* lo, hipStream_t st,
-                           int nkv = 0, long kv_bs = 0, int kv_hs = 0, int kv_rs = 0) {
-  // nkv > 0: the GQA kernels, k / v with nkv heads and their own strides (dlt_attn_fwd_gqa)
-  if (!attn_hd_ok(hd) || S <= 0 || in_rs % 8 || in_hs % 8 || in_bs % 8) return -1;
-  if (nkv < 0 || (nkv && (nh % nkv || kv_rs % 8 || kv_hs % 8 || kv_bs % 8))) return -5;
+// One tensor's layout: element (b, head, row, d) lives at base + b*b + head*h + row*r + d.
+// Head-major [B*nh, S, hd]: {nh*S*hd, S*hd, hd}; inside the packed [B*S, 3H] QKV GEMM
+// output: {S*3H, hd, 3H} with k, v = q + H, q + 2H.
+struct dlt_attn_stride {
+  long b;
+  int h, r;
+};
+// Arguments of dlt_attn_fwd and dlt_attn_bwd; the forward ignores the backward's fields.
+struct dlt_attn_args {
+  const bf16_t *q, *k, *v;
+  bf16_t* o;    // [B*S, nh*hd]: written by the forward, read by the backward
+  float* lse;   // [B, nh, S], per query head
+  // uint32 [2][B*nh, ceil(S/32), S] keep bits, needed when thr != 0 -- [0] row layout
+  // (lane = query), [1] transposed (lane = key), see k_dropout_bits; per query head
+  uint32_t* mask;
+  const bf16_t* dout;
+  float* delta_ws;  // [B, nh, S] workspace: rowsum(dO * O), written by dQ for dK/dV
+  bf16_t *dq, *dk, *dv;
+  // document mask's bounds, int32 [B, S]; null = causal only.  The forward and dQ read lo,
+  // dK/dV reads hi: the backward takes both or neither
+  const int *lo, *hi;
+  // [>= S, 32] fp32, both or neither: the backward applies the inverse RoPE rotation to dq
+  // and dk in the store (the gradient w.r.t. the pre-rotation q/k of the packed QKV)
+  const float *cosT, *sinT;
+  int B, nh;
+  // 0: the MHA kernels.  > 0: the GQA kernels (also for nkv == nh) -- k / v, dk / dv hold nkv
+  // heads (nkv divides nh; query head h reads kv head h / (nh / nkv)) with the kv / dkv
+  // strides, which the MHA kernels do not read (k, v follow q's strides, dk, dv follow dq's)
+  int nkv;
+  int S, hd, hk;
+  float scale, dscale;
+  uint32_t key, thr;  // thr != 0: dropout on
+  int gen_mask;       // forward; 0: the keep bits are already in `mask` (dlt_attn_dropout_mask)
+  struct {
+    dlt_attn_stride q, kv, dq, dkv;
+  } stride;
+};
+// ops/hip.py mirrors the struct field by field: a field added on one side only must not load
+static_assert(sizeof(dlt_attn_args) == 232, "dlt_attn_args changed: update _AttnArgs in ops/hip.py");
+DLT_API int dlt_attn_args_size() { return (int)sizeof(dlt_attn_args); }
+static inline bool attn_stride_ok(const dlt_attn_stride& s, int m) { return !(s.r % m || s.h % m || s.b % m); }
+
+DLT_API int dlt_attn_fwd(const dlt_attn_args* a, hipStream_t st) {
+  const int nh = a->nh, nkv = a->nkv, S = a->S;
+  const dlt_attn_stride sq = a->stride.q, skv = nkv ? a->stride.kv : dlt_attn_stride{0, 0, 0};
+  if (!attn_hd_ok(a->hd) || S <= 0 || !attn_stride_ok(sq, 8)) return -1;
+  if (nkv < 0 || (nkv && (nh % nkv || !attn_stride_ok(skv, 8)))) return -5;
   const int G = nkv ? nh / nkv : 1;
-  if (thr && !mask) return -2;  // dropout needs the keep-bit buffer
+  if (a->thr && !a->mask) return -2;  // dropout needs the keep-bit buffer
   const int nrb = (S + RB - 1) / RB;
   const int xm = xcd_map_enabled();
-  const dim3 grid(attn_grid(nrb, B * nh, xm));  // work items, see work_item()
-  const float c_log2 = scale * LOG2E;
-  if (thr) {
-    if (gen_mask) {
-      const int rc = dlt_attn_dropout_mask(mask, B, nh, S, key, thr, st);
-      if (rc) return rc;
-    }
-    DLT_GQA_DISPATCH(nkv, DLT_DOC_DISPATCH(lo, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk,
-                         k_attn_fwd<true, HKC, HDC, DOCC, GQAC><<<grid, NT, 0, st>>>(
-                             q, k, v, o, lse, mask, S, nh, c_log2, dscale, in_bs, in_hs, in_rs, xm, lo, G, kv_bs, kv_hs,
-                             kv_rs)))));
-  } else {
-    DLT_GQA_DISPATCH(nkv, DLT_DOC_DISPATCH(lo, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk,
-                         k_attn_fwd<false, HKC, HDC, DOCC, GQAC><<<grid, NT, 0, st>>>(
-                             q, k, v, o, lse, nullptr, S, nh, c_log2, dscale, in_bs, in_hs, in_rs, xm, lo, G, kv_bs,
-                             kv_hs, kv_rs)))));
+  const dim3 grid(attn_grid(nrb, a->B * nh, xm));  // work items, see work_item()
+  const float c_log2 = a->scale * LOG2E;
+  if (a->thr && a->gen_mask) {
+    const int rc = dlt_attn_dropout_mask(a->mask, a->B, nh, S, a->key, a->thr, st);
+    if (rc) return rc;
   }
+  DLT_BOOL_DISPATCH(DROPC, a->thr, DLT_BOOL_DISPATCH(GQAC, nkv, DLT_BOOL_DISPATCH(DOCC, a->lo,
+      DLT_HD_DISPATCH(a->hd, DLT_HK_DISPATCH(a->hk, k_attn_fwd<DROPC, HKC, HDC, DOCC, GQAC><<<grid, NT, 0, st>>>(
+          a->q, a->k, a->v, a->o, a->lse, DROPC ? a->mask : nullptr, S, nh, c_log2, a->dscale, sq.b, sq.h, sq.r, xm,
+          a->lo, G, skv.b, skv.h, skv.r))))));
   DLT_CHECK_LAUNCH();
 }
-DLT_API int dlt_attn_fwd_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse, uint32_t* mask,
-                            int B, int nh, int S, int hd, float scale, uint32_t key, uint32_t thr, float dscale,
-                            int gen_mask, long in_bs, int in_hs, int in_rs, int hk, hipStream_t st) {
-  return attn_fwd_launch(q, k, v, o, lse, mask, B, nh, S, hd, scale, key, thr, dscale, gen_mask, in_bs, in_hs, in_rs, hk,
-                         nullptr, st);
-}
-DLT_API int dlt_attn_fwd_doc(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse, uint32_t* mask,
-                             int B, int nh, int S, int hd, float scale, uint32_t key, uint32_t thr, float dscale,
-                             int gen_mask, long in_bs, int in_hs, int in_rs, int hk, const int* lo, hipStream_t st) {
-  return attn_fwd_launch(q, k, v, o, lse, mask, B, nh, S, hd, scale, key, thr, dscale, gen_mask, in_bs, in_hs, in_rs, hk,
-                         lo, st);
-}
-// Grouped-query attention: k / v hold nkv heads (nkv divides nh; query head h reads kv head
-// h / (nh / nkv)) at base + b*kv_bs + kvh*kv_hs + row*kv_rs.  lo: the document mask's lower
-// bounds, or null.  o, lse and the keep bits are per query head, as above.
-DLT_API int dlt_attn_fwd_gqa(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse, uint32_t* mask,
-                             int B, int nh, int nkv, int S, int hd, float scale, uint32_t key, uint32_t thr,
-                             float dscale, int gen_mask, long in_bs, int in_hs, int in_rs, long kv_bs, int kv_hs,
-                             int kv_rs, int hk, const int* lo, hipStream_t st) {
-  if (nkv <= 0) return -5;
-  return attn_fwd_launch(q, k, v, o, lse, mask, B, nh, S, hd, scale, key, thr, dscale, gen_mask, in_bs, in_hs, in_rs, hk,
-                         lo, st, nkv, kv_bs, kv_hs, kv_rs);
-}
 
-DLT_API int dlt_attn_fwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse, uint32_t* mask,
-                         int B, int nh, int S, int hd, float scale, uint32_t key, uint32_t thr, float dscale,
-                         int gen_mask, int hk, hipStream_t st) {
-  return dlt_attn_fwd_ex(q, k, v, o, lse, mask, B, nh, S, hd, scale, key, thr, dscale, gen_mask,
-                         (long)nh * S * hd, S * hd, hd, hk, st);
-}
-
-// dq/dk/dv use the (out_bs, out_hs, out_rs) layout; with cosT/sinT ([>= S, 32] fp32)
-// the inverse RoPE rotation is applied to dq and dk in the store (the gradient w.r.t.
-// the pre-rotation q/k of the packed QKV).
-// dlt_attn_bwd_doc: the same with the document mask's lo (dQ) and hi (dK/dV), both
-// int32 [B, S] and given together (both null = causal only).
-static int attn_bwd_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o, const bf16_t* dout,
-                           const float* lse, const uint32_t* mask, float* delta_ws, bf16_t* dq, bf16_t* dk,
-                           bf16_t* dv, int B, int nh, int S, int hd, float scale, float dscale, long in_bs,
-                           int in_hs, int in_rs, long out_bs, int out_hs, int out_rs, const float* cosT,
-                           const float* sinT, int hk, const int* lo, const int* hi, hipStream_t st, int nkv = 0,
-                           long kv_bs = 0, int kv_hs = 0, int kv_rs = 0, long kvo_bs = 0, int kvo_hs = 0,
-                           int kvo_rs = 0) {
-  // nkv > 0: the GQA kernels (dlt_attn_bwd_gqa) -- k / v read with the kv strides, dk / dv
-  // written with the kvo strides, dK/dV grid over the B * nkv KV heads
-  if ((lo == nullptr) != (hi == nullptr)) return -4;
-  if (nkv < 0 || (nkv && (nh % nkv || kv_rs % 8 || kv_hs % 8 || kv_bs % 8 || kvo_rs % 4 || kvo_hs % 4 || kvo_bs % 4)))
-    return -5;
+DLT_API int dlt_attn_bwd(const dlt_attn_args* a, hipStream_t st) {
+  const int nh = a->nh, nkv = a->nkv, S = a->S;
+  const dlt_attn_stride sq = a->stride.q, sdq = a->stride.dq;
+  const dlt_attn_stride skv = nkv ? a->stride.kv : dlt_attn_stride{0, 0, 0}, sdkv = nkv ? a->stride.dkv : sdq;
+  if ((a->lo == nullptr) != (a->hi == nullptr)) return -4;
+  if (nkv < 0 || (nkv && (nh % nkv || !attn_stride_ok(skv, 8) || !attn_stride_ok(sdkv, 4)))) return -5;
   const int G = nkv ? nh / nkv : 1;
-  if (!attn_hd_ok(hd) || S <= 0 || in_rs % 8 || in_hs % 8 || in_bs % 8 || out_rs % 4 || out_hs % 4 || out_bs % 4)
-    return -1;
-  if ((cosT == nullptr) != (sinT == nullptr)) return -3;
-  const float c_log2 = scale * LOG2E;
+  if (!attn_hd_ok(a->hd) || S <= 0 || !attn_stride_ok(sq, 8) || !attn_stride_ok(sdq, 4)) return -1;
+  if ((a->cosT == nullptr) != (a->sinT == nullptr)) return -3;
+  if (a->thr && !a->mask) return -2;
+  const float scale = a->scale, dscale = a->dscale, c_log2 = scale * LOG2E;
   const int nrb = (S + RB - 1) / RB;
   const int xm = xcd_map_enabled();
-  const dim3 gk(attn_grid(nrb, B * (nkv ? nkv : nh), xm)), gq(attn_grid(nrb, B * nh, xm));  // work items, see work_item()
+  const dim3 gk(attn_grid(nrb, a->B * (nkv ? nkv : nh), xm)), gq(attn_grid(nrb, a->B * nh, xm));  // work items, see work_item()
+  // dK/dV's lanes are keys: it reads the transposed keep bits
+  const uint32_t* mask = a->thr ? a->mask : nullptr;
+  const uint32_t* maskT = mask ? mask + (size_t)a->B * nh * S * ((S + 31) / 32) : nullptr;
   // dQ first: it also produces Delta = rowsum(dO * O) (no separate kernel), which
-  // dK/dV then reads.
-  if (mask) {
-    const uint32_t* maskT = mask + (size_t)B * nh * S * ((S + 31) / 32);
-    DLT_GQA_DISPATCH(nkv, DLT_DOC_DISPATCH(lo, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk,
-                         k_attn_bwd_dq<true, HKC, HDC, DOCC, GQAC><<<gq, NT, 0, st>>>(
-                             q, k, v, dout, o, lse, delta_ws, mask, dq, S, nh, c_log2, scale, dscale, in_bs, in_hs, in_rs,
-                             out_bs, out_hs, out_rs, cosT, sinT, xm, lo, G, kv_bs, kv_hs, kv_rs)))));
-    if (nkv)
-      DLT_DOC_DISPATCH(hi, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_bwd_dkdv_gqa<true, HKC, HDC, DOCC><<<gk, NT, 0, st>>>(
-                              q, k, v, dout, lse, delta_ws, maskT, dk, dv, S, nh, c_log2, scale, dscale, in_bs, in_hs,
-                              in_rs, kvo_bs, kvo_hs, kvo_rs, cosT, sinT, xm, hi, G, kv_bs, kv_hs, kv_rs))));
+  // dK/dV then reads.  DROPC spans the three launches: the device code lists the kernels
+  // in the order the launches name them (dQ, dK/dV GQA, dK/dV with dropout, then without).
+  DLT_BOOL_DISPATCH(DROPC, mask, {
+    DLT_BOOL_DISPATCH(GQAC, nkv, DLT_BOOL_DISPATCH(DOCC, a->lo, DLT_HD_DISPATCH(a->hd, DLT_HK_DISPATCH(a->hk,
+        k_attn_bwd_dq<DROPC, HKC, HDC, DOCC, GQAC><<<gq, NT, 0, st>>>(
+            a->q, a->k, a->v, a->dout, a->o, a->lse, a->delta_ws, mask, a->dq, S, nh, c_log2, scale, dscale, sq.b,
+            sq.h, sq.r, sdq.b, sdq.h, sdq.r, a->cosT, a->sinT, xm, a->lo, G, skv.b, skv.h, skv.r)))));
+    if (nkv)  // grid over the B * nkv KV heads
+      DLT_BOOL_DISPATCH(DOCC, a->hi, DLT_HD_DISPATCH(a->hd, DLT_HK_DISPATCH(a->hk,
+          k_attn_bwd_dkdv_gqa<DROPC, HKC, HDC, DOCC><<<gk, NT, 0, st>>>(
+              a->q, a->k, a->v, a->dout, a->lse, a->delta_ws, maskT, a->dk, a->dv, S, nh, c_log2, scale, dscale, sq.b,
+              sq.h, sq.r, sdkv.b, sdkv.h, sdkv.r, a->cosT, a->sinT, xm, a->hi, G, skv.b, skv.h, skv.r))));
     else
-      DLT_DOC_DISPATCH(hi, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_bwd_dkdv<true, HKC, HDC, DOCC><<<gk, NT, 0, st>>>(
-                              q, k, v, dout, lse, delta_ws, maskT, dk, dv, S, nh, c_log2, scale, dscale, in_bs, in_hs,
-                              in_rs, out_bs, out_hs, out_rs, cosT, sinT, xm, hi))));
-  } else {
-    DLT_GQA_DISPATCH(nkv, DLT_DOC_DISPATCH(lo, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk,
-                         k_attn_bwd_dq<false, HKC, HDC, DOCC, GQAC><<<gq, NT, 0, st>>>(
-                             q, k, v, dout, o, lse, delta_ws, mask, dq, S, nh, c_log2, scale, dscale, in_bs, in_hs, in_rs,
-                             out_bs, out_hs, out_rs, cosT, sinT, xm, lo, G, kv_bs, kv_hs, kv_rs)))));
-    if (nkv)
-      DLT_DOC_DISPATCH(hi, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_bwd_dkdv_gqa<false, HKC, HDC, DOCC><<<gk, NT, 0, st>>>(
-                              q, k, v, dout, lse, delta_ws, mask, dk, dv, S, nh, c_log2, scale, dscale, in_bs, in_hs,
-                              in_rs, kvo_bs, kvo_hs, kvo_rs, cosT, sinT, xm, hi, G, kv_bs, kv_hs, kv_rs))));
-    else
-      DLT_DOC_DISPATCH(hi, DLT_HD_DISPATCH(hd, DLT_HK_DISPATCH(hk, k_attn_bwd_dkdv<false, HKC, HDC, DOCC><<<gk, NT, 0, st>>>(
-                              q, k, v, dout, lse, delta_ws, mask, dk, dv, S, nh, c_log2, scale, dscale, in_bs, in_hs,
-                              in_rs, out_bs, out_hs, out_rs, cosT, sinT, xm, hi))));
-  }
+      DLT_BOOL_DISPATCH(DOCC, a->hi, DLT_HD_DISPATCH(a->hd, DLT_HK_DISPATCH(a->hk,
+          k_attn_bwd_dkdv<DROPC, HKC, HDC, DOCC><<<gk, NT, 0, st>>>(
+              a->q, a->k, a->v, a->dout, a->lse, a->delta_ws, maskT, a->dk, a->dv, S, nh, c_log2, scale, dscale, sq.b,
+              sq.h, sq.r, sdq.b, sdq.h, sdq.r, a->cosT, a->sinT, xm, a->hi))));
+  });
   DLT_CHECK_LAUNCH();
-}
-DLT_API int dlt_attn_bwd_ex(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o, const bf16_t* dout,
-                            const float* lse, const uint32_t* mask, float* delta_ws, bf16_t* dq, bf16_t* dk,
-                            bf16_t* dv, int B, int nh, int S, int hd, float scale, float dscale, long in_bs,
-                            int in_hs, int in_rs, long out_bs, int out_hs, int out_rs, const float* cosT,
-                            const float* sinT, int hk, hipStream_t st) {
-  return attn_bwd_launch(q, k, v, o, dout, lse, mask, delta_ws, dq, dk, dv, B, nh, S, hd, scale, dscale, in_bs, in_hs,
-                         in_rs, out_bs, out_hs, out_rs, cosT, sinT, hk, nullptr, nullptr, st);
-}
-DLT_API int dlt_attn_bwd_doc(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o, const bf16_t* dout,
-                             const float* lse, const uint32_t* mask, float* delta_ws, bf16_t* dq, bf16_t* dk,
-                             bf16_t* dv, int B, int nh, int S, int hd, float scale, float dscale, long in_bs,
-                             int in_hs, int in_rs, long out_bs, int out_hs, int out_rs, const float* cosT,
-                             const float* sinT, int hk, const int* lo, const int* hi, hipStream_t st) {
-  return attn_bwd_launch(q, k, v, o, dout, lse, mask, delta_ws, dq, dk, dv, B, nh, S, hd, scale, dscale, in_bs, in_hs,
-                         in_rs, out_bs, out_hs, out_rs, cosT, sinT, hk, lo, hi, st);
-}
-// Grouped-query backward: k / v as in dlt_attn_fwd_gqa; dq uses (out_bs, out_hs, out_rs), dk / dv
-// (nkv heads) use (kvo_bs, kvo_hs, kvo_rs).  lo / hi: the document mask's bounds, both or neither.
-DLT_API int dlt_attn_bwd_gqa(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o, const bf16_t* dout,
-                             const float* lse, const uint32_t* mask, float* delta_ws, bf16_t* dq, bf16_t* dk,
-                             bf16_t* dv, int B, int nh, int nkv, int S, int hd, float scale, float dscale, long in_bs,
-                             int in_hs, int in_rs, long kv_bs, int kv_hs, int kv_rs, long out_bs, int out_hs,
-                             int out_rs, long kvo_bs, int kvo_hs, int kvo_rs, const float* cosT, const float* sinT,
-                             int hk, const int* lo, const int* hi, hipStream_t st) {
-  if (nkv <= 0) return -5;
-  return attn_bwd_launch(q, k, v, o, dout, lse, mask, delta_ws, dq, dk, dv, B, nh, S, hd, scale, dscale, in_bs, in_hs,
-                         in_rs, out_bs, out_hs, out_rs, cosT, sinT, hk, lo, hi, st, nkv, kv_bs, kv_hs, kv_rs, kvo_bs,
-                         kvo_hs, kvo_rs);
-}
-
-DLT_API int dlt_attn_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o, const bf16_t* dout,
-                         const float* lse, const uint32_t* mask, float* delta_ws, bf16_t* dq, bf16_t* dk, bf16_t* dv,
-                         int B, int nh, int S, int hd, float scale, float dscale, int hk, hipStream_t st) {
-  const long bs = (long)nh * S * hd;
-  return dlt_attn_bwd_ex(q, k, v, o, dout, lse, mask, delta_ws, dq, dk, dv, B, nh, S, hd, scale, dscale, bs, S * hd,
-                         hd, bs, S * hd, hd, nullptr, nullptr, hk, st);
 }

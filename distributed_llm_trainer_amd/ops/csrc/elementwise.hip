@@ -243,7 +243,7 @@ __global__ __launch_bounds__(256) void k_rope_qkv_bwd(const bf16_t* __restrict__
 
 // In-place RoPE of the packed [B*S, 3, nh, hd] QKV GEMM output: the q and k column
 // blocks (2*nh contiguous heads per row) are rotated, v is untouched.  The attention
-// kernels then read q/k/v straight from this buffer (dlt_attn_fwd_ex), so no head-major
+// kernels then read q/k/v straight from this buffer (strided dlt_attn_fwd), so no head-major
 // copies are written (2/3 of the traffic of k_rope_qkv_fwd, and its backward
 // disappears into the attention epilogue).
 template <int HK = 0>
@@ -331,23 +331,20 @@ DLT_API int dlt_rope_qkv_fwd(const bf16_t* qkv, const float* cosT, const float* 
   DLT_CHECK_LAUNCH();
 }
 
-DLT_API int dlt_rope_qk_inplace(bf16_t* qkv, const float* cosT, const float* sinT, int M, int S, int nh, int hd,
-                                int hk, hipStream_t st) {
-  if (hd % 16 || S <= 0 || M % S || (long)M * 3 * nh * hd >= (1L << 31)) return -1;
-  const size_t total = (size_t)M * 2 * nh * (hd / 16);
-  DLT_HK_DISPATCH(hk, k_rope_qk_inplace<HKC><<<ew_blocks(total), 256, 0, st>>>(qkv, cosT, sinT, M, S, nh, hd));
-  DLT_CHECK_LAUNCH();
-}
-
-// packed [M, (nh + 2 nkv) * hd] rows: q (nh heads) | k (nkv heads) | v (nkv heads)
-DLT_API int dlt_rope_qk_inplace_gqa(bf16_t* qkv, const float* cosT, const float* sinT, int M, int S, int nh, int nkv,
-                                    int hd, int hk, hipStream_t st) {
-  if (hd % 16 || S <= 0 || M % S || nkv <= 0 || nh <= 0 || nh % nkv ||
-      (long)M * (nh + 2 * nkv) * hd >= (1L << 31))
+// nkv == 0: packed [M, 3 * nh * hd] rows; nkv > 0: [M, (nh + 2 nkv) * hd] rows, q (nh heads) |
+// k (nkv heads) | v (nkv heads) -- also for nkv == nh
+DLT_API int dlt_rope_qk_inplace(bf16_t* qkv, const float* cosT, const float* sinT, int M, int S, int nh, int nkv,
+                                int hd, int hk, hipStream_t st) {
+  const int nk = nkv ? nkv : nh;
+  if (hd % 16 || S <= 0 || M % S || nkv < 0 || (nkv && (nh <= 0 || nh % nkv)) ||
+      (long)M * (nh + 2 * nk) * hd >= (1L << 31))
     return -1;
-  const size_t total = (size_t)M * (nh + nkv) * (hd / 16);
-  DLT_HK_DISPATCH(hk, k_rope_qk_inplace_gqa<HKC><<<ew_blocks(total), 256, 0, st>>>(qkv, cosT, sinT, M, S, nh + nkv,
-                                                                                  (nh + 2 * nkv) * hd, hd));
+  const size_t total = (size_t)M * (nh + nk) * (hd / 16);
+  if (!nkv)
+    DLT_HK_DISPATCH(hk, k_rope_qk_inplace<HKC><<<ew_blocks(total), 256, 0, st>>>(qkv, cosT, sinT, M, S, nh, hd));
+  else
+    DLT_HK_DISPATCH(hk, k_rope_qk_inplace_gqa<HKC><<<ew_blocks(total), 256, 0, st>>>(qkv, cosT, sinT, M, S, nh + nkv,
+                                                                                    (nh + 2 * nkv) * hd, hd));
   DLT_CHECK_LAUNCH();
 }
 

@@ -77,34 +77,12 @@ _SIGS = {
                          c_void_p],
     "dlt_gemm_bf16_down_swiglu_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                       c_int, c_void_p],
-    "dlt_attn_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
-                     c_uint32, c_uint32, c_float, c_int, c_int, c_void_p],
+    # (const dlt_attn_args*, stream): see _AttnArgs
+    "dlt_attn_fwd": [c_void_p, c_void_p],
+    "dlt_attn_bwd": [c_void_p, c_void_p],
     "dlt_attn_dropout_mask": [c_void_p, c_int, c_int, c_int, c_uint32, c_uint32, c_void_p],
-    "dlt_attn_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                     c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_void_p],
-    "dlt_attn_fwd_ex": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                        c_float, c_uint32, c_uint32, c_float, c_int, ctypes.c_long, c_int, c_int, c_int, c_void_p],
-    "dlt_attn_bwd_ex": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                        c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, ctypes.c_long, c_int, c_int,
-                        ctypes.c_long, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
-    # the _ex launchers with the document mask's bounds (lo; lo, hi) before the stream
-    "dlt_attn_fwd_doc": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                         c_float, c_uint32, c_uint32, c_float, c_int, ctypes.c_long, c_int, c_int, c_int, c_void_p,
-                         c_void_p],
-    "dlt_attn_bwd_doc": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                         c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, ctypes.c_long, c_int, c_int,
-                         ctypes.c_long, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
-    "dlt_rope_qk_inplace": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    # grouped-query attention: nkv after nh, the k / v strides after q's (backward: then dq's and
-    # dk / dv's output strides), the document bounds (or null) before the stream
-    "dlt_attn_fwd_gqa": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                         c_float, c_uint32, c_uint32, c_float, c_int, ctypes.c_long, c_int, c_int, ctypes.c_long,
-                         c_int, c_int, c_int, c_void_p, c_void_p],
-    "dlt_attn_bwd_gqa": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                         c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
-                         ctypes.c_long, c_int, c_int, ctypes.c_long, c_int, c_int, ctypes.c_long, c_int, c_int,
-                         ctypes.c_long, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
-    "dlt_rope_qk_inplace_gqa": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "dlt_attn_args_size": [],
+    "dlt_rope_qk_inplace": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "dlt_dec_norm_qkv": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                          c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "dlt_dec_attn": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p],
@@ -143,6 +121,9 @@ def lib():
         L.dlt_gemm_wgrad_grp_scratch.restype = ctypes.c_long
         L.dlt_lmhead_loss_scratch.argtypes = [c_int, c_int]
         L.dlt_lmhead_loss_scratch.restype = ctypes.c_long
+        if L.dlt_attn_args_size() != ctypes.sizeof(_AttnArgs):
+            raise RuntimeError(f"{_LIBPATH}: dlt_attn_args is {L.dlt_attn_args_size()} bytes, _AttnArgs "
+                               f"{ctypes.sizeof(_AttnArgs)}: rebuild the library (ops/build.py)")
         _LIB = L
     return _LIB
 
@@ -496,33 +477,24 @@ def rope_qk_inplace(qkv, B, S, nh, cos, sin, nkv=None):
     (grouped-query attention) the row is [B*S, H + 2*KV]: nh q heads | nkv k heads | nkv v heads."""
     if nkv is not None:
         nkv = _req_nkv(nh, nkv, "rope_qk_inplace")
-        if qkv.dtype == torch.float32:
-            _no_gqa_f32("rope_qk_inplace")
-        M, Wd = qkv.shape
-        hd = Wd // (nh + 2 * nkv)
-        if M != B * S or hd * (nh + 2 * nkv) != Wd or hd % 16:
-            raise ValueError("rope_qk_inplace: qkv must be [B*S, (nh + 2*nkv)*hd] with hd % 16 == 0")
-        hk = _req_act(qkv, qkv.dtype, "rope_qk.qkv")
-        if cos.shape[0] < S or cos.shape[1] != hd // 2 or sin.shape != cos.shape:
-            raise ValueError("rope tables too short")
-        _req(cos, torch.float32, "rope_qk.cos")
-        _req(sin, torch.float32, "rope_qk.sin")
-        _chk(lib().dlt_rope_qk_inplace_gqa(_p(qkv), _p(cos), _p(sin), M, S, nh, nkv, hd, hk, _stream()),
-             "rope_qk_inplace_gqa")
-        return qkv
     if qkv.dtype == torch.float32:
+        if nkv is not None:
+            _no_gqa_f32("rope_qk_inplace")
         from . import hip_f32
         return hip_f32.rope_qk_inplace(qkv, B, S, nh, cos, sin)
-    M, threeH = qkv.shape
-    hd = threeH // (3 * nh)
-    if M != B * S or hd * 3 * nh != threeH or hd % 16:
-        raise ValueError("rope_qk_inplace: bad shapes")
+    M, Wd = qkv.shape
+    heads = 3 * nh if nkv is None else nh + 2 * nkv
+    hd = Wd // heads
+    if M != B * S or hd * heads != Wd or hd % 16:
+        raise ValueError("rope_qk_inplace: bad shapes" if nkv is None else
+                         "rope_qk_inplace: qkv must be [B*S, (nh + 2*nkv)*hd] with hd % 16 == 0")
     hk = _req_act(qkv, qkv.dtype, "rope_qk.qkv")
     if cos.shape[0] < S or cos.shape[1] != hd // 2 or sin.shape != cos.shape:
         raise ValueError("rope tables too short")
     _req(cos, torch.float32, "rope_qk.cos")
     _req(sin, torch.float32, "rope_qk.sin")
-    _chk(lib().dlt_rope_qk_inplace(_p(qkv), _p(cos), _p(sin), M, S, nh, hd, hk, _stream()), "rope_qk_inplace")
+    _chk(lib().dlt_rope_qk_inplace(_p(qkv), _p(cos), _p(sin), M, S, nh, nkv or 0, hd, hk, _stream()),
+         "rope_qk_inplace" if nkv is None else "rope_qk_inplace_gqa")
     return qkv
 
 
@@ -593,6 +565,91 @@ def _head_major_nkv(q, k, v, nkv, name: str):
     return nkv
 
 
+class _Stride(ctypes.Structure):
+    """dlt_attn_stride: element strides (batch, head, row) of one tensor."""
+    _fields_ = [("b", ctypes.c_long), ("h", c_int), ("r", c_int)]
+
+
+class _AttnStrides(ctypes.Structure):
+    _fields_ = [("q", _Stride), ("kv", _Stride), ("dq", _Stride), ("dkv", _Stride)]
+
+
+class _AttnArgs(ctypes.Structure):
+    """dlt_attn_args of csrc/attention.hip, field by field (lib() compares the sizes)."""
+    _fields_ = ([(n, c_void_p) for n in ("q", "k", "v", "o", "lse", "mask", "dout", "delta_ws", "dq", "dk", "dv",
+                                         "lo", "hi", "cosT", "sinT")]
+                + [(n, c_int) for n in ("B", "nh", "nkv", "S", "hd", "hk")]
+                + [("scale", c_float), ("dscale", c_float), ("key", c_uint32), ("thr", c_uint32),
+                   ("gen_mask", c_int), ("stride", _AttnStrides)])
+
+
+def _keep_bits_fwd(p, mask, B, nh, S, device):
+    """(thr, dscale, mask, gen) of a forward: ``mask`` is the caller's keep bits (gen = 0), a new
+    buffer for the launcher to fill (gen = 1), or None without dropout."""
+    thr = rng.keep_threshold(p)
+    if not thr:
+        return 0, 1.0, None, 1
+    if mask is not None:
+        _req(mask, torch.int32, "attn.mask", 2 * B * nh * S * ((S + 31) // 32))
+        return thr, 1.0 / (1.0 - p), mask, 0
+    # [0] row layout (lane = query), [1] transposed (lane = key) -- see attention.hip;
+    # with store_mask=False it only lives for this call (the backward regenerates it)
+    mask = torch.empty(2, B * nh, (S + 31) // 32, S, dtype=torch.int32, device=device)
+    return thr, 1.0 / (1.0 - p), mask, 1
+
+
+def _keep_bits_bwd(p, key, mask, B, nh, S, device):
+    """(thr, dscale, mask) of a backward; ``mask``: the forward's keep bits or None."""
+    thr = rng.keep_threshold(p)
+    if not thr:
+        return 0, 1.0, None
+    if mask is None:  # forward ran with store_mask=False: regenerate the keep bits only
+        mask = attention_dropout_mask(B, nh, S, p, key, device=device)
+    return thr, 1.0 / (1.0 - p), mask
+
+
+def _head_major(q, k, v):
+    """((q, k, v) pointers, q strides, k / v strides) of q [B, nh, S, hd] and k, v [B, nkv, S, hd];
+    strides are (batch, head, row) in elements."""
+    S, hd = q.shape[2], q.shape[3]
+    return (_p(q), _p(k), _p(v)), (q.shape[1] * S * hd, S * hd, hd), (k.shape[1] * S * hd, S * hd, hd)
+
+
+def _packed_row(qkv, S, H, hd, KV):
+    """The same for q | k | v inside the packed [B*S, H + 2*KV] rows."""
+    Wd = H + 2 * KV
+    return (_p(qkv), _off(qkv, H), _off(qkv, H + KV)), (S * Wd, hd, Wd), (S * Wd, hd, Wd)
+
+
+def _attn_name(name, nkv, doc):
+    return name + ("_gqa" if nkv is not None else "" if doc is None else "_doc")
+
+
+def _attn_fwd_launch(name, src, o, lse, keep, key, lo, B, nh, nkv, S, hd, hk, scale):
+    """dlt_attn_fwd on q / k / v of layout ``src`` (:func:`_head_major`, :func:`_packed_row`)
+    with ``keep`` of :func:`_keep_bits_fwd`; nkv None: the MHA kernels."""
+    (q, k, v), sq, skv = src
+    thr, dscale, mask, gen = keep
+    a = _AttnArgs(q=q, k=k, v=v, o=_p(o), lse=_p(lse), mask=_p(mask), lo=_p(lo), B=B, nh=nh, nkv=nkv or 0, S=S,
+                  hd=hd, hk=hk, scale=scale, dscale=dscale, key=key & 0xFFFFFFFF, thr=thr, gen_mask=gen,
+                  stride=_AttnStrides(q=sq, kv=skv))
+    _chk(lib().dlt_attn_fwd(ctypes.byref(a), _stream()), _attn_name(name, nkv, lo))
+
+
+def _attn_bwd_launch(name, src, dst, o, do, lse, keep, doc, rope, B, nh, nkv, S, hd, hk, scale):
+    """dlt_attn_bwd: dq / dk / dv into layout ``dst``; ``keep`` of :func:`_keep_bits_bwd`,
+    ``doc`` = (lo, hi), ``rope`` = (cos, sin) or (None, None)."""
+    (q, k, v), sq, skv = src
+    (dq, dk, dv), sdq, sdkv = dst
+    thr, dscale, mask = keep
+    delta = torch.empty(B, nh, S, dtype=torch.float32, device=lse.device)
+    a = _AttnArgs(q=q, k=k, v=v, o=_p(o), lse=_p(lse), mask=_p(mask), dout=_p(do), delta_ws=_p(delta), dq=dq, dk=dk,
+                  dv=dv, lo=_p(doc[0]), hi=_p(doc[1]), cosT=_p(rope[0]), sinT=_p(rope[1]), B=B, nh=nh, nkv=nkv or 0,
+                  S=S, hd=hd, hk=hk, scale=scale, dscale=dscale, thr=thr,
+                  stride=_AttnStrides(q=sq, kv=skv, dq=sdq, dkv=sdkv))
+    _chk(lib().dlt_attn_bwd(ctypes.byref(a), _stream()), _attn_name(name, nkv, doc[0]))
+
+
 def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=None, scale=None, doc=None,
                   nkv=None):
     """Returns (o [B*S, nh*hd] bf16, aux).  With dropout on, the keep bits are written
@@ -620,36 +677,14 @@ def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=
     o = torch.empty(B * S, nh * hd, dtype=q.dtype, device=q.device) if out is None else out
     _req(o, q.dtype, "attn.o", B * S * nh * hd)
     lse = torch.empty(B, nh, S, dtype=torch.float32, device=q.device)
-    thr = rng.keep_threshold(p)
-    dscale = 1.0 / (1.0 - p) if thr else 1.0
-    gen = 1
-    if not thr:
-        mask = None
-    elif mask is not None:
-        _req(mask, torch.int32, "attn.mask", 2 * B * nh * S * ((S + 31) // 32))
-        gen = 0
-    else:
-        # [0] row layout (lane = query), [1] transposed (lane = key) -- see attention.hip;
-        # with store_mask=False it only lives for this call (the backward regenerates it)
-        mask = torch.empty(2, B * nh, (S + 31) // 32, S, dtype=torch.int32, device=q.device)
+    keep = _keep_bits_fwd(p, mask, B, nh, S, q.device)
     sc = 1.0 / math.sqrt(hd) if scale is None else float(scale)
-    if nkv is not None:
-        _chk(lib().dlt_attn_fwd_gqa(_p(q), _p(k), _p(v), _p(o), _p(lse), _p(mask), B, nh, nkv, S, hd, sc,
-                                    key & 0xFFFFFFFF, thr, dscale, gen, nh * S * hd, S * hd, hd, nkv * S * hd, S * hd,
-                                    hd, hk, _p(lo), _stream()), "attn_fwd_gqa")
-    elif doc is None:
-        _chk(lib().dlt_attn_fwd(_p(q), _p(k), _p(v), _p(o), _p(lse), _p(mask), B, nh, S, hd, sc,
-                                key & 0xFFFFFFFF, thr, dscale, gen, hk, _stream()), "attn_fwd")
-    else:
-        _chk(lib().dlt_attn_fwd_doc(_p(q), _p(k), _p(v), _p(o), _p(lse), _p(mask), B, nh, S, hd, sc,
-                                    key & 0xFFFFFFFF, thr, dscale, gen, nh * S * hd, S * hd, hd, hk, _p(lo),
-                                    _stream()), "attn_fwd_doc")
-    return o, AttnAux((lse, mask if (store_mask or gen == 0) else None))
+    _attn_fwd_launch("attn_fwd", _head_major(q, k, v), o, lse, keep, key, lo, B, nh, nkv, S, hd, hk, sc)
+    return o, AttnAux((lse, keep[2] if (store_mask or not keep[3]) else None))
 
 
 def _packed_dims(qkv, B, S, nh, nkv=None):
-    """(M, H, hd) of the packed QKV; with ``nkv`` its rows are [H + 2*KV] and KV = nkv * hd
-    is returned too."""
+    """(M, H, hd, KV) of the packed QKV with rows [H + 2*KV]; KV = H without ``nkv``."""
     M, Wd = qkv.shape
     nk = nh if nkv is None else _req_nkv(nh, nkv, "packed attention")
     hd = Wd // (nh + 2 * nk)
@@ -659,8 +694,6 @@ def _packed_dims(qkv, B, S, nh, nkv=None):
     if hd not in ATTN_HEAD_DIMS:
         raise NotImplementedError(f"attention kernels take head_dim {ATTN_HEAD_DIMS} (got {hd})")
     _req_act(qkv, qkv.dtype, "attn.qkv")
-    if nkv is None:
-        return M, nh * hd, hd
     return M, nh * hd, hd, nk * hd
 
 
@@ -674,39 +707,15 @@ def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=
         from . import hip_f32
         return hip_f32.attention_fwd_packed(qkv, B, S, nh, p, key, out=out, mask=mask, store_mask=store_mask,
                                             doc=doc)
-    if nkv is None:
-        M, H, hd = _packed_dims(qkv, B, S, nh)
-    else:
-        M, H, hd, KV = _packed_dims(qkv, B, S, nh, nkv)
+    M, H, hd, KV = _packed_dims(qkv, B, S, nh, nkv)
     lo, _ = _req_doc(doc, B, S, qkv.device, "attn")
-    hk = _HK[qkv.dtype]
     o = torch.empty(M, H, dtype=qkv.dtype, device=qkv.device) if out is None else out
     _req(o, qkv.dtype, "attn.o", M * H)
     lse = torch.empty(B, nh, S, dtype=torch.float32, device=qkv.device)
-    thr = rng.keep_threshold(p)
-    dscale = 1.0 / (1.0 - p) if thr else 1.0
-    gen = 1
-    if not thr:
-        mask = None
-    elif mask is not None:
-        _req(mask, torch.int32, "attn.mask", 2 * B * nh * S * ((S + 31) // 32))
-        gen = 0
-    else:  # with store_mask=False it only lives for this call (the backward regenerates it)
-        mask = torch.empty(2, B * nh, (S + 31) // 32, S, dtype=torch.int32, device=qkv.device)
-    if nkv is not None:
-        Wd = H + 2 * KV
-        _chk(lib().dlt_attn_fwd_gqa(_p(qkv), _off(qkv, H), _off(qkv, H + KV), _p(o), _p(lse), _p(mask), B, nh, nkv, S,
-                                    hd, 1.0 / math.sqrt(hd), key & 0xFFFFFFFF, thr, dscale, gen, S * Wd, hd, Wd,
-                                    S * Wd, hd, Wd, hk, _p(lo), _stream()), "attn_fwd_packed_gqa")
-    elif doc is None:
-        _chk(lib().dlt_attn_fwd_ex(_p(qkv), _off(qkv, H), _off(qkv, 2 * H), _p(o), _p(lse), _p(mask), B, nh, S, hd,
-                                   1.0 / math.sqrt(hd), key & 0xFFFFFFFF, thr, dscale, gen, S * 3 * H, hd, 3 * H, hk,
-                                   _stream()), "attn_fwd_packed")
-    else:
-        _chk(lib().dlt_attn_fwd_doc(_p(qkv), _off(qkv, H), _off(qkv, 2 * H), _p(o), _p(lse), _p(mask), B, nh, S, hd,
-                                    1.0 / math.sqrt(hd), key & 0xFFFFFFFF, thr, dscale, gen, S * 3 * H, hd, 3 * H, hk,
-                                    _p(lo), _stream()), "attn_fwd_packed_doc")
-    return o, AttnAux((lse, mask if (store_mask or gen == 0) else None))
+    keep = _keep_bits_fwd(p, mask, B, nh, S, qkv.device)
+    _attn_fwd_launch("attn_fwd_packed", _packed_row(qkv, S, H, hd, KV), o, lse, keep, key, lo, B, nh, nkv, S, hd,
+                     _HK[qkv.dtype], 1.0 / math.sqrt(hd))
+    return o, AttnAux((lse, keep[2] if (store_mask or not keep[3]) else None))
 
 
 def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, doc=None, nkv=None):
@@ -720,14 +729,9 @@ def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, 
             _no_gqa_f32("attention_bwd_packed")
         from . import hip_f32
         return hip_f32.attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=out, doc=doc)
-    if nkv is None:
-        M, H, hd = _packed_dims(qkv, B, S, nh)
-        KV = H
-    else:
-        M, H, hd, KV = _packed_dims(qkv, B, S, nh, nkv)
+    M, H, hd, KV = _packed_dims(qkv, B, S, nh, nkv)
     Wd = H + 2 * KV
     lo, hi = _req_doc(doc, B, S, qkv.device, "attn_bwd")
-    hk = _HK[qkv.dtype]
     for t, nm in ((o, "o"), (do, "do")):
         _req(t, qkv.dtype, "attn_bwd." + nm, M * H)
     lse, mask = aux if isinstance(aux, tuple) else (aux, None)
@@ -736,31 +740,11 @@ def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, 
         raise ValueError("rope tables too short")
     _req(cos, torch.float32, "attn_bwd.cos")
     _req(sin, torch.float32, "attn_bwd.sin")
-    thr = rng.keep_threshold(p)
-    if thr and mask is None:  # forward ran with store_mask=False: regenerate the keep bits only
-        mask = attention_dropout_mask(B, nh, S, p, key, device=qkv.device)
-    if not thr:
-        mask = None
+    keep = _keep_bits_bwd(p, key, mask, B, nh, S, qkv.device)
     dqkv = torch.empty(M, Wd, dtype=qkv.dtype, device=qkv.device) if out is None else out
     _req(dqkv, qkv.dtype, "attn_bwd.dqkv", M * Wd)
-    delta = torch.empty(B, nh, S, dtype=torch.float32, device=qkv.device)
-    dscale = 1.0 / (1.0 - p) if thr else 1.0
-    st = S * 3 * H
-    if nkv is not None:
-        st = S * Wd
-        _chk(lib().dlt_attn_bwd_gqa(_p(qkv), _off(qkv, H), _off(qkv, H + KV), _p(o), _p(do), _p(lse), _p(mask),
-                                    _p(delta), _p(dqkv), _off(dqkv, H), _off(dqkv, H + KV), B, nh, nkv, S, hd,
-                                    1.0 / math.sqrt(hd), dscale, st, hd, Wd, st, hd, Wd, st, hd, Wd, st, hd, Wd,
-                                    _p(cos), _p(sin), hk, _p(lo), _p(hi), _stream()), "attn_bwd_packed_gqa")
-    elif doc is None:
-        _chk(lib().dlt_attn_bwd_ex(_p(qkv), _off(qkv, H), _off(qkv, 2 * H), _p(o), _p(do), _p(lse), _p(mask), _p(delta),
-                                   _p(dqkv), _off(dqkv, H), _off(dqkv, 2 * H), B, nh, S, hd, 1.0 / math.sqrt(hd), dscale,
-                                   st, hd, 3 * H, st, hd, 3 * H, _p(cos), _p(sin), hk, _stream()), "attn_bwd_packed")
-    else:
-        _chk(lib().dlt_attn_bwd_doc(_p(qkv), _off(qkv, H), _off(qkv, 2 * H), _p(o), _p(do), _p(lse), _p(mask),
-                                    _p(delta), _p(dqkv), _off(dqkv, H), _off(dqkv, 2 * H), B, nh, S, hd,
-                                    1.0 / math.sqrt(hd), dscale, st, hd, 3 * H, st, hd, 3 * H, _p(cos), _p(sin), hk,
-                                    _p(lo), _p(hi), _stream()), "attn_bwd_packed_doc")
+    _attn_bwd_launch("attn_bwd_packed", _packed_row(qkv, S, H, hd, KV), _packed_row(dqkv, S, H, hd, KV), o, do, lse,
+                     keep, (lo, hi), (cos, sin), B, nh, nkv, S, hd, _HK[qkv.dtype], 1.0 / math.sqrt(hd))
     return dqkv
 
 
@@ -779,35 +763,15 @@ def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, scale=None, doc=None
     for t, nm, cnt in ((q, "q", n), (k, "k", nk), (v, "v", nk), (o, "o", n), (do, "do", n)):
         hk = _req_act(t, q.dtype, "attn_bwd." + nm, cnt)
     lo, hi = _req_doc(doc, B, S, q.device, "attn_bwd")
-    if isinstance(aux, tuple):
-        lse, mask = aux
-    else:
-        lse, mask = aux, None
+    lse, mask = aux if isinstance(aux, tuple) else (aux, None)
     _req(lse, torch.float32, "attn_bwd.lse", B * nh * S)
-    thr = rng.keep_threshold(p)
-    if thr and mask is None:  # forward ran with store_mask=False: regenerate the keep bits only
-        mask = attention_dropout_mask(q.shape[0], q.shape[1], q.shape[2], p, key, device=q.device)
-    if not thr:
-        mask = None
-    delta = torch.empty(B, nh, S, dtype=torch.float32, device=q.device)
+    keep = _keep_bits_bwd(p, key, mask, B, nh, S, q.device)
     dq = torch.empty_like(q)
     dk = torch.empty_like(k)
     dv = torch.empty_like(v)
-    dscale = 1.0 / (1.0 - p) if thr else 1.0
     sc = 1.0 / math.sqrt(hd) if scale is None else float(scale)
-    if nkv is not None:
-        bs, hs, kbs = nh * S * hd, S * hd, nkv * S * hd
-        _chk(lib().dlt_attn_bwd_gqa(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(mask), _p(delta), _p(dq), _p(dk),
-                                    _p(dv), B, nh, nkv, S, hd, sc, dscale, bs, hs, hd, kbs, hs, hd, bs, hs, hd, kbs, hs,
-                                    hd, None, None, hk, _p(lo), _p(hi), _stream()), "attn_bwd_gqa")
-    elif doc is None:
-        _chk(lib().dlt_attn_bwd(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(mask), _p(delta), _p(dq), _p(dk),
-                                _p(dv), B, nh, S, hd, sc, dscale, hk, _stream()), "attn_bwd")
-    else:
-        bs, hs = nh * S * hd, S * hd
-        _chk(lib().dlt_attn_bwd_doc(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(mask), _p(delta), _p(dq), _p(dk),
-                                    _p(dv), B, nh, S, hd, sc, dscale, bs, hs, hd, bs, hs, hd, None, None, hk, _p(lo),
-                                    _p(hi), _stream()), "attn_bwd_doc")
+    _attn_bwd_launch("attn_bwd", _head_major(q, k, v), _head_major(dq, dk, dv), o, do, lse, keep, (lo, hi),
+                     (None, None), B, nh, nkv, S, hd, hk, sc)
     return dq, dk, dv
 
 

@@ -311,6 +311,51 @@ def test_attention_packed_fwd_bwd(S, p, hd):
     _close(got, want2, 2e-2 * max(1.0, scale), 2e-2, "dqkv packed vs fp32 ref")
 
 
+def test_attn_launch_rejects_bad_args():
+    """dlt_attn_fwd / dlt_attn_bwd return their documented code and launch nothing when one
+    scalar of an otherwise valid dlt_attn_args is wrong (B 1, nh 2, S 64, hd 64, head-major).
+    Every wrong value would keep a launch inside the buffers: a row stride of hd - 4, hd = 96
+    with the strides of hd = 64, nkv = 3 beside K/V buffers of two S-row heads."""
+    import ctypes
+    torch.manual_seed(33)
+    B, nh, S, hd = 1, 2, 64, 64
+    q, k, v, do = (torch.randn(B, nh, S, hd, device=DEV).bfloat16() for _ in range(4))
+    o = torch.full((B * S, nh * hd), 7.0, device=DEV, dtype=torch.bfloat16)
+    dq, dk, dv = (torch.full_like(q, 7.0) for _ in range(3))
+    lse = torch.zeros(B, nh, S, device=DEV)
+    delta = torch.zeros(B, nh, S, device=DEV)
+    lo = torch.zeros(B, S, dtype=torch.int32, device=DEV)
+    cos, sin = hip.rope_tables(hd, S, device=DEV)
+    hm = (nh * S * hd, S * hd, hd)
+    base = dict(q=q.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), o=o.data_ptr(), lse=lse.data_ptr(),
+                dout=do.data_ptr(), delta_ws=delta.data_ptr(), dq=dq.data_ptr(), dk=dk.data_ptr(), dv=dv.data_ptr(),
+                B=B, nh=nh, S=S, hd=hd, scale=0.125, dscale=1.0, key=77, gen_mask=1)
+    L, stream = hip.lib(), hip._stream()
+
+    def call(fn, strides=(hm, hm, hm, hm), **kw):
+        a = hip._AttnArgs(**{**base, **kw}, stride=hip._AttnStrides(*strides))
+        rc = fn(ctypes.byref(a), stream)
+        torch.cuda.synchronize()
+        return rc
+
+    odd = (hm[0], hm[1], hd - 4)
+    cases = [("row stride % 8", -1, dict(strides=(odd, hm, hm, hm)), "fb"),
+             ("hd 96", -1, dict(hd=96), "fb"),
+             ("thr without mask", -2, dict(thr=6554), "fb"),
+             ("cosT without sinT", -3, dict(cosT=cos.data_ptr()), "b"),
+             ("lo without hi", -4, dict(lo=lo.data_ptr()), "b"),
+             ("nkv 3 for nh 2", -5, dict(nkv=3), "fb")]
+    for what, code, kw, dirs in cases:
+        for d in dirs:
+            assert call(L.dlt_attn_fwd if d == "f" else L.dlt_attn_bwd, **kw) == code, (what, d)
+            for t in (o, dq, dk, dv):
+                assert (t == 7.0).all(), (what, d, "an output was written")
+    # the base is valid: without the one wrong scalar both directions launch
+    assert call(L.dlt_attn_fwd) == 0 and (o != 7.0).any()
+    assert call(L.dlt_attn_bwd) == 0
+    assert (dq != 7.0).any() and (dk != 7.0).any() and (dv != 7.0).any()
+
+
 @pytest.mark.parametrize("M,N,K", [(8192, 2304, 768), (8192, 768, 3072), (1000, 300, 200), (256, 50304, 768)])
 def test_gemm_planner(M, N, K):
     from distributed_llm_trainer_amd.ops import gemm

@@ -10,7 +10,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from distributed_llm_trainer_amd.ops import hip, rng  # noqa: E402
-from distributed_llm_trainer_amd.ops.hip import _off, _p, _stream, lib  # noqa: E402
+from distributed_llm_trainer_amd.ops.hip import _attn_bwd_launch, _attn_fwd_launch, _packed_row  # noqa: E402
 
 
 def timeit(fn, iters=20):
@@ -35,18 +35,18 @@ cos, sin = hip.rope_tables(64, S, device="cuda")
 o, aux = hip.attention_fwd_packed(qkv, B, S, nh, p, key)
 lse, mask = aux
 do = torch.randn_like(o)
-thr = rng.keep_threshold(p)
-ds = 1.0 / (1.0 - p)
-delta = torch.empty(B, nh, S, dtype=torch.float32, device="cuda")
+keep = (rng.keep_threshold(p), 1.0 / (1.0 - p), mask)
 dqkv = torch.empty(M, 3 * H, dtype=torch.bfloat16, device="cuda")
-st = S * 3 * H
-for name, bs, hs in (("normal", st, hd), ("one head (L2)", 0, 0)):
+ptrs, st, _ = _packed_row(qkv, S, H, hd, H)
+dst = _packed_row(dqkv, S, H, hd, H)
+sc = 1.0 / math.sqrt(hd)
+for name, bs, hs in (("normal", st[0], st[1]), ("one head (L2)", 0, 0)):
+    src = (ptrs, (bs, hs, st[2]), (bs, hs, st[2]))
+
     def fwd():
-        lib().dlt_attn_fwd_ex(_p(qkv), _off(qkv, H), _off(qkv, 2 * H), _p(o), _p(lse), _p(mask), B, nh, S, hd,
-                              1.0 / math.sqrt(hd), key & 0xFFFFFFFF, thr, ds, 0, bs, hs, 3 * H, 0, _stream())
+        _attn_fwd_launch("attn_fwd_packed", src, o, lse, keep + (0,), key, None, B, nh, None, S, hd, 0, sc)
 
     def bwd():
-        lib().dlt_attn_bwd_ex(_p(qkv), _off(qkv, H), _off(qkv, 2 * H), _p(o), _p(do), _p(lse), _p(mask), _p(delta),
-                              _p(dqkv), _off(dqkv, H), _off(dqkv, 2 * H), B, nh, S, hd, 1.0 / math.sqrt(hd), ds,
-                              bs, hs, 3 * H, st, hd, 3 * H, _p(cos), _p(sin), 0, _stream())
+        _attn_bwd_launch("attn_bwd_packed", src, dst, o, do, lse, keep, (None, None), (cos, sin), B, nh, None, S, hd,
+                         0, sc)
     print(f"{name:14s} fwd {timeit(fwd):6.1f} us  bwd (dQ + dK/dV) {timeit(bwd):6.1f} us", flush=True)

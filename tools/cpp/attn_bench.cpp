@@ -18,10 +18,13 @@ int main() {
   fill<<<1024, 256>>>(q, n, 1); fill<<<1024, 256>>>(k, n, 2); fill<<<1024, 256>>>(v, n, 3);
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   for (int drop = 0; drop < 2; ++drop) {
-    unsigned thr = drop ? 6554 : 0;
-    for (int i = 0; i < 3; ++i) dlt_attn_fwd(q, k, v, o, lse, mask, B, nh, S, hd, 0.125f, 77, thr, 1.f / 0.9f, 1, 0, 0);
+    const long bs = (long)nh * S * hd;
+    const dlt_attn_args a = {.q = q, .k = k, .v = v, .o = o, .lse = lse, .mask = mask, .B = B, .nh = nh, .S = S, .hd = hd,
+                             .scale = 0.125f, .dscale = 1.f / 0.9f, .key = 77, .thr = drop ? 6554u : 0u, .gen_mask = 1,
+                             .stride = {.q = {bs, S * hd, hd}}};
+    for (int i = 0; i < 3; ++i) dlt_attn_fwd(&a, 0);
     hipEventRecord(e0, 0);
-    for (int i = 0; i < 20; ++i) dlt_attn_fwd(q, k, v, o, lse, mask, B, nh, S, hd, 0.125f, 77, thr, 1.f / 0.9f, 1, 0, 0);
+    for (int i = 0; i < 20; ++i) dlt_attn_fwd(&a, 0);
     hipEventRecord(e1, 0); hipEventSynchronize(e1);
     float ms; hipEventElapsedTime(&ms, e0, e1);
     printf("dropout=%d fwd %.1f us\n", drop, ms * 1000 / 20);

@@ -27,13 +27,19 @@ int main(int argc, char** argv) {
   unsigned long long* tim;
   (void)hipMalloc(&tim, (size_t)G * 2 * 6 * 8);
   (void)hipMemcpyToSymbol(HIP_SYMBOL(g_attn_ftim), &tim, sizeof(tim));
-  const unsigned thr = 6554;
-  for (int i = 0; i < 20; ++i) dlt_attn_fwd(q, k, v, o, lse, mask, B, nh, S, hd, 0.125f, 77, thr, 1.f / 0.9f, i == 0, 0, 0);
+  const long bs = (long)nh * S * hd;
+  dlt_attn_args a = {.q = q, .k = k, .v = v, .o = o, .lse = lse, .mask = mask, .B = B, .nh = nh, .S = S, .hd = hd,
+                     .scale = 0.125f, .dscale = 1.f / 0.9f, .key = 77, .thr = 6554, .gen_mask = 1,
+                     .stride = {.q = {bs, S * hd, hd}}};
+  for (int i = 0; i < 20; ++i) {
+    dlt_attn_fwd(&a, 0);
+    a.gen_mask = 0;
+  }
   (void)hipMemset(tim, 0, (size_t)G * 2 * 6 * 8);
   hipEvent_t e0, e1;
   (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
   (void)hipEventRecord(e0, 0);
-  dlt_attn_fwd(q, k, v, o, lse, mask, B, nh, S, hd, 0.125f, 77, thr, 1.f / 0.9f, 0, 0, 0);
+  dlt_attn_fwd(&a, 0);
   (void)hipEventRecord(e1, 0);
   (void)hipDeviceSynchronize();
   float ms = 0;

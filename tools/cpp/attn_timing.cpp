@@ -29,11 +29,14 @@ int main(int argc, char** argv) {
   unsigned long long* tim;
   (void)hipMalloc(&tim, (size_t)G * 2 * 8 * 8);
   (void)hipMemcpyToSymbol(HIP_SYMBOL(g_attn_tim), &tim, sizeof(tim));
-  const unsigned thr = 6554;
-  dlt_attn_fwd(q, k, v, o, lse, mask, B, nh, S, hd, 0.125f, 77, thr, 1.f / 0.9f, 1, 0, 0);
-  for (int i = 0; i < 3; ++i) dlt_attn_bwd(q, k, v, o, dout, lse, mask, delta, dq, dk, dv, B, nh, S, hd, 0.125f, 1.f / 0.9f, 0, 0);
+  const dlt_attn_stride hm = {(long)nh * S * hd, S * hd, hd};
+  const dlt_attn_args a = {.q = q, .k = k, .v = v, .o = o, .lse = lse, .mask = mask, .dout = dout, .delta_ws = delta,
+                           .dq = dq, .dk = dk, .dv = dv, .B = B, .nh = nh, .S = S, .hd = hd, .scale = 0.125f,
+                           .dscale = 1.f / 0.9f, .key = 77, .thr = 6554, .gen_mask = 1, .stride = {.q = hm, .dq = hm}};
+  dlt_attn_fwd(&a, 0);
+  for (int i = 0; i < 3; ++i) dlt_attn_bwd(&a, 0);
   (void)hipMemset(tim, 0, (size_t)G * 2 * 8 * 8);
-  dlt_attn_bwd(q, k, v, o, dout, lse, mask, delta, dq, dk, dv, B, nh, S, hd, 0.125f, 1.f / 0.9f, 0, 0);
+  dlt_attn_bwd(&a, 0);
   (void)hipDeviceSynchronize();
   std::vector<unsigned long long> h((size_t)G * 2 * 8);
   (void)hipMemcpy(h.data(), tim, h.size() * 8, hipMemcpyDeviceToHost);

@@ -200,7 +200,7 @@ static int epi_main(int M, int H, int I, int S) {
     auto unfused = [&]() {
       int rc = run_blas(A, B, C2, M, N, K, st);
       if (rc) return rc;
-      if (which == 0) return dlt_rope_qk_inplace(C2, dc, ds, M, S, H / 64, 64, 0, st);
+      if (which == 0) return dlt_rope_qk_inplace(C2, dc, ds, M, S, H / 64, 0, 64, 0, st);
       return dlt_swiglu_fwd(C2, Sb2, M, I, 0, st);
     };
     CK(hipMemsetAsync(C, 0xff, (size_t)M * N * 2, st));
