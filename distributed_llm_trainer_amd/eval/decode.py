@@ -9,6 +9,11 @@ filtering (``logits < kth`` -> -inf), softmax, ``torch.multinomial``; contexts l
 than ``max_seq_len`` are cropped to the last ``max_seq_len`` tokens (the cache is then
 re-prefilled on the cropped window so RoPE positions match the reference exactly).
 
+With grouped-query attention (``num_kv_heads < num_heads``) the cache holds the
+``num_kv_heads`` K/V heads.  The fused decode step (``ops/csrc/decode.hip``) has a form
+for either layout (:func:`_fused_kind`): the grouped-query one reads every cached K/V
+row once for all query heads of its group and splits the keys over several workgroups.
+
 Weights are read from the engine's provider (bf16 shadows on GPU / FSDP gathered
 units), so generation works the same for single-GPU, DDP and FSDP-trained models.
 """
@@ -137,7 +142,15 @@ class DecodeGraph:
         self.pos = torch.full((1,), pos, dtype=torch.long, device=dev)
         self.kpos = torch.arange(cfg.max_seq_len, device=dev)
         # fused HIP step (ops/csrc/decode.hip): 5 kernels per layer instead of ~25 ATen ops
-        self.fused = _fused_ok(model, B)
+        # (a grouped-query model: the _gqa forms of the two attention-side kernels)
+        self.kind = _fused_kind(model, B)
+        self.fused = self.kind is not None
+        if self.kind == "gqa":
+            # key chunks per K/V head and the partials they merge through: allocated once,
+            # outside the capture
+            self.kv_splits = _gqa_splits(cfg, B)
+            self.attn_ws = (model.engine.ops.dec_attn_gqa_workspace(B, cfg.num_heads, self.kv_splits, dev)
+                            if self.kv_splits > 1 else None)
         if self.fused:
             H, I = cfg.hidden_size, cfg.intermediate_size
             self.h = torch.empty(B, H, dtype=torch.float32, device=dev)
@@ -173,9 +186,15 @@ class DecodeGraph:
         scale = 1.0 / math.sqrt(cfg.head_dim)
         for i in range(cfg.num_layers):
             w = prov.layer(i)
-            ops.dec_norm_qkv(self.h, w.ln1, eng.eps, w.wqkv, cos_t, sin_t, self.pos, self.qb, cache.k[i], cache.v[i],
-                             cfg.num_heads)
-            ops.dec_attn(self.qb, cache.k[i], cache.v[i], self.pos, self.ob, scale)
+            if self.kind == "gqa":
+                ops.dec_norm_qkv_gqa(self.h, w.ln1, eng.eps, w.wqkv, cos_t, sin_t, self.pos, self.qb, cache.k[i],
+                                     cache.v[i], cfg.num_heads, cfg.num_kv_heads)
+                ops.dec_attn_gqa(self.qb, cache.k[i], cache.v[i], self.pos, self.ob, scale, cfg.num_heads,
+                                 splits=self.kv_splits, ws=self.attn_ws)
+            else:
+                ops.dec_norm_qkv(self.h, w.ln1, eng.eps, w.wqkv, cos_t, sin_t, self.pos, self.qb, cache.k[i],
+                                 cache.v[i], cfg.num_heads)
+                ops.dec_attn(self.qb, cache.k[i], cache.v[i], self.pos, self.ob, scale)
             ops.dec_gemv_res(self.ob, w.wo, self.h)
             ops.dec_norm_gu(self.h, w.ln2, eng.eps, w.wgu, self.sb)
             ops.dec_gemv_res(self.sb, w.wdown, self.h)
@@ -235,22 +254,63 @@ class DecodeGraph:
 DEC_LDS_MAX = 160 * 1024  # bytes of LDS per workgroup on gfx950
 
 
-def _fused_ok(model, B: int) -> bool:
-    """The fused HIP decode step applies: HIP ops, a supported batch, head_dim 64, and
-    the LDS its kernels need fits one CU: ``k_dec_attn`` keeps all ``max_seq_len``
-    scores of a (batch, head) in LDS (maxS * 4 + 1056 B: max_seq_len <= ~40.7k), the
-    norm + GEMV kernels one normed bf16 row per batch entry (``dec_lds`` in decode.hip).
-    Beyond that ``DecodeGraph`` captures the ATen step instead.  The fused kernels are
-    multi-head only: a grouped-query model (num_kv_heads < num_heads) takes the ATen step."""
+DEC_KV_SPLITS = (1, 2, 4, 8)
+DEC_KV_SPLIT_LONG = 4096  # caches longer than this take 8 key chunks per K/V head, shorter ones 4
+
+
+def _dec_kv_splits(B: int, nkv: int, maxS: int) -> int:
+    """Key chunks per K/V head (NS) of the grouped-query decode attention, fixed when the
+    step is captured: 4, and 8 for a cache longer than DEC_KV_SPLIT_LONG.  Measured on GPT-2
+    small with 4 and 1 K/V heads at B = 1 and 8 (profiles/gqa_decode.md): over a generation
+    that fills the cache this is the fastest NS, or within 2 % of it, in every cell; B * nkv
+    (1 to 32 there) did not change the choice, and between the two measured cache lengths
+    (1024 and 16384) the threshold is their geometric mean.
+    ``DLT_DECODE_KV_SPLITS=n`` (n in 1, 2, 4, 8) overrides the rule for A/B runs."""
+    env = os.environ.get("DLT_DECODE_KV_SPLITS", "").strip()
+    if env:
+        if not env.isdigit() or int(env) not in DEC_KV_SPLITS:
+            raise ValueError(f"DLT_DECODE_KV_SPLITS={env!r}: expected one of {DEC_KV_SPLITS}")
+        return int(env)
+    return 4 if maxS <= DEC_KV_SPLIT_LONG else 8
+
+
+def _gqa_splits(cfg, B: int) -> int:
+    """NS of a model's fused grouped-query step (:func:`_dec_kv_splits`)."""
+    return _dec_kv_splits(B, cfg.num_kv_heads, cfg.max_seq_len)
+
+
+def _fused_kind(model, B: int) -> Optional[str]:
+    """Which fused HIP decode step applies: ``"mha"`` (``dec_norm_qkv`` / ``dec_attn``),
+    ``"gqa"`` (num_kv_heads < num_heads: ``dec_norm_qkv_gqa`` / ``dec_attn_gqa``) or None,
+    for which ``DecodeGraph`` captures the ATen step instead.  Both kinds need HIP ops, a
+    supported batch, head_dim 64, ``DLT_DECODE_FUSED != 0`` and the LDS of their kernels to
+    fit one CU: the norm + GEMV kernels stage one normed bf16 row per batch entry
+    (``dec_lds`` in decode.hip); ``k_dec_attn`` keeps all ``max_seq_len`` scores of a
+    (batch, head) (maxS * 4 + 1056 B: max_seq_len <= ~40.7k), ``k_dec_attn_gqa`` the scores
+    of a group's query heads over one key chunk at the NS of :func:`_gqa_splits`."""
     ops = model.engine.ops
     cfg = model.config
-    if cfg.num_kv_heads != cfg.num_heads:
-        return False
-    attn_lds = cfg.max_seq_len * 4 + 8 * 4 + 4 * 64 * 4
     norm_lds = B * cfg.hidden_size * 2 + B * 4 * 4 + B * 16 * 4
-    return (hasattr(ops, "dec_norm_qkv") and B in getattr(ops, "DECODE_BATCHES", ())
-            and cfg.head_dim == 64 and attn_lds <= DEC_LDS_MAX and norm_lds <= DEC_LDS_MAX
-            and os.environ.get("DLT_DECODE_FUSED", "1") != "0")
+    if not (hasattr(ops, "dec_norm_qkv") and B in getattr(ops, "DECODE_BATCHES", ())
+            and cfg.head_dim == 64 and norm_lds <= DEC_LDS_MAX
+            and os.environ.get("DLT_DECODE_FUSED", "1") != "0"):
+        return None
+    if cfg.num_kv_heads == cfg.num_heads:
+        attn_lds = cfg.max_seq_len * 4 + 8 * 4 + 4 * 64 * 4
+        return "mha" if attn_lds <= DEC_LDS_MAX else None
+    # the grouped-query kernels are bf16 only: an fp16 / fp32 engine keeps the ATen step it had
+    if not hasattr(ops, "dec_attn_gqa") or getattr(model.engine, "act_dtype", torch.bfloat16) != torch.bfloat16:
+        return None
+    from ..ops.hip import dec_attn_chunk, dec_attn_gqa_lds
+    G = cfg.num_heads // cfg.num_kv_heads
+    lds = dec_attn_gqa_lds(G, dec_attn_chunk(cfg.max_seq_len, _gqa_splits(cfg, B)))
+    return "gqa" if lds <= DEC_LDS_MAX else None
+
+
+def _fused_ok(model, B: int) -> bool:
+    """The multi-head fused kernel set applies (:func:`_fused_kind` is ``"mha"``); False
+    for every grouped-query model, whose fused step is the ``"gqa"`` kind."""
+    return _fused_kind(model, B) == "mha"
 
 
 def _graph_ok(model, device) -> bool:
@@ -279,8 +339,8 @@ def kv_cached_generate(model, input_ids: torch.Tensor, max_new_tokens: int = 100
     logits = forward_cached(model, ctx, cache)
     out = input_ids
     n_dev = min(max_new_tokens - 1, cfg.max_seq_len - cache.len)
-    if (n_dev > 0 and temperature > 0 and _graph_ok(model, input_ids.device) and _fused_ok(model, B)
-            and os.environ.get("DLT_DECODE_DEVICE_LOOP", "1") != "0"):
+    if (n_dev > 0 and temperature > 0 and _graph_ok(model, input_ids.device)
+            and _fused_kind(model, B) is not None and os.environ.get("DLT_DECODE_DEVICE_LOOP", "1") != "0"):
         # first token from the prefill logits (ATen sampling), then one graph replay per
         # token: the fused step samples on the device and feeds itself (no host round trip)
         lg = logits / temperature

@@ -31,7 +31,8 @@ CPU_OPS = _namespace(reference, "reference")
 
 # HIP-only: the fused one-token decode step (eval/decode.py DecodeGraph)
 _HIP_ONLY = ("dec_norm_qkv", "dec_attn", "dec_gemv_res", "dec_norm_gu", "dec_norm_head", "dec_sample", "dec_advance", "dec_sample_workspace",
-             "DECODE_BATCHES")
+             "DECODE_BATCHES", "dec_norm_qkv_gqa", "dec_attn_gqa", "dec_attn_gqa_workspace", "dec_attn_chunk",
+             "dec_attn_gqa_lds", "DEC_ATTN_SPLITS")
 
 
 def hip_ops():

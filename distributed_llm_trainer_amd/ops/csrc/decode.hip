@@ -8,6 +8,9 @@
 //
 //   dec_norm_qkv    : h -> RMSNorm -> QKV GEMV -> RoPE(q, k) -> K/V cache row at `pos`, q
 //   dec_attn        : q . K[0..pos]^T -> softmax -> . V      (one workgroup per (b, head))
+//   dec_attn_gqa    : the same for a grouped-query model: one pass over a K/V head serves the
+//                     G query heads of its group, the keys split over NS workgroups
+//                     (+ dec_attn_combine, a fixed-order merge of the NS partials)
 //   dec_gemv_res    : h += o . Wo^T  /  h += s . Wdown^T      (residual add in fp32)
 //   dec_norm_gu     : h -> RMSNorm -> gate/up GEMV -> SwiGLU -> s
 //   dec_norm_head   : h -> RMSNorm -> lm_head GEMV -> fp32 logits
@@ -172,28 +175,30 @@ __device__ __forceinline__ void rows_dot(const bf16_t* const (&wrow)[NR], int K,
 
 }  // namespace
 
-// grid (3 * nh * 4): workgroup g owns dims {8c..8c+7} u {8c+32..8c+39} (c = g % 4: the 8
-// NeoX RoPE pairs of a quarter head) of head (g / 4) % nh of block g / (4 nh) (0 q, 1 k,
-// 2 v) -- 16 rows, 4 per wave, one load round trip.
+// grid ((nh + 2 nkv) * 4): workgroup g owns dims {8c..8c+7} u {8c+32..8c+39} (c = g % 4:
+// the 8 NeoX RoPE pairs of a quarter head) of head hb = g / 4 of the packed q | k | v row
+// (nh query heads, then nkv key heads, then nkv value heads; weight rows hb * 64 ..) -- 16
+// rows, 4 per wave, one load round trip.  nkv == nh is the multi-head layout [3H, H].
 template <int B>
 __global__ __launch_bounds__(DEC_NT) void k_dec_norm_qkv(const float* __restrict__ h, const void* __restrict__ lnw,
                                                          int wbf16, float eps, const bf16_t* __restrict__ wqkv,
                                                          const float* __restrict__ cosT, const float* __restrict__ sinT,
                                                          const long* __restrict__ posp, bf16_t* __restrict__ qout,
                                                          bf16_t* __restrict__ kc, bf16_t* __restrict__ vc, int H, int nh,
-                                                         int maxS) {
+                                                         int nkv, int maxS) {
   extern __shared__ __attribute__((aligned(16))) char dsm[];
   bf16_t* xs = reinterpret_cast<bf16_t*>(dsm);                       // [B][H]
   float* red = reinterpret_cast<float*>(dsm + (size_t)B * H * 2);     // [B][4]
   float* outv = red + B * 4;                                          // [B][16]
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int quarter = blockIdx.x & 3, hb = blockIdx.x >> 2;
-  const int blk = hb / nh, head = hb % nh;
+  const int blk = hb < nh ? 0 : (hb < nh + nkv ? 1 : 2);
+  const int head = hb - (blk == 0 ? 0 : (blk == 1 ? nh : nh + nkv));
   // local row l (0..15) -> head dim: l < 8 ? 8 quarter + l : 32 + 8 quarter + (l - 8)
   auto dim_of = [&](int l) { return (l < 8 ? 0 : 32) + 8 * quarter + (l & 7); };
   const bf16_t* rows[4];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) rows[r] = wqkv + (size_t)(blk * H + head * 64 + dim_of(wid * 4 + r)) * H;
+  for (int r = 0; r < 4; ++r) rows[r] = wqkv + (size_t)(hb * 64 + dim_of(wid * 4 + r)) * H;
   RowsPre<4, 2> pre;
   rows_pre<4, 2>(rows, H, pre);
   stage_normed<B>(h, H, lnw, wbf16, eps, xs, red);
@@ -223,7 +228,7 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_norm_qkv(const float* __restrict
     if (blk == 0)
       qout[(size_t)b * H + head * 64 + d] = f2bf(y);
     else
-      (blk == 1 ? kc : vc)[(((size_t)b * nh + head) * maxS + pos) * 64 + d] = f2bf(y);
+      (blk == 1 ? kc : vc)[(((size_t)b * nkv + head) * maxS + pos) * 64 + d] = f2bf(y);
   }
 }
 
@@ -304,6 +309,226 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_attn(const bf16_t* __restrict__ 
     const float r = (oacc[tid] + oacc[64 + tid] + oacc[128 + tid] + oacc[192 + tid]) * inv;
     o[(size_t)b * H + head * 64 + tid] = f2bf(r);
   }
+}
+
+// Grouped-query attention of the decode step: the G = nh / nkv query heads of a group read
+// their K/V head ONCE.  grid (B * nkv * GS * NS): workgroup (b, kv head, sub-group, s) owns up
+// to GT query heads (GS = ceil(G / 16) sub-groups: 1 for G <= 16) and the key chunk
+// [s C, min((s + 1) C, pos + 1)), C = dec_attn_chunk(maxS, NS) fixed on the host.
+//   scores : lane = key; the thread loads its K row (8 x 16 bytes, all in flight) and dots it
+//            with every head's q (fp32 in LDS, the same address in every lane: broadcast
+//            reads), sc[g][key] in LDS (GT C 4 bytes, GT the instantiation: the smallest of
+//            1, 2, 3, 4, 6, 8, 12, 16 that holds the heads), the per-head max in registers
+//   softmax: per head over the chunk, fp32, max subtracted
+//   o      : lane = (key slot, 8 dims) as in k_dec_attn; one 16-byte V load feeds the GT
+//            accumulator rows (GT * 8 registers), then key slots are summed by halving
+//            xor-shuffles and the 4 waves through LDS
+// NS == 1 normalises and writes bf16 o; NS > 1 writes the unnormalised partial (o[64], m, l)
+// to ws [B, nh, NS, 66] fp32 for k_dec_attn_combine.  A chunk beyond pos writes m = -inf,
+// l = 0 and reads no cache row.
+constexpr int GQA_WS = 66;    // floats per partial: o[64], m, l
+constexpr int GQA_GMAX = 16;  // query heads per workgroup (128 accumulator registers)
+
+template <int GT>
+__global__ __launch_bounds__(DEC_NT) void k_dec_attn_gqa(const bf16_t* __restrict__ q, const bf16_t* __restrict__ kc,
+                                                         const bf16_t* __restrict__ vc, const long* __restrict__ posp,
+                                                         bf16_t* __restrict__ o, float* __restrict__ ws, int H, int nh,
+                                                         int nkv, int maxS, int NS, int C, float scale) {
+  extern __shared__ __attribute__((aligned(16))) char dsm[];
+  float* red = reinterpret_cast<float*>(dsm);  // [2][4][GT] per-wave max, sum
+  float* oacc = red + 8 * GT;                  // [4][GT][64]
+  float* qs = oacc + 4 * GT * 64;              // [GT][64] q in fp32
+  float* sc = qs + GT * 64;                    // [GT][C] scores -> probabilities
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int G = nh / nkv, GS = (G + GQA_GMAX - 1) / GQA_GMAX;
+  int t = blockIdx.x;
+  const int s = t % NS;
+  t /= NS;
+  const int sub = t % GS;
+  t /= GS;
+  const int kvh = t % nkv, b = t / nkv;
+  const int Gl = min(GT, G - sub * GT);  // GT == GQA_GMAX whenever GS > 1
+  const int h0 = kvh * G + sub * GT;     // first query head of this workgroup
+  DLT_DASSERT(posp[0] >= 0 && posp[0] < maxS);
+  const int len = (int)(posp[0] < maxS ? posp[0] + 1 : maxS);
+  const int lo = s * C, n = min(lo + C, len) - lo;  // n <= C keys of this chunk (<= 0: none)
+  if (n <= 0) {  // (uniform) only with NS > 1: chunk 0 always holds key 0
+    if (tid < Gl) {
+      float* w = ws + (((size_t)b * nh + h0 + tid) * NS + s) * GQA_WS;
+      w[64] = -INFINITY;
+      w[65] = 0.f;
+    }
+    return;
+  }
+  const bf16_t* K = kc + (((size_t)b * nkv + kvh) * maxS + lo) * 64;
+  const bf16_t* V = vc + (((size_t)b * nkv + kvh) * maxS + lo) * 64;
+  // The thread's first K row and the group's q are requested together (one round trip); every
+  // later trip requests its successor's row before its own dot products.  Rows are clamped to
+  // n - 1 (a row that exists) so that no load sits behind a branch; a clamped row is not used.
+  u16x8 kv[8];
+  {
+    const int j0 = min(tid, n - 1);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) kv[c] = *reinterpret_cast<const u16x8*>(K + (size_t)j0 * 64 + c * 8);
+  }
+  // q in fp32; a padded head (g >= Gl) repeats the last one, so the loops over g have no branch
+  // (a branch splits the loads of an unrolled trip into one exposed round trip each)
+  if (tid < GT * 8) {  // one 16-byte chunk of q per thread
+    const u16x8 w = *reinterpret_cast<const u16x8*>(q + (size_t)b * H + (size_t)(h0 + min(tid >> 3, Gl - 1)) * 64 +
+                                                    (tid & 7) * 8);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) qs[tid * 8 + e] = bf2f(w.v[e]);
+  }
+  __syncthreads();
+  float mx[GT];
+#pragma unroll
+  for (int g = 0; g < GT; ++g) mx[g] = -INFINITY;
+  for (int j = tid; j < n; j += DEC_NT) {
+    float kf[64];
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) kf[c * 8 + e] = bf2f(kv[c].v[e]);
+    {
+      const int jn = min(j + DEC_NT, n - 1);
+#pragma unroll
+      for (int c = 0; c < 8; ++c) kv[c] = *reinterpret_cast<const u16x8*>(K + (size_t)jn * 64 + c * 8);
+    }
+    // dims outer, heads inner: GT independent fma chains, and the q reads (the same address in
+    // every lane: broadcast, no bank conflict) of the next dims overlap them
+    float a[GT];
+#pragma unroll
+    for (int g = 0; g < GT; ++g) a[g] = 0.f;
+#pragma unroll
+    for (int c = 0; c < 16; ++c)
+#pragma unroll
+      for (int g = 0; g < GT; ++g) {
+        const float4 qv = *reinterpret_cast<const float4*>(qs + g * 64 + c * 4);
+        a[g] = fmaf(qv.x, kf[c * 4], a[g]);
+        a[g] = fmaf(qv.y, kf[c * 4 + 1], a[g]);
+        a[g] = fmaf(qv.z, kf[c * 4 + 2], a[g]);
+        a[g] = fmaf(qv.w, kf[c * 4 + 3], a[g]);
+      }
+#pragma unroll
+    for (int g = 0; g < GT; ++g) {
+      a[g] *= scale;
+      sc[g * C + j] = a[g];
+      mx[g] = fmaxf(mx[g], a[g]);
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < GT; ++g) {
+#pragma unroll
+    for (int o2 = 32; o2 > 0; o2 >>= 1) mx[g] = fmaxf(mx[g], __shfl_xor(mx[g], o2, 64));
+    if (lane == 0) red[wid * GT + g] = mx[g];
+  }
+  __syncthreads();
+  float sum[GT];
+#pragma unroll
+  for (int g = 0; g < GT; ++g) {
+    mx[g] = fmaxf(fmaxf(red[g], red[GT + g]), fmaxf(red[2 * GT + g], red[3 * GT + g]));
+    sum[g] = 0.f;
+  }
+  for (int j = tid; j < n; j += DEC_NT) {  // the thread's own scores: no barrier since the writes
+#pragma unroll
+    for (int g = 0; g < GT; ++g) {
+      const float p = __expf(sc[g * C + j] - mx[g]);
+      sc[g * C + j] = p;
+      sum[g] += p;
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < GT; ++g) {
+    sum[g] = wave_sum64(sum[g]);
+    if (lane == 0) red[(4 + wid) * GT + g] = sum[g];
+  }
+  __syncthreads();  // every probability and every wave's sum written
+  // o[g][d] = sum_j p_gj v_j[d]: lane (js, dc) = (tid / 8, tid % 8) loads dims 8dc..8dc+7 of
+  // keys j = js, js + 32, ... once and uses them for every head of the group
+  const int dc = tid & 7, js = tid >> 3;
+  float acc[GT * 8];  // [g][e]
+#pragma unroll
+  for (int i = 0; i < GT * 8; ++i) acc[i] = 0.f;
+  // 4 keys per trip, their loads issued together; a key past the chunk re-reads key n - 1
+  // (a row that exists) with weight 0, so the trip has no branch either
+  for (int j0 = js; j0 < n; j0 += 4 * (DEC_NT / 8)) {
+    u16x8 vv[4];
+    int jc[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      jc[u] = min(j0 + u * (DEC_NT / 8), n - 1);
+      vv[u] = *reinterpret_cast<const u16x8*>(V + (size_t)jc[u] * 64 + dc * 8);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const float ok = j0 + u * (DEC_NT / 8) < n ? 1.f : 0.f;
+      float vf[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) vf[e] = bf2f(vv[u].v[e]);
+#pragma unroll
+      for (int g = 0; g < GT; ++g) {
+        const float p = sc[g * C + jc[u]] * ok;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[g * 8 + e] = fmaf(p, vf[e], acc[g * 8 + e]);
+      }
+    }
+  }
+  // Sum over the wave's 8 key slots (lane bits 5, 4, 3) by halving: at each step a lane keeps
+  // one half of its values, hands the other half to its partner and adds what it receives
+  // (7/8 GT * 8 shuffles instead of 3 GT * 8).  Lane (k, dc), k = (lane >> 3) & 7, ends with
+  // the GT sums of the flat indices k GT .. k GT + GT - 1 of [g][e].
+#pragma unroll
+  for (int st = 0; st < 3; ++st) {
+    const int m = 32 >> st, half = (GT * 8) >> (st + 1);
+    const bool up = (lane & m) != 0;
+#pragma unroll
+    for (int i = 0; i < half; ++i) {
+      const float send = up ? acc[i] : acc[i + half];
+      const float keep = up ? acc[i + half] : acc[i];
+      acc[i] = keep + __shfl_xor(send, m, 64);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < GT; ++i) {
+    const int v = ((lane >> 3) & 7) * GT + i;  // = g * 8 + e
+    oacc[(wid * GT + (v >> 3)) * 64 + dc * 8 + (v & 7)] = acc[i];
+  }
+  __syncthreads();
+  for (int i = tid; i < Gl * 64; i += DEC_NT) {
+    const int g = i >> 6;
+    const float r = oacc[i] + oacc[GT * 64 + i] + oacc[2 * GT * 64 + i] + oacc[3 * GT * 64 + i];
+    if (NS == 1) {
+      const float inv = 1.f / (red[4 * GT + g] + red[5 * GT + g] + red[6 * GT + g] + red[7 * GT + g]);
+      o[(size_t)b * H + h0 * 64 + i] = f2bf(r * inv);
+    } else {
+      ws[(((size_t)b * nh + h0 + g) * NS + s) * GQA_WS + (i & 63)] = r;
+    }
+  }
+  if (NS > 1 && tid < Gl) {
+    float* w = ws + (((size_t)b * nh + h0 + tid) * NS + s) * GQA_WS;
+    w[64] = fmaxf(fmaxf(red[tid], red[GT + tid]), fmaxf(red[2 * GT + tid], red[3 * GT + tid]));
+    w[65] = red[4 * GT + tid] + red[5 * GT + tid] + red[6 * GT + tid] + red[7 * GT + tid];
+  }
+}
+
+// grid (B * nh), one wave: lane = dim.  The NS partials of a (b, query head) are merged in
+// the fixed order s = 0 .. NS - 1, each rescaled by exp(m_s - M); an empty chunk (l == 0) is
+// skipped without reading its o.  No atomics and no arrival order: the same bits every run.
+__global__ __launch_bounds__(64) void k_dec_attn_combine(const float* __restrict__ ws, bf16_t* __restrict__ o,
+                                                         int NS) {
+  const float* w = ws + (size_t)blockIdx.x * NS * GQA_WS;
+  float M = -INFINITY;
+  for (int s = 0; s < NS; ++s) M = fmaxf(M, w[s * GQA_WS + 64]);
+  float L = 0.f, r = 0.f;
+  for (int s = 0; s < NS; ++s) {
+    const float l = w[s * GQA_WS + 65];
+    if (l > 0.f) {
+      const float f = __expf(w[s * GQA_WS + 64] - M);
+      L = fmaf(l, f, L);
+      r = fmaf(w[s * GQA_WS + threadIdx.x], f, r);
+    }
+  }
+  o[(size_t)blockIdx.x * 64 + threadIdx.x] = f2bf(r / L);
 }
 
 // h[b][r] += bf16(x[b] . W[r]) for the 16 rows of this workgroup (4 per wave, R rows total).
@@ -776,15 +1001,65 @@ __global__ void k_dec_advance(long* pos) { pos[0] += 1; }
 
 static size_t dec_lds(int B, int K) { return (size_t)B * K * 2 + (size_t)B * 4 * 4 + (size_t)B * 16 * 4; }
 
+DLT_API int dlt_dec_norm_qkv_gqa(const float* h, const void* lnw, int wbf16, float eps, const bf16_t* wqkv,
+                                 const float* cosT, const float* sinT, const long* pos, bf16_t* qout, bf16_t* kc,
+                                 bf16_t* vc, int B, int H, int nh, int nkv, int maxS, hipStream_t st);
+
 DLT_API int dlt_dec_norm_qkv(const float* h, const void* lnw, int wbf16, float eps, const bf16_t* wqkv,
                              const float* cosT, const float* sinT, const long* pos, bf16_t* qout, bf16_t* kc,
                              bf16_t* vc, int B, int H, int nh, int maxS, hipStream_t st) {
-  if (H != nh * 64 || H % 8 || dec_lds(B, H) > 160 * 1024) return -1;
-#define L(BB)                                                                                                      \
-  k_dec_norm_qkv<BB><<<3 * nh * 4, DEC_NT, dec_lds(BB, H), st>>>(h, lnw, wbf16, eps, wqkv, cosT, sinT, pos, qout, kc, vc, \
-                                                             H, nh, maxS)
+  return dlt_dec_norm_qkv_gqa(h, lnw, wbf16, eps, wqkv, cosT, sinT, pos, qout, kc, vc, B, H, nh, nh, maxS, st);
+}
+
+// Grouped-query form: wqkv [H + 2 nkv 64, H] (q | k | v), caches [B, nkv, maxS, 64].
+DLT_API int dlt_dec_norm_qkv_gqa(const float* h, const void* lnw, int wbf16, float eps, const bf16_t* wqkv,
+                                 const float* cosT, const float* sinT, const long* pos, bf16_t* qout, bf16_t* kc,
+                                 bf16_t* vc, int B, int H, int nh, int nkv, int maxS, hipStream_t st) {
+  if (H != nh * 64 || H % 8 || nkv < 1 || nh % nkv || maxS < 1 || dec_lds(B, H) > 160 * 1024) return -1;
+#define L(BB)                                                                                                     \
+  k_dec_norm_qkv<BB><<<(nh + 2 * nkv) * 4, DEC_NT, dec_lds(BB, H), st>>>(h, lnw, wbf16, eps, wqkv, cosT, sinT, pos, \
+                                                                        qout, kc, vc, H, nh, nkv, maxS)
   DEC_DISPATCH(B, L)
 #undef L
+  DLT_CHECK_LAUNCH();
+}
+
+// Keys per workgroup of the split grouped-query attention; eval/decode.py and the tests take
+// the same value from ops/hip.py dec_attn_chunk.
+static int dec_attn_chunk(int maxS, int NS) { return (maxS + NS - 1) / NS; }
+
+// q, o [B, nh * 64] bf16, caches [B, nkv, maxS, 64]; NS in {1, 2, 4, 8} key chunks per K/V
+// head; ws: fp32 [B, nh, NS, 66] (NS > 1).  Two launches on `st` for NS > 1, one otherwise.
+DLT_API int dlt_dec_attn_gqa(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const long* pos, bf16_t* o,
+                             float* ws, int B, int H, int nh, int nkv, int maxS, int NS, float scale,
+                             hipStream_t st) {
+  if (B < 1 || H != nh * 64 || nkv < 1 || nh % nkv || maxS < 1) return -1;
+  if ((NS != 1 && NS != 2 && NS != 4 && NS != 8) || (NS > 1 && !ws)) return -1;
+  const int G = nh / nkv, Gw = G < GQA_GMAX ? G : GQA_GMAX, GS = (G + GQA_GMAX - 1) / GQA_GMAX;
+  const int C = dec_attn_chunk(maxS, NS);
+  const int gts[8] = {1, 2, 3, 4, 6, 8, 12, 16};
+  int GT = 16;
+  for (int i = 7; i >= 0; --i)
+    if (gts[i] >= Gw) GT = gts[i];
+  const size_t lds = (size_t)GT * (C + 8 + 4 * 64 + 64) * 4;  // scores, max / sum, o of 4 waves, q
+  if (lds > 160 * 1024) return -1;
+  const int grid = B * nkv * GS * NS;
+#define L(GG)                                                                                                   \
+  case GG:                                                                                                      \
+    k_dec_attn_gqa<GG><<<grid, DEC_NT, lds, st>>>(q, kc, vc, pos, o, ws, H, nh, nkv, maxS, NS, C, scale); \
+    break
+  switch (GT) {
+    L(1);
+    L(2);
+    L(3);
+    L(4);
+    L(6);
+    L(8);
+    L(12);
+    L(16);
+  }
+#undef L
+  if (NS > 1) k_dec_attn_combine<<<B * nh, 64, 0, st>>>(ws, o, NS);
   DLT_CHECK_LAUNCH();
 }
 

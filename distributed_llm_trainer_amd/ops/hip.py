@@ -86,6 +86,10 @@ _SIGS = {
     "dlt_dec_norm_qkv": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                          c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "dlt_dec_attn": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p],
+    "dlt_dec_norm_qkv_gqa": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "dlt_dec_attn_gqa": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                         c_int, c_float, c_void_p],
     "dlt_dec_gemv_res": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "dlt_dec_norm_gu": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "dlt_dec_norm_head": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
@@ -160,6 +164,78 @@ def dec_attn(q, kc, vc, pos, o_out, scale):
     _req(o_out, torch.bfloat16, "dec.o", B * H)
     _chk(lib().dlt_dec_attn(_p(q), _p(kc), _p(vc), _p(pos), _p(o_out), B, H, nh, maxS, float(scale), _stream()),
          "dec_attn")
+
+
+def dec_norm_qkv_gqa(h, ln, eps, wqkv, cos, sin, pos, q_out, kc, vc, nh, nkv):
+    """:func:`dec_norm_qkv` for a grouped-query model: wqkv [H + 2 * nkv * 64, H] laid out
+    q | k | v, caches [B, nkv, maxS, 64]; RoPE on the nh query and nkv key heads."""
+    B, H = h.shape
+    nkv = _req_nkv(nh, nkv, "dec_norm_qkv_gqa")
+    _req(h, torch.float32, "dec.h", B * H)
+    w, wbf16 = _norm_weight(ln, H, "dec.ln1")
+    _dec_w(wqkv, "dec.wqkv")
+    _req(q_out, torch.bfloat16, "dec.q", B * H)
+    _req(pos, torch.int64, "dec.pos", 1)
+    _req(kc, torch.bfloat16, "dec.k_cache")
+    _req(vc, torch.bfloat16, "dec.v_cache")
+    maxS = kc.shape[2] if kc.dim() == 4 else -1
+    if (H != nh * 64 or kc.shape != (B, nkv, maxS, 64) or vc.shape != kc.shape
+            or wqkv.shape != (H + 2 * nkv * 64, H) or cos.shape[0] < maxS or sin.shape[0] < maxS):
+        raise ValueError("dec_norm_qkv_gqa: shape mismatch")
+    _chk(lib().dlt_dec_norm_qkv_gqa(_p(h), _p(w), wbf16, float(eps), _p(wqkv), _p(cos), _p(sin), _p(pos), _p(q_out),
+                                    _p(kc), _p(vc), B, H, nh, nkv, maxS, _stream()), "dec_norm_qkv_gqa")
+
+
+DEC_ATTN_SPLITS = (1, 2, 4, 8)  # key chunks per K/V head of dec_attn_gqa
+DEC_ATTN_GQA_HEADS = 16         # query heads per workgroup (GQA_GMAX in decode.hip)
+DEC_ATTN_WS = 66                # fp32 per partial: o[64], m, l
+
+
+def dec_attn_chunk(maxS: int, splits: int) -> int:
+    """Keys per workgroup of :func:`dec_attn_gqa`: chunk s is [s * C, min((s + 1) * C, pos + 1))."""
+    if splits not in DEC_ATTN_SPLITS or maxS < 1:
+        raise ValueError(f"dec_attn_chunk: splits must be one of {DEC_ATTN_SPLITS} and maxS positive")
+    return -(-maxS // splits)
+
+
+def dec_attn_gqa_lds(G: int, C: int) -> int:
+    """Bytes of LDS of a ``k_dec_attn_gqa`` workgroup: the scores of its (at most 16) query
+    heads over its C keys, and the reduction, output and q areas (decode.hip dlt_dec_attn_gqa)."""
+    gw = min(G, DEC_ATTN_GQA_HEADS)
+    gt = next(t for t in (1, 2, 3, 4, 6, 8, 12, 16) if t >= gw)
+    return gt * (C + 8 + 4 * 64 + 64) * 4
+
+
+def dec_attn_gqa_workspace(B: int, nh: int, splits: int, device) -> torch.Tensor:
+    """The fp32 partials [B, nh, splits, 66] of :func:`dec_attn_gqa` with ``splits`` > 1."""
+    return torch.empty(B * nh * splits * DEC_ATTN_WS, dtype=torch.float32, device=device)
+
+
+def dec_attn_gqa(q, kc, vc, pos, o_out, scale, nh, splits=1, ws=None):
+    """Decode attention of a grouped-query model: q, o_out [B, nh * 64] bf16, caches
+    [B, nkv, maxS, 64]; every K/V row is read once for the nh / nkv query heads of its group.
+    ``splits`` > 1 divides the keys over that many workgroups per K/V head (chunks of
+    :func:`dec_attn_chunk`) and merges their partials, in order, through ``ws``
+    (:func:`dec_attn_gqa_workspace`)."""
+    if kc.dim() != 4 or kc.shape[3] != 64 or vc.shape != kc.shape:
+        raise ValueError("dec_attn_gqa: caches must be [B, nkv, maxS, 64]")
+    B, nkv, maxS, _ = kc.shape
+    if isinstance(nh, bool) or not isinstance(nh, int) or nh < 1 or nh % nkv:
+        raise ValueError(f"dec_attn_gqa: nkv ({nkv}) must divide nh ({nh})")
+    if splits not in DEC_ATTN_SPLITS:
+        raise ValueError(f"dec_attn_gqa: splits must be one of {DEC_ATTN_SPLITS}")
+    H = nh * 64
+    _req(q, torch.bfloat16, "dec.q", B * H)
+    _req(o_out, torch.bfloat16, "dec.o", B * H)
+    _req(kc, torch.bfloat16, "dec.k_cache")
+    _req(vc, torch.bfloat16, "dec.v_cache")
+    _req(pos, torch.int64, "dec.pos", 1)
+    if splits > 1:
+        if ws is None:
+            raise ValueError("dec_attn_gqa: splits > 1 needs a workspace (dec_attn_gqa_workspace)")
+        _req(ws, torch.float32, "dec.attn_ws", B * nh * splits * DEC_ATTN_WS)
+    _chk(lib().dlt_dec_attn_gqa(_p(q), _p(kc), _p(vc), _p(pos), _p(o_out), _p(ws if splits > 1 else None), B, H, nh,
+                                nkv, maxS, splits, float(scale), _stream()), "dec_attn_gqa")
 
 
 def dec_gemv_res(x, w, h):

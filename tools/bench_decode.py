@@ -1,5 +1,10 @@
 """Decode throughput of GPT.generate (KV cache) with and without the HIP-graph step.
-usage: python tools/bench_decode.py [model_size] [batch] [new_tokens]"""
+usage: python tools/bench_decode.py [model_size] [batch] [new_tokens] [num_kv_heads] [max_seq_len]
+
+``num_kv_heads`` (default: the preset's, multi-head) makes the model grouped-query; the
+run then also prints which fused step it took (``_fused_kind``) and the key splits (NS,
+``DLT_DECODE_KV_SPLITS``) of its attention, and times the captured step once more at the
+last cache position (every key read).  ``max_seq_len`` overrides the preset's cache length."""
 import os
 import sys
 import time
@@ -12,9 +17,24 @@ from distributed_llm_trainer_amd.models import GPT, GPTConfig  # noqa: E402
 size = sys.argv[1] if len(sys.argv) > 1 else "small"
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 N = int(sys.argv[3]) if len(sys.argv) > 3 else 200
+NKV = int(sys.argv[4]) if len(sys.argv) > 4 else None
+MAXS = int(sys.argv[5]) if len(sys.argv) > 5 else None
 torch.manual_seed(0)
-m = GPT(GPTConfig.from_preset(size)).to("cuda")
+cfg = GPTConfig.from_preset(size)
+if NKV is not None:
+    cfg.num_kv_heads = NKV
+if MAXS is not None:
+    cfg.max_seq_len = MAXS
+if NKV is not None or MAXS is not None:
+    cfg.__post_init__()
+m = GPT(cfg).to("cuda")
 m.enable_engine()
+from distributed_llm_trainer_amd.eval.decode import DecodeGraph, KVCache, _fused_kind, _gqa_splits, forward_cached  # noqa: E402
+if NKV is not None:
+    kind = _fused_kind(m, B)
+    ns = _gqa_splits(m.config, B) if kind == "gqa" else "-"
+    print(f"{size} B={B} nh={m.config.num_heads} nkv={m.config.num_kv_heads} max_seq_len={m.config.max_seq_len}: "
+          f"fused kind {kind}, NS {ns}", flush=True)
 ids = torch.randint(0, 50257, (B, 32), device="cuda")
 for mode, graph, loop in (("eager", "0", "0"), ("graph, host sampling", "1", "0"), ("graph, device loop", "1", "1")):
     os.environ["DLT_DECODE_GRAPH"] = graph
@@ -29,7 +49,6 @@ for mode, graph, loop in (("eager", "0", "0"), ("graph, host sampling", "1", "0"
           flush=True)
 
 # replay-only cost of the captured step (no sampling / Python in the loop)
-from distributed_llm_trainer_amd.eval.decode import DecodeGraph, KVCache, forward_cached  # noqa: E402
 with torch.no_grad():
     c = KVCache(m.config, B, "cuda", m.engine.act_dtype)
     forward_cached(m, ids, c)
@@ -41,6 +60,22 @@ with torch.no_grad():
         g.graph.replay()
     torch.cuda.synchronize()
     print(f"graph replay only: {(time.perf_counter() - t) / 100 * 1e3:.3f} ms/step")
+    if NKV is not None:
+        # three windows of 300 replays each, at the prompt's position and over a full cache
+        # (the rows beyond the prompt are zero): the spread between windows is the noise
+        for name, p in (("prompt position", c.len), ("full cache", m.config.max_seq_len - 1)):
+            g.pos.fill_(p)
+            ws = []
+            for _ in range(4):  # the first window warms up
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                for _ in range(300):
+                    g.graph.replay()
+                torch.cuda.synchronize()
+                ws.append((time.perf_counter() - t) / 300 * 1e3)
+            print(f"graph replay only, {name}: min {min(ws[1:]):.4f} ms/step "
+                  f"(windows {' '.join(f'{w:.4f}' for w in ws[1:])})", flush=True)
+        g.pos.fill_(c.len)
     lg = g(nxt)
     torch.cuda.synchronize()
     t = time.perf_counter()
