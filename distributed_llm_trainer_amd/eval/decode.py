@@ -49,6 +49,14 @@ def _rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Tensor
     return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1)
 
 
+def _qk_norm(q: torch.Tensor, k: torch.Tensor, w, eps: float):
+    """QK-norm (cfg.qk_norm: ``w.qn`` / ``w.kn`` are set): RMSNorm over head_dim of every
+    query / key head, before RoPE -- the cache then holds normalised, rotated keys."""
+    if getattr(w, "qn", None) is None:
+        return q, k
+    return _rms(q, w.qn, eps), _rms(k, w.kn, eps)
+
+
 def _split_qkv(qkv: torch.Tensor, cfg):
     """Packed projection [B, T, H + 2*KV] fp32 -> q [B, T, nh, hd], k, v [B, T, nkv, hd]."""
     B, T, _ = qkv.shape
@@ -88,6 +96,7 @@ def forward_cached(model, ids: torch.Tensor, cache: KVCache) -> torch.Tensor:
         w = prov.layer(i)
         n1 = _rms(h, w.ln1, eng.eps).to(dt)
         q, k, v = _split_qkv(torch.matmul(n1, w.wqkv.t()).float(), cfg)
+        q, k = _qk_norm(q, k, w, eng.eps)
         q = _rope(q, cos, sin)
         k = _rope(k, cos, sin)
         cache.k[i][:, :, p0:p0 + T] = k.transpose(1, 2).to(dt)
@@ -225,6 +234,7 @@ class DecodeGraph:
             w = prov.layer(i)
             n1 = _rms(h, w.ln1, eng.eps).to(dt)
             q, k, v = _split_qkv(torch.matmul(n1, w.wqkv.t()).float(), cfg)
+            q, k = _qk_norm(q, k, w, eng.eps)
             q = _rope(q, cos, sin)
             k = _rope(k, cos, sin)
             cache.k[i].index_copy_(2, self.pos, k.transpose(1, 2).to(dt))
@@ -282,7 +292,8 @@ def _gqa_splits(cfg, B: int) -> int:
 def _fused_kind(model, B: int) -> Optional[str]:
     """Which fused HIP decode step applies: ``"mha"`` (``dec_norm_qkv`` / ``dec_attn``),
     ``"gqa"`` (num_kv_heads < num_heads: ``dec_norm_qkv_gqa`` / ``dec_attn_gqa``) or None,
-    for which ``DecodeGraph`` captures the ATen step instead.  Both kinds need HIP ops, a
+    for which ``DecodeGraph`` captures the ATen step instead (always for a QK-norm model: the
+    fused norm + QKV kernels do not apply q_norm / k_norm).  Both kinds need HIP ops, a
     supported batch, head_dim 64, ``DLT_DECODE_FUSED != 0`` and the LDS of their kernels to
     fit one CU: the norm + GEMV kernels stage one normed bf16 row per batch entry
     (``dec_lds`` in decode.hip); ``k_dec_attn`` keeps all ``max_seq_len`` scores of a
@@ -290,6 +301,8 @@ def _fused_kind(model, B: int) -> Optional[str]:
     of a group's query heads over one key chunk at the NS of :func:`_gqa_splits`."""
     ops = model.engine.ops
     cfg = model.config
+    if getattr(cfg, "qk_norm", False):  # no fused norm + QKV kernel applies q_norm / k_norm: the ATen step does
+        return None
     norm_lds = B * cfg.hidden_size * 2 + B * 4 * 4 + B * 16 * 4
     if not (hasattr(ops, "dec_norm_qkv") and B in getattr(ops, "DECODE_BATCHES", ())
             and cfg.head_dim == 64 and norm_lds <= DEC_LDS_MAX

@@ -52,6 +52,10 @@ class GPTConfig:
     # 1 = multi-query).  Query head h attends with kv head h // (num_heads // num_kv_heads).
     num_kv_heads: Optional[int] = None
 
+    # QK-norm (Qwen3 form): an RMSNorm over head_dim, with one [head_dim] weight per layer for
+    # the query heads (q_norm) and one for the key heads (k_norm), applied before RoPE.
+    qk_norm: bool = False
+
     def __post_init__(self) -> None:
         if self.intermediate_size is None:
             self.intermediate_size = 4 * self.hidden_size
@@ -63,6 +67,7 @@ class GPTConfig:
         if self.num_kv_heads < 1 or self.num_heads % self.num_kv_heads != 0:
             raise ValueError(
                 f"num_kv_heads ({self.num_kv_heads}) must divide num_heads ({self.num_heads})")
+        self.qk_norm = bool(self.qk_norm)
 
     # ------------------------------------------------------------------ presets
     @classmethod
@@ -112,6 +117,8 @@ class GPTConfig:
         """True trainable parameter count (tied embedding counted once)."""
         h, i = self.hidden_size, self.intermediate_size
         per_layer = 2 * h * h + 2 * self.kv_size * h + 3 * h * i + 2 * h
+        if self.qk_norm:
+            per_layer += 2 * self.head_dim  # q_norm, k_norm
         return self.vocab_size * h + self.num_layers * per_layer + h
 
     def num_parameters_legacy(self) -> int:
@@ -139,20 +146,26 @@ class GPTConfig:
         d = asdict(self)
         if self.num_kv_heads == self.num_heads:  # MHA configs stay what they were
             del d["num_kv_heads"]
+        if not self.qk_norm:  # ... and so do configs without QK-norm
+            del d["qk_norm"]
         return d
 
-    # Pickled configs (checkpoints) follow to_dict(): an MHA config carries no num_kv_heads,
-    # so its pickle is what it was before the field existed and older pickles load.
+    # Pickled configs (checkpoints) follow to_dict(): an MHA config carries no num_kv_heads and
+    # one without QK-norm no qk_norm, so their pickles are what they were before the fields
+    # existed and older pickles load.
     def __getstate__(self) -> Dict[str, Any]:
         state = dict(self.__dict__)
         if state.get("num_kv_heads") == state.get("num_heads"):
             state.pop("num_kv_heads", None)
+        if not state.get("qk_norm"):
+            state.pop("qk_norm", None)
         return state
 
     def __setstate__(self, state: Dict[str, Any]) -> None:
         self.__dict__.update(state)
         if self.__dict__.get("num_kv_heads") is None:
             self.num_kv_heads = self.num_heads
+        self.qk_norm = bool(self.__dict__.get("qk_norm", False))
 
     @classmethod
     def from_dict(cls, d: Dict[str, Any]) -> "GPTConfig":

@@ -72,6 +72,8 @@ class LayerWeights:
     wdown: torch.Tensor  # [H, I]
     ln1: torch.Tensor    # [H]
     ln2: torch.Tensor    # [H]
+    qn: Any = None       # QK-norm (cfg.qk_norm): q_norm / k_norm weights [head_dim], else None
+    kn: Any = None
 
 
 @dataclass
@@ -82,6 +84,8 @@ class LayerGrads:
     wdown: torch.Tensor
     ln1: torch.Tensor
     ln2: torch.Tensor
+    qn: Any = None       # fp32 [head_dim] gradients of q_norm / k_norm (cfg.qk_norm)
+    kn: Any = None
 
 
 @dataclass
@@ -135,6 +139,7 @@ class _LayerCache:
     rstd1: Any = None
     n1: Any = None
     q: Any = None      # packed path: the roped [M, 3H] qkv (k, v = None)
+    raw: Any = None    # QK-norm: the pre-norm q|k columns [M, H + KV], kept / recomputed with q
     k: Any = None
     v: Any = None
     o: Any = None
@@ -257,6 +262,16 @@ class GPTEngine:
             if not self.packed_qkv:
                 raise NotImplementedError("grouped-query attention on the GPU runs on the packed QKV layout "
                                           "(DLT_PACKED_QKV=0 is not supported with num_kv_heads < num_heads)")
+        # QK-norm (cfg.qk_norm): the QKV GEMM is followed by qknorm_rope_inplace (norm + RoPE
+        # in place, pre-norm q|k copied to ``raw``) instead of the RoPE forms, and qknorm_bwd
+        # runs between the attention backward and the QKV data-gradient GEMM
+        self.qk_norm = bool(cfg.qk_norm)
+        if self.qk_norm and getattr(ops, "backend", "") == "hip":
+            from ..ops import check_qk_norm
+            check_qk_norm("cuda", cfg.head_dim, act_dtype)
+            if not self.packed_qkv:
+                raise NotImplementedError("QK-norm on the GPU runs on the packed QKV layout "
+                                          "(DLT_PACKED_QKV=0 is not supported with qk_norm)")
         # last layers of the deferred-wgrad backward whose weight gradients run on the
         # current stream instead of the side stream (see _backward_gen)
         self.main_wgrad_layers = int(os.environ.get("DLT_MAIN_WGRAD_LAYERS", "1"))
@@ -466,12 +481,30 @@ class GPTEngine:
         cfg = self.cfg
         per_layer_chains = cfg.num_layers * 2 * (2 if self.act_dtype == torch.bfloat16 else 4)
         qkv = M * (cfg.hidden_size + 2 * cfg.kv_size) * per_layer_chains
+        if self.qk_norm:  # the pre-norm q|k copy is kept (or recomputed) with the QKV output
+            qkv += M * (cfg.hidden_size + cfg.kv_size) * per_layer_chains
         gu = M * 2 * cfg.intermediate_size * per_layer_chains
         rest = M * (2 * cfg.hidden_size + cfg.intermediate_size) * per_layer_chains
         keep_qkv = qkv <= self.ac_budget
         keep_gu = keep_qkv and qkv + gu <= self.ac_budget
         keep_rest = keep_gu and qkv + gu + rest <= self.ac_budget and os.environ.get("DLT_AC_KEEP_REST", "1") != "0"
         return keep_qkv, keep_gu, keep_rest
+
+    def _qknorm_fwd(self, qkv, w, B: int, S: int, cos, sin):
+        """QK-norm + RoPE of the QKV GEMM output in place; returns ``raw``, the pre-norm q|k
+        columns the backward needs (the in-place write destroys them)."""
+        cfg = self.cfg
+        raw = torch.empty(B * S, cfg.hidden_size + cfg.kv_size, dtype=qkv.dtype, device=qkv.device)
+        self.ops.qknorm_rope_inplace(qkv, B, S, cfg.num_heads, cos, sin, w.qn, w.kn, self.eps, raw, **self.gqa_kw)
+        return raw
+
+    @staticmethod
+    def _split_tables(raw, cos, sin):
+        """RoPE tables of the head split of the split q/k/v layout: with QK-norm the rotation
+        is already applied, so the split rotates by the identity (cos 1, sin 0: exact)."""
+        if raw is None:
+            return cos, sin
+        return torch.ones_like(cos), torch.zeros_like(sin)
 
     def _layer_forward(self, st: _StepState, i: int, r, d, key_d: int, p_d: float,
                        save: bool):
@@ -491,7 +524,7 @@ class GPTEngine:
         mask, mask_ev = self._attn_mask_async(B, S, pa, k_attn, dv)
         x, n1, rstd1 = ops.add_dropout_rmsnorm_fwd(r, d, w.ln1, self.eps, p_d, key_d, self.act_dtype,
                                                    y_out=sb("n1", H))
-        fused_rope = self.packed_qkv and hasattr(gm, "linear_rope") and not self.gqa
+        fused_rope = self.packed_qkv and hasattr(gm, "linear_rope") and not self.gqa and not self.qk_norm
         if fused_rope:  # QKV GEMM with RoPE on q/k in its epilogue (when that races faster)
             qkv = gm.linear_rope(n1, w.wqkv, B, S, cfg.num_heads, cos, sin, ops)
         else:
@@ -514,14 +547,17 @@ class GPTEngine:
             if st.recompute:
                 keep = keep and mask_bytes <= M * H * 4
             kw["store_mask"] = keep
+        raw = None
+        if self.qk_norm:
+            raw = self._qknorm_fwd(qkv, w, B, S, cos, sin)
         if self.packed_qkv:
-            if not fused_rope:
+            if not fused_rope and raw is None:
                 ops.rope_qk_inplace(qkv, B, S, cfg.num_heads, cos, sin, **self.gqa_kw)
             o, lse = ops.attention_fwd_packed(qkv, B, S, cfg.num_heads, pa, k_attn, out=sb("o", H), **kw,
                                               **self.gqa_kw)
             q, k, v = qkv, None, None
         else:
-            q, k, v = ops.rope_qkv_fwd(qkv, B, S, cfg.num_heads, cos, sin, **self.gqa_kw)
+            q, k, v = ops.rope_qkv_fwd(qkv, B, S, cfg.num_heads, *self._split_tables(raw, cos, sin), **self.gqa_kw)
             o, lse = ops.attention_fwd(q, k, v, pa, k_attn, True, out=sb("o", H), **kw)
         del qkv
         a = gm.linear(o, w.wo)
@@ -539,14 +575,14 @@ class GPTEngine:
         if s_ring or self._refill_s(st):
             s = None
         if save:
-            c = _LayerCache(x=x, rstd1=rstd1, n1=n1, q=q, k=k, v=v, o=o, lse=lse,
+            c = _LayerCache(x=x, rstd1=rstd1, n1=n1, q=q, raw=raw, k=k, v=v, o=o, lse=lse,
                             x2=x2, rstd2=rstd2, n2=n2, gu=gu, s=s)
         elif st.recompute:
             if self.selective_recompute:
                 keep_qkv, keep_gu, keep_rest = self._ac_keep(M)
                 c = _LayerCache(x=x, o=o, lse=lse, x2=x2)
                 if keep_qkv and self.packed_qkv:
-                    c.q = q
+                    c.q, c.raw = q, raw
                 if keep_gu:
                     c.gu = gu
                 if keep_rest and keep_qkv and self.packed_qkv:  # nothing left to recompute
@@ -576,9 +612,18 @@ class GPTEngine:
         sb = lambda name, n: self._sb(st, i, name, M, n, dv)  # noqa: E731
         _, n1, rstd1 = ops.add_dropout_rmsnorm_fwd(c.x, None, w.ln1, self.eps, 0.0, 0, self.act_dtype,
                                                    y_out=sb("n1", H))
+        raw = c.raw
         if c.q is not None:  # QKV output kept by the forward (_ac_keep)
             qkv = c.q
             q, k, v = qkv, None, None
+        elif self.qk_norm:
+            qkv = gm.linear(n1, w.wqkv)
+            raw = self._qknorm_fwd(qkv, w, B, S, cos, sin)
+            if self.packed_qkv:
+                q, k, v = qkv, None, None
+            else:
+                q, k, v = ops.rope_qkv_fwd(qkv, B, S, cfg.num_heads, *self._split_tables(raw, cos, sin),
+                                           **self.gqa_kw)
         elif self.packed_qkv and hasattr(gm, "linear_rope") and not self.gqa:
             qkv = gm.linear_rope(n1, w.wqkv, B, S, cfg.num_heads, cos, sin, ops)
             q, k, v = qkv, None, None
@@ -603,7 +648,7 @@ class GPTEngine:
             s = None if s_ring else ops.swiglu_fwd(gu, out=sb("s", I))
         if s_ring:
             s = None
-        return _LayerCache(x=c.x, rstd1=rstd1, n1=n1, q=q, k=k, v=v, o=c.o, lse=c.lse,
+        return _LayerCache(x=c.x, rstd1=rstd1, n1=n1, q=q, raw=raw, k=k, v=v, o=c.o, lse=c.lse,
                            x2=c.x2, rstd2=rstd2, n2=n2, gu=gu, s=s)
 
     def forward(self, ids: torch.Tensor, targets: Optional[torch.Tensor], train: bool,
@@ -1065,6 +1110,12 @@ class GPTEngine:
                 del do
                 dqkv = ops.rope_qkv_bwd(dq, dk, dv, cos, sin, out=sb(i, "dqkv", self.qkv_width))
                 del dq, dk, dv
+            if self.qk_norm:
+                # dqkv's q|k columns hold dL/d(normalised head): the norm's backward rewrites
+                # them in place, and both QKV GEMMs below read the result.  gr.qn / gr.kn are
+                # shared with the other micro-steps like gr.ln1 / gr.ln2: this write lies
+                # between wait_prev(i) and mark(i)
+                ops.qknorm_bwd(dqkv, c.raw, B, S, cfg.num_heads, w.qn, w.kn, self.eps, gr.qn, gr.kn, **self.gqa_kw)
             dn1 = gm.linear_dgrad(dqkv, w.wqkv)
             key_prev = self._keys(st.micro, i - 1)[2] if i > 0 else 0
             p_prev = ph if i > 0 else 0.0

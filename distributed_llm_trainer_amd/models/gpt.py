@@ -92,6 +92,13 @@ class CausalSelfAttention(nn.Module):
         self.k_proj = nn.Linear(h, kv, bias=False)
         self.v_proj = nn.Linear(h, kv, bias=False)
         self.o_proj = nn.Linear(h, h, bias=False)
+        # QK-norm (config.qk_norm): RMSNorm over head_dim on every query / key head before
+        # RoPE, one weight per layer shared by the heads.  Without it the modules (and their
+        # state-dict keys) do not exist.
+        self.qk_norm = config.qk_norm
+        if self.qk_norm:
+            self.q_norm = RMSNorm(self.head_dim)
+            self.k_norm = RMSNorm(self.head_dim)
         self.attn_dropout = nn.Dropout(config.attention_dropout)
         self.resid_dropout = nn.Dropout(config.dropout)
         self.rotary_emb = RotaryPositionEmbedding(self.head_dim, config.max_seq_len)
@@ -106,6 +113,8 @@ class CausalSelfAttention(nn.Module):
         q = self.q_proj(hidden_states).view(B, S, self.num_heads, self.head_dim).transpose(1, 2)
         k = self.k_proj(hidden_states).view(B, S, self.num_kv_heads, self.head_dim).transpose(1, 2)
         v = self.v_proj(hidden_states).view(B, S, self.num_kv_heads, self.head_dim).transpose(1, 2)
+        if self.qk_norm:
+            q, k = self.q_norm(q), self.k_norm(k)
         cos, sin = self.rotary_emb(q, S)
         q, k = apply_rotary_pos_emb(q, k, cos[None, None], sin[None, None])
         if self.num_kv_heads != self.num_heads:  # query head h uses kv head h // G
@@ -226,6 +235,8 @@ class GPT(nn.Module):
             compute_dtype = act_dtype
         if self.config.num_kv_heads != self.config.num_heads and (ops is None or ops.backend == "hip"):
             ops_mod.check_gqa(dev, self.config.head_dim, act_dtype)  # before anything is re-homed
+        if self.config.qk_norm and (ops is None or ops.backend == "hip"):
+            ops_mod.check_qk_norm(dev, self.config.head_dim, act_dtype)
         if provider is None:
             from ..parallel.flat import FlatParamStore
             provider = FlatParamStore(self, dev, compute_dtype=compute_dtype)

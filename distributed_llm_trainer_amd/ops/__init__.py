@@ -16,7 +16,8 @@ from . import reference, rng
 _FUNCS = ("rope_tables", "embedding_fwd", "embedding_bwd", "add_dropout_rmsnorm_fwd", "rmsnorm_bwd",
           "rope_qkv_fwd", "rope_qkv_bwd", "attention_fwd", "attention_bwd", "swiglu_fwd", "swiglu_bwd",
           "cross_entropy_fwd_bwd", "scale_bf16", "rope_qk_inplace", "attention_fwd_packed",
-          "attention_bwd_packed", "lmhead_loss", "lmhead_loss_fits", "doc_bounds")
+          "attention_bwd_packed", "lmhead_loss", "lmhead_loss_fits", "doc_bounds", "qknorm_rope_inplace",
+          "qknorm_bwd")
 
 
 def _namespace(mod, name):
@@ -82,6 +83,24 @@ def check_gqa(device, head_dim: int = 64, act_dtype=torch.bfloat16) -> None:
         raise NotImplementedError(f"grouped-query attention (num_kv_heads < num_heads) needs head_dim in "
                                   f"{tuple(ATTN_HEAD_DIMS)} on the GPU; head_dim {head_dim} would run zero-padded "
                                   f"or as GEMMs, which have no grouped K/V")
+
+
+def check_qk_norm(device, head_dim: int = 64, act_dtype=torch.bfloat16) -> None:
+    """Raises NotImplementedError when the route :func:`for_device` picks for this model has
+    no QK-norm (``GPTConfig.qk_norm``): on the GPU the norm is fused with the in-place RoPE of
+    the 16-bit packed QKV (``qknorm_rope_inplace`` / ``qknorm_bwd``, head_dim 64 / 128); the
+    zero-padded heads, the GEMM-formulated route and the fp32 kernels have no such kernel.
+    Called when the engine is enabled, so the error comes before the first step."""
+    if torch.device(device).type != "cuda" or os.environ.get("DLT_ALLOW_REFERENCE_ON_GPU") == "1":
+        return
+    from .hip import ATTN_HEAD_DIMS
+    if act_dtype == torch.float32:
+        raise NotImplementedError("QK-norm (qk_norm) is not implemented for fp32 activations on the GPU: "
+                                  "use bf16 or fp16")
+    if head_dim not in ATTN_HEAD_DIMS:
+        raise NotImplementedError(f"QK-norm (qk_norm) needs head_dim in {tuple(ATTN_HEAD_DIMS)} on the GPU; "
+                                  f"head_dim {head_dim} would run zero-padded or as GEMMs, which have no "
+                                  f"QK-norm kernel")
 
 
 def for_device(device, head_dim: int = 64, act_dtype=torch.bfloat16) -> types.SimpleNamespace:

@@ -84,6 +84,15 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// sum over the N neighbouring lanes (N a power of two, the group aligned to N) that share
+// one head vector: an xor butterfly adds the same pairs on every lane, so all N lanes end
+// with the same bits
+template <int N>
+__device__ __forceinline__ float head_sum(float v) {
+#pragma unroll
+  for (int o = 1; o < N; o <<= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));

@@ -318,9 +318,93 @@ __global__ __launch_bounds__(256) void k_rope_qk_inplace_gqa(bf16_t* __restrict_
   }
 }
 
+// QK-norm + RoPE in place (GPTConfig.qk_norm): every q and k head vector x of the packed
+// row [q: nh heads | k: nkv heads | v: nkv heads] becomes rope(x * rsqrt(mean(x^2) + eps) * w),
+// w = qw for the q heads and kw for the k heads (one [HD] weight per layer, shared by the
+// heads); v is untouched.  Norm and rotation run in fp32 on the 16-bit GEMM output and the
+// result is rounded once.  The pre-norm q|k values also go to raw [M, hq * HD] (hq = nh + nkv):
+// the in-place write destroys them and k_qknorm_bwd (norm.hip) needs them; rstd is
+// recomputed there, not stored.  Lane layout of k_rope_qk_inplace_gqa: a thread holds 8
+// elements of the lower rotation half and their 8 partners, so the HD / 16 lanes of a head are
+// neighbours in one wave (256 % (HD / 16) == 0 and the grid stride keeps the alignment) and
+// the sum of squares is a butterfly of __shfl_xor over them (head_sum, common.h): no LDS.
+template <int HK, int HD>
+__global__ __launch_bounds__(256) void k_qknorm_rope_inplace(bf16_t* __restrict__ qkv, bf16_t* __restrict__ raw,
+                                                             const float* __restrict__ cosT,
+                                                             const float* __restrict__ sinT,
+                                                             const float* __restrict__ qw,
+                                                             const float* __restrict__ kw, float eps, int M, int S,
+                                                             int nh, int hq, int rs) {
+  constexpr int HALF = HD / 2;
+  constexpr int CPR = HALF / 8;  // lanes per head
+  const int total = M * hq * CPR;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const int j = (i % CPR) * 8;
+    const int r = i / CPR;
+    const int hh = r % hq;
+    const int m = r / hq;
+    const int s = m % S;
+    bf16_t* p = qkv + (size_t)m * rs + hh * HD;
+    const u16x8 a = *reinterpret_cast<const u16x8*>(p + j);
+    const u16x8 c = *reinterpret_cast<const u16x8*>(p + HALF + j);
+    bf16_t* rp = raw + (size_t)m * (hq * HD) + hh * HD;
+    *reinterpret_cast<u16x8*>(rp + j) = a;
+    *reinterpret_cast<u16x8*>(rp + HALF + j) = c;
+    float x1[8], x2[8];
+    float ss = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      x1[e] = h2f<HK>(a.v[e]);
+      x2[e] = h2f<HK>(c.v[e]);
+      ss += x1[e] * x1[e] + x2[e] * x2[e];
+    }
+    const float rstd = rsqrtf(head_sum<CPR>(ss) * (1.f / HD) + eps);
+    const float* w = hh < nh ? qw : kw;
+    const float* cp = cosT + s * HALF + j;
+    const float* sp = sinT + s * HALF + j;
+    const float4 c0 = *reinterpret_cast<const float4*>(cp), c1 = *reinterpret_cast<const float4*>(cp + 4);
+    const float4 s0 = *reinterpret_cast<const float4*>(sp), s1 = *reinterpret_cast<const float4*>(sp + 4);
+    const float4 a0 = *reinterpret_cast<const float4*>(w + j), a1 = *reinterpret_cast<const float4*>(w + j + 4);
+    const float4 b0 = *reinterpret_cast<const float4*>(w + HALF + j);
+    const float4 b1 = *reinterpret_cast<const float4*>(w + HALF + j + 4);
+    const float cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+    const float sn[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+    const float w1[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+    const float w2[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+    u16x8 o1, o2;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float u1 = x1[e] * rstd * w1[e], u2 = x2[e] * rstd * w2[e];
+      o1.v[e] = f2h<HK>(u1 * cc[e] - u2 * sn[e]);
+      o2.v[e] = f2h<HK>(u2 * cc[e] + u1 * sn[e]);
+    }
+    *reinterpret_cast<u16x8*>(p + j) = o1;
+    *reinterpret_cast<u16x8*>(p + HALF + j) = o2;
+  }
+}
+
 static inline int ew_blocks(size_t total) {
   size_t b = (total + 255) / 256;
   return (int)(b > 16384 ? 16384 : (b == 0 ? 1 : b));
+}
+
+// packed [M, (nh + 2 nkv) * hd] rows (nkv == nh: multi-head), hd 64 / 128; raw [M, (nh + nkv) * hd];
+// qw, kw: fp32 [hd]
+DLT_API int dlt_qknorm_rope_inplace(bf16_t* qkv, bf16_t* raw, const float* cosT, const float* sinT, const float* qw,
+                                    const float* kw, float eps, int M, int S, int nh, int nkv, int hd, int hk,
+                                    hipStream_t st) {
+  if ((hd != 64 && hd != 128) || S <= 0 || M <= 0 || M % S || nkv <= 0 || nh <= 0 || nh % nkv ||
+      (long)M * (nh + 2 * nkv) * hd >= (1L << 31))
+    return -1;
+  const int hq = nh + nkv, rs = (nh + 2 * nkv) * hd;
+  const int blocks = ew_blocks((size_t)M * hq * (hd / 16));
+  if (hd == 64)
+    DLT_HK_DISPATCH(hk, k_qknorm_rope_inplace<HKC, 64><<<blocks, 256, 0, st>>>(qkv, raw, cosT, sinT, qw, kw, eps, M, S,
+                                                                               nh, hq, rs));
+  else
+    DLT_HK_DISPATCH(hk, k_qknorm_rope_inplace<HKC, 128><<<blocks, 256, 0, st>>>(qkv, raw, cosT, sinT, qw, kw, eps, M, S,
+                                                                                nh, hq, rs));
+  DLT_CHECK_LAUNCH();
 }
 
 DLT_API int dlt_rope_qkv_fwd(const bf16_t* qkv, const float* cosT, const float* sinT, bf16_t* q, bf16_t* k,

@@ -275,6 +275,126 @@ __global__ __launch_bounds__(64 * QN) void k_colsum_acc(const float* __restrict_
   }
 }
 
+// Backward of the QK-norm of k_qknorm_rope_inplace (elementwise.hip).  dqkv is the packed
+// gradient as the attention backward leaves it: its q|k columns hold g = dL/du, u the
+// normalised pre-RoPE head.  With x the pre-norm head (raw [M, hq * HD]), rstd recomputed
+// from it, xh = x * rstd and dxh = g * w, the q|k columns are overwritten in place with
+//   dx = rstd * (dxh - xh * mean(dxh * xh))
+// (rounded once); the v columns are not touched.  dw[j] = sum over tokens and heads of g * xh:
+// blockIdx.y = 0 handles the q heads (weight qw), 1 the k heads (kw).  A thread owns lane
+// c = tid % CPR of slot tid / CPR (the forward's lane layout: 8 elements of each rotation
+// half) and walks heads slot, slot + gridDim.x * SLOTS, ... adding g * xh into 16 registers;
+// the block then sums its SLOTS slots per column through LDS in slot order and writes row
+// (blockIdx.y * gridDim.x + blockIdx.x) of the fp32 workspace -- every block writes its row,
+// also one without work.  k_colsum_acc adds the rows into dw in a fixed order: no float
+// atomics, two calls give the same bits.
+template <int HK, int HD>
+__global__ __launch_bounds__(256) void k_qknorm_bwd(bf16_t* __restrict__ dqkv, const bf16_t* __restrict__ raw,
+                                                    const float* __restrict__ qw, const float* __restrict__ kw,
+                                                    float* __restrict__ ws, float eps, int M, int nh, int nkv) {
+  constexpr int HALF = HD / 2;
+  constexpr int CPR = HALF / 8;  // lanes per head
+  constexpr int SLOTS = 256 / CPR;
+  __shared__ float red[SLOTS][HD];
+  const int part = blockIdx.y;
+  const int heads = part ? nkv : nh;
+  const int col0 = part ? nh * HD : 0;  // first column of the part in a dqkv / raw row
+  const int rs = (nh + 2 * nkv) * HD, rr = (nh + nkv) * HD;
+  const float* w = part ? kw : qw;
+  const int j = (threadIdx.x % CPR) * 8, slot = threadIdx.x / CPR;
+  float w1[8], w2[8], acc1[8], acc2[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    w1[e] = w[j + e];
+    w2[e] = w[HALF + j + e];
+    acc1[e] = 0.f;
+    acc2[e] = 0.f;
+  }
+  const int items = M * heads;
+  for (int r = blockIdx.x * SLOTS + slot; r < items; r += gridDim.x * SLOTS) {
+    const int m = r / heads, h = r % heads;
+    const bf16_t* xp = raw + (size_t)m * rr + col0 + h * HD;
+    bf16_t* gp = dqkv + (size_t)m * rs + col0 + h * HD;
+    const u16x8 xa = *reinterpret_cast<const u16x8*>(xp + j);
+    const u16x8 xc = *reinterpret_cast<const u16x8*>(xp + HALF + j);
+    const u16x8 ga = *reinterpret_cast<const u16x8*>(gp + j);
+    const u16x8 gc = *reinterpret_cast<const u16x8*>(gp + HALF + j);
+    float x1[8], x2[8];
+    float ss = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      x1[e] = h2f<HK>(xa.v[e]);
+      x2[e] = h2f<HK>(xc.v[e]);
+      ss += x1[e] * x1[e] + x2[e] * x2[e];
+    }
+    const float rstd = rsqrtf(head_sum<CPR>(ss) * (1.f / HD) + eps);
+    float d1[8], d2[8];
+    float dot = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float g1 = h2f<HK>(ga.v[e]), g2 = h2f<HK>(gc.v[e]);
+      x1[e] *= rstd;  // xh
+      x2[e] *= rstd;
+      d1[e] = g1 * w1[e];  // dxh
+      d2[e] = g2 * w2[e];
+      dot += d1[e] * x1[e] + d2[e] * x2[e];
+      acc1[e] += g1 * x1[e];
+      acc2[e] += g2 * x2[e];
+    }
+    const float mean = head_sum<CPR>(dot) * (1.f / HD);
+    u16x8 o1, o2;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      o1.v[e] = f2h<HK>(rstd * (d1[e] - x1[e] * mean));
+      o2.v[e] = f2h<HK>(rstd * (d2[e] - x2[e] * mean));
+    }
+    *reinterpret_cast<u16x8*>(gp + j) = o1;
+    *reinterpret_cast<u16x8*>(gp + HALF + j) = o2;
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    red[slot][j + e] = acc1[e];
+    red[slot][HALF + j + e] = acc2[e];
+  }
+  __syncthreads();
+  if (threadIdx.x < HD) {
+    float s = 0.f;
+    for (int k = 0; k < SLOTS; ++k) s += red[k][threadIdx.x];
+    ws[((size_t)part * gridDim.x + blockIdx.x) * HD + threadIdx.x] = s;
+  }
+}
+
+// blocks per part of k_qknorm_bwd: one head per slot and pass, at most 1024 blocks
+static inline int qknorm_bwd_blocks(int M, int nh, int hd) {
+  const int slots = 256 / (hd / 16);
+  const long b = ((long)M * nh + slots - 1) / slots;
+  return (int)(b > 1024 ? 1024 : (b < 1 ? 1 : b));
+}
+
+// floats of the workspace of dlt_qknorm_bwd (2 parts x blocks x hd)
+DLT_API long dlt_qknorm_bwd_ws(int M, int nh, int hd) {
+  if ((hd != 64 && hd != 128) || M <= 0 || nh <= 0) return -1;
+  return 2L * qknorm_bwd_blocks(M, nh, hd) * hd;
+}
+
+// dqkv [M, (nh + 2 nkv) * hd] (q|k columns rewritten in place), raw [M, (nh + nkv) * hd], qw / kw
+// fp32 [hd], dqw / dkw fp32 [hd] accumulated, ws: dlt_qknorm_bwd_ws floats
+DLT_API int dlt_qknorm_bwd(bf16_t* dqkv, const bf16_t* raw, const float* qw, const float* kw, float* dqw, float* dkw,
+                           float* ws, float eps, int M, int nh, int nkv, int hd, int hk, hipStream_t stream) {
+  if ((hd != 64 && hd != 128) || M <= 0 || nkv <= 0 || nh <= 0 || nh % nkv ||
+      (long)M * (nh + 2 * nkv) * hd >= (1L << 31))
+    return -1;
+  const int blocks = qknorm_bwd_blocks(M, nh, hd);
+  const dim3 grid(blocks, 2), block(256);
+  if (hd == 64)
+    DLT_HK_DISPATCH(hk, k_qknorm_bwd<HKC, 64><<<grid, block, 0, stream>>>(dqkv, raw, qw, kw, ws, eps, M, nh, nkv));
+  else
+    DLT_HK_DISPATCH(hk, k_qknorm_bwd<HKC, 128><<<grid, block, 0, stream>>>(dqkv, raw, qw, kw, ws, eps, M, nh, nkv));
+  k_colsum_acc<4><<<(hd + 15) / 16, 256, 0, stream>>>(ws, dqw, blocks, hd);
+  k_colsum_acc<4><<<(hd + 15) / 16, 256, 0, stream>>>(ws + (size_t)blocks * hd, dkw, blocks, hd);
+  DLT_CHECK_LAUNCH();
+}
+
 static inline int nch_of(int H) {
   int n = (H / 4 + 63) / 64;
   if (n > 8 && n <= 12) n = 12;

@@ -83,6 +83,10 @@ _SIGS = {
     "dlt_attn_dropout_mask": [c_void_p, c_int, c_int, c_int, c_uint32, c_uint32, c_void_p],
     "dlt_attn_args_size": [],
     "dlt_rope_qk_inplace": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "dlt_qknorm_rope_inplace": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int,
+                                c_int, c_int, c_int, c_void_p],
+    "dlt_qknorm_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int,
+                       c_int, c_int, c_int, c_void_p],
     "dlt_dec_norm_qkv": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                          c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "dlt_dec_attn": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p],
@@ -125,6 +129,8 @@ def lib():
         L.dlt_gemm_wgrad_grp_scratch.restype = ctypes.c_long
         L.dlt_lmhead_loss_scratch.argtypes = [c_int, c_int]
         L.dlt_lmhead_loss_scratch.restype = ctypes.c_long
+        L.dlt_qknorm_bwd_ws.argtypes = [c_int, c_int, c_int]
+        L.dlt_qknorm_bwd_ws.restype = ctypes.c_long
         if L.dlt_attn_args_size() != ctypes.sizeof(_AttnArgs):
             raise RuntimeError(f"{_LIBPATH}: dlt_attn_args is {L.dlt_attn_args_size()} bytes, _AttnArgs "
                                f"{ctypes.sizeof(_AttnArgs)}: rebuild the library (ops/build.py)")
@@ -572,6 +578,93 @@ def rope_qk_inplace(qkv, B, S, nh, cos, sin, nkv=None):
     _chk(lib().dlt_rope_qk_inplace(_p(qkv), _p(cos), _p(sin), M, S, nh, nkv or 0, hd, hk, _stream()),
          "rope_qk_inplace" if nkv is None else "rope_qk_inplace_gqa")
     return qkv
+
+
+# ---------------------------------------------------------------- QK-norm
+def _qknorm_dims(t, B, S, nh, nkv, name: str):
+    """(nkv, hd) of a packed [B*S, (nh + 2*nkv)*hd] tensor of a QK-norm call (hd 64 / 128)."""
+    nkv = nh if nkv is None else _req_nkv(nh, nkv, name)
+    if t.dtype == torch.float32:
+        raise NotImplementedError(f"{name}: QK-norm is not implemented for fp32 activations on the GPU")
+    if t.dim() != 2 or B < 1 or S < 1 or nh < 1:
+        raise ValueError(f"{name}: expected a [B*S, (nh + 2*nkv)*hd] tensor")
+    M, Wd = t.shape
+    heads = nh + 2 * nkv
+    hd = Wd // heads
+    if M != B * S or hd * heads != Wd:
+        raise ValueError(f"{name}: expected [B*S, (nh + 2*nkv)*hd] = [{B * S}, {heads}*hd], got {list(t.shape)}")
+    if hd not in ATTN_HEAD_DIMS:
+        raise NotImplementedError(f"{name}: QK-norm needs head_dim in {tuple(ATTN_HEAD_DIMS)} on the GPU, got {hd}")
+    if M * Wd >= 2 ** 31:
+        raise ValueError(f"{name}: {M} x {Wd} elements overflow the kernel's 32-bit index")
+    return nkv, hd
+
+
+def _qknorm_weight(w: torch.Tensor, hd: int, name: str) -> torch.Tensor:
+    """The [hd] norm weight as the kernels read it: fp32, contiguous, 16-byte aligned (the
+    flat master is; a gathered 16-bit FSDP unit is upcast, hd elements)."""
+    if not isinstance(w, torch.Tensor) or not w.is_cuda or w.numel() != hd:
+        raise ValueError(f"{name}: expected a GPU tensor of {hd} elements")
+    if w.dtype != torch.float32:
+        w = w.float()
+    if not w.is_contiguous() or w.data_ptr() % 16:
+        w = w.contiguous().clone()
+    return w
+
+
+def qknorm_rope_inplace(qkv, B, S, nh, cos, sin, qw, kw, eps, raw_out, nkv=None):
+    """QK-norm + RoPE of the q and k heads of the packed [B*S, (nh + 2*nkv)*hd] QKV in place:
+    head vector x -> rope(x * rsqrt(mean(x^2) + eps) * w), w = ``qw`` / ``kw`` ([hd]); fp32
+    math, one rounding; v untouched.  ``raw_out`` [B*S, (nh + nkv)*hd] receives the pre-norm
+    q|k values (the backward's input)."""
+    nkv, hd = _qknorm_dims(qkv, B, S, nh, nkv, "qknorm_rope_inplace")
+    M = B * S
+    hk = _req_act(qkv, qkv.dtype, "qknorm_rope.qkv")
+    _req(raw_out, qkv.dtype, "qknorm_rope.raw_out", M * (nh + nkv) * hd)
+    if raw_out.device != qkv.device:
+        raise ValueError("qknorm_rope.raw_out: expected the device of qkv")
+    if cos.dim() != 2 or cos.shape[0] < S or cos.shape[1] != hd // 2 or sin.shape != cos.shape:
+        raise ValueError("qknorm_rope_inplace: rope tables too short")
+    _req(cos, torch.float32, "qknorm_rope.cos")
+    _req(sin, torch.float32, "qknorm_rope.sin")
+    qw = _qknorm_weight(qw, hd, "qknorm_rope.qw")
+    kw = _qknorm_weight(kw, hd, "qknorm_rope.kw")
+    _chk(lib().dlt_qknorm_rope_inplace(_p(qkv), _p(raw_out), _p(cos), _p(sin), _p(qw), _p(kw), float(eps), M, S, nh,
+                                       nkv, hd, hk, _stream()), "qknorm_rope_inplace")
+    return qkv
+
+
+def qknorm_bwd_workspace(M: int, nh: int, hd: int, device) -> torch.Tensor:
+    """fp32 workspace of :func:`qknorm_bwd`: the per-workgroup weight-gradient partials."""
+    n = lib().dlt_qknorm_bwd_ws(M, nh, hd)
+    if n <= 0:
+        raise ValueError(f"qknorm_bwd: no kernel for M={M}, nh={nh}, hd={hd}")
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def qknorm_bwd(dqkv, raw, B, S, nh, qw, kw, eps, dqw, dkw, nkv=None, ws=None):
+    """Backward of the norm of :func:`qknorm_rope_inplace`.  The q|k columns of the packed
+    gradient ``dqkv`` (as ``attention_bwd_packed`` leaves it: dL/du, inverse rotation applied)
+    are overwritten in place with dL/dx; v columns untouched.  ``dqw`` / ``dkw`` (fp32 [hd])
+    += sum over tokens and heads of g * xh, reduced in a fixed order (no atomics)."""
+    nkv, hd = _qknorm_dims(dqkv, B, S, nh, nkv, "qknorm_bwd")
+    M = B * S
+    hk = _req_act(dqkv, dqkv.dtype, "qknorm_bwd.dqkv")
+    _req(raw, dqkv.dtype, "qknorm_bwd.raw", M * (nh + nkv) * hd)
+    qw = _qknorm_weight(qw, hd, "qknorm_bwd.qw")
+    kw = _qknorm_weight(kw, hd, "qknorm_bwd.kw")
+    _req(dqw, torch.float32, "qknorm_bwd.dqw", hd)
+    _req(dkw, torch.float32, "qknorm_bwd.dkw", hd)
+    if ws is None:
+        ws = qknorm_bwd_workspace(M, nh, hd, dqkv.device)
+    else:
+        _req(ws, torch.float32, "qknorm_bwd.ws", lib().dlt_qknorm_bwd_ws(M, nh, hd))
+    for t, n in ((raw, "raw"), (dqw, "dqw"), (dkw, "dkw"), (ws, "ws")):
+        if t.device != dqkv.device:
+            raise ValueError(f"qknorm_bwd.{n}: expected the device of dqkv")
+    _chk(lib().dlt_qknorm_bwd(_p(dqkv), _p(raw), _p(qw), _p(kw), _p(dqw), _p(dkw), _p(ws), float(eps), M, nh, nkv,
+                              hd, hk, _stream()), "qknorm_bwd")
+    return dqkv
 
 
 def _off(t: torch.Tensor, elems: int):

@@ -166,6 +166,47 @@ def rope_qk_inplace(qkv: torch.Tensor, B: int, S: int, nh: int, cos: torch.Tenso
     return qkv
 
 
+def qknorm_rope_inplace(qkv: torch.Tensor, B: int, S: int, nh: int, cos: torch.Tensor, sin: torch.Tensor,
+                        qw: torch.Tensor, kw: torch.Tensor, eps: float, raw_out: torch.Tensor, nkv=None):
+    """QK-norm + RoPE of the q and k heads of the packed [B*S, H + 2*KV] QKV in place: head
+    vector x (the GEMM output as rounded to the activation dtype) -> rope(x * rsqrt(mean(x^2)
+    + eps) * w) with ``qw`` / ``kw`` [hd]; norm and rotation in fp32, rounded once.  The
+    pre-norm q|k columns go to ``raw_out`` [B*S, H + KV]; v is untouched."""
+    (tq, tk, _), hd = _qkv_views(qkv, B, S, nh, nkv)
+    _, _, H, KV = _packed_dims(qkv, nh, nkv)
+    if tuple(raw_out.shape) != (B * S, H + KV) or raw_out.dtype != qkv.dtype:
+        raise ValueError(f"qknorm_rope_inplace: raw_out must be [{B * S}, {H + KV}] {qkv.dtype}")
+    raw_out.copy_(qkv[:, :H + KV])
+    c = cos[:S].view(1, S, 1, hd // 2)
+    s = sin[:S].view(1, S, 1, hd // 2)
+    for t, w in ((tq, qw), (tk, kw)):
+        x = t.float()
+        u = x * torch.rsqrt(x.pow(2).mean(dim=-1, keepdim=True) + eps) * w.float()
+        t.copy_(_rot(u, c, s).to(qkv.dtype))
+    return qkv
+
+
+def qknorm_bwd(dqkv: torch.Tensor, raw: torch.Tensor, B: int, S: int, nh: int, qw: torch.Tensor, kw: torch.Tensor,
+               eps: float, dqw: torch.Tensor, dkw: torch.Tensor, nkv=None, ws=None):
+    """Backward of the norm of :func:`qknorm_rope_inplace`.  The q|k columns of ``dqkv`` hold
+    g = dL/du (u the normalised pre-RoPE head: ``attention_bwd_packed`` applies the inverse
+    rotation) and are overwritten with dx = rstd * (dxh - xh * mean(dxh * xh)), xh = x * rstd,
+    dxh = g * w, x from ``raw``; fp32 math, rounded once; v columns untouched.  ``dqw`` /
+    ``dkw`` += sum over tokens and heads of g * xh."""
+    (gq, gk, _), hd = _qkv_views(dqkv, B, S, nh, nkv)
+    nkv, _, H, KV = _packed_dims(dqkv, nh, nkv)
+    r = raw.view(B, S, H + KV)
+    xq, xk = r[..., :H].view(B, S, nh, hd), r[..., H:].view(B, S, nkv, hd)
+    for gt, xt, w, dw in ((gq, xq, qw, dqw), (gk, xk, kw, dkw)):
+        x, g = xt.float(), gt.float()
+        rstd = torch.rsqrt(x.pow(2).mean(dim=-1, keepdim=True) + eps)
+        xh = x * rstd
+        dxh = g * w.float()
+        dw += (g * xh).sum(dim=(0, 1, 2)).to(dw.dtype)
+        gt.copy_((rstd * (dxh - xh * (dxh * xh).mean(dim=-1, keepdim=True))).to(dqkv.dtype))
+    return dqkv
+
+
 def _split_packed(qkv, B, S, nh, nkv=None):
     views, _ = _qkv_views(qkv, B, S, nh, nkv)
     return tuple(t.transpose(1, 2).contiguous() for t in views)

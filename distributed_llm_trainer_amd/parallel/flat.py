@@ -72,6 +72,9 @@ class FlatLayout:
         for i in range(L):
             add(f"layers.{i}.input_layernorm.weight", (H,))
             add(f"layers.{i}.post_attention_layernorm.weight", (H,))
+            if cfg.qk_norm:  # QK-norm weights ride with the layer's norm weights (no decay)
+                add(f"layers.{i}.attention.q_norm.weight", (cfg.head_dim,))
+                add(f"layers.{i}.attention.k_norm.weight", (cfg.head_dim,))
         add("norm.weight", (H,))
         self.total = off
         self.segments = segs
@@ -143,14 +146,18 @@ class FlatParamStore(ParamProvider):
                 wgu=v(self.shadow, p + "mlp.gate_proj.weight", 2 * I, H),
                 wdown=v(self.shadow, p + "mlp.down_proj.weight", H, I),
                 ln1=vec(self.flat, p + "input_layernorm.weight"),
-                ln2=vec(self.flat, p + "post_attention_layernorm.weight")))
+                ln2=vec(self.flat, p + "post_attention_layernorm.weight"),
+                qn=vec(self.flat, p + "attention.q_norm.weight") if cfg.qk_norm else None,
+                kn=vec(self.flat, p + "attention.k_norm.weight") if cfg.qk_norm else None))
             self._lgrads.append(LayerGrads(
                 wqkv=v(self.grad, p + "attention.q_proj.weight", QKV, H),
                 wo=v(self.grad, p + "attention.o_proj.weight", H, H),
                 wgu=v(self.grad, p + "mlp.gate_proj.weight", 2 * I, H),
                 wdown=v(self.grad, p + "mlp.down_proj.weight", H, I),
                 ln1=vec(self.grad, p + "input_layernorm.weight"),
-                ln2=vec(self.grad, p + "post_attention_layernorm.weight")))
+                ln2=vec(self.grad, p + "post_attention_layernorm.weight"),
+                qn=vec(self.grad, p + "attention.q_norm.weight") if cfg.qk_norm else None,
+                kn=vec(self.grad, p + "attention.k_norm.weight") if cfg.qk_norm else None))
         e = bn["embed_tokens.weight"]
         self._head = HeadWeights(
             embed=self.flat[e.offset:e.offset + e.numel].view(e.shape),
@@ -162,7 +169,7 @@ class FlatParamStore(ParamProvider):
     def unit_ranges(self) -> Dict[object, List[Tuple[int, int]]]:
         """The flat ranges of each forward unit, in forward order: "head" (embedding / tied
         lm_head + the final norm; the embedding is read first) and layer i (its weights and
-        its two norm weights).  Together they cover the buffer exactly once (the lazy
+        its norm weights).  Together they cover the buffer exactly once (the lazy
         optimizer step updates one unit at a time, training/optim.py LazyStep)."""
         lay, H = self.layout, self.cfg.hidden_size
         bn = lay.by_name
@@ -173,7 +180,12 @@ class FlatParamStore(ParamProvider):
             n1 = bn[f"layers.{i}.input_layernorm.weight"]
             n2 = bn[f"layers.{i}.post_attention_layernorm.weight"]
             assert n2.offset == n1.offset + H
-            units[i] = [(a, b), (n1.offset, n2.offset + H)]
+            end = n2.offset + H
+            if self.cfg.qk_norm:  # q_norm, k_norm follow the layer's two norm weights
+                kn = bn[f"layers.{i}.attention.k_norm.weight"]
+                assert bn[f"layers.{i}.attention.q_norm.weight"].offset == end
+                end = kn.offset + kn.numel
+            units[i] = [(a, b), (n1.offset, end)]
         return units
 
     # pending lazy optimizer step (training/optim.py LazyStep): each unit's update is

@@ -12,7 +12,7 @@ one gather in flight beyond the one being consumed (``limit_all_gathers``).
 
 MI355X-specific design choices:
 
-* Unit = one flat buffer laid out ``[q|k|v|o|gate|up|down|ln1|ln2]`` so the
+* Unit = one flat buffer laid out ``[q|k|v|o|gate|up|down|ln1|ln2]`` (``|q_norm|k_norm`` with QK-norm) so the
   gathered bf16 buffer is directly the packed QKV / gate|up GEMM operands (no
   unflatten copies).  The root unit ``[embed(Vp rows)|norm]`` keeps the padded
   vocabulary rows so the gathered buffer IS the lm_head operand.
@@ -88,7 +88,7 @@ class FlatUnit:
         self.host_bufs = []      # cpu_offload: pinned staging buffers, one per pending reduce
         self.refs = 0            # chains (forward / backward of a micro-step) using `full`
         self.ready_ev = None     # HIP event: `full` is complete (recorded after the gather wait)
-        self.norm_grad = None    # bf16-gradient mode: fp32 ln1 | ln2 gradients of the micro-step
+        self.norm_grad = None    # bf16-gradient mode: fp32 ln1 | ln2 (| q_norm | k_norm) gradients of the micro-step
         self.head_q = []         # root unit: gradient buffers of backwards issued but not yet reduced
 
     def local_slice(self) -> Tuple[int, int]:
@@ -192,6 +192,9 @@ class FSDPRuntime(ParamProvider):
             add(p + "mlp.down_proj.weight", (H, I))
             add(p + "input_layernorm.weight", (H,))
             add(p + "post_attention_layernorm.weight", (H,))
+            if cfg.qk_norm:  # QK-norm weights: part of the layer's unit, after its norm weights
+                add(p + "attention.q_norm.weight", (cfg.head_dim,))
+                add(p + "attention.k_norm.weight", (cfg.head_dim,))
         return segs, off
 
     @torch.no_grad()
@@ -397,6 +400,21 @@ class FSDPRuntime(ParamProvider):
                 return buf[s.offset:s.offset + rows * cols].view(rows, cols)
         raise KeyError(name)
 
+    def _qk_views(self, u: FlatUnit, buf: torch.Tensor, p: str) -> dict:
+        """The qn / kn fields (QK-norm weights or gradients) of a layer unit's buffer; empty
+        without cfg.qk_norm."""
+        if not self.cfg.qk_norm:
+            return {}
+        return {"qn": self._view(u, buf, p + "attention.q_norm.weight"),
+                "kn": self._view(u, buf, p + "attention.k_norm.weight")}
+
+    def _qk_side(self, norm_grad: torch.Tensor) -> dict:
+        """The same fields in the fp32 side buffer of the bf16-gradient mode (after ln1 | ln2)."""
+        if not self.cfg.qk_norm:
+            return {}
+        H, hd = self.cfg.hidden_size, self.cfg.head_dim
+        return {"qn": norm_grad[2 * H:2 * H + hd], "kn": norm_grad[2 * H + hd:]}
+
     def layer(self, i):
         u = self.units[i]
         self._wait_gather(u)
@@ -408,7 +426,8 @@ class FSDPRuntime(ParamProvider):
                             wgu=self._view(u, f, p + "mlp.gate_proj.weight", 2 * I, H),
                             wdown=self._view(u, f, p + "mlp.down_proj.weight", H, I),
                             ln1=self._view(u, f, p + "input_layernorm.weight"),
-                            ln2=self._view(u, f, p + "post_attention_layernorm.weight"))
+                            ln2=self._view(u, f, p + "post_attention_layernorm.weight"),
+                            **self._qk_views(u, f, p))
 
     def layer_grads(self, i):
         u = self.units[i]
@@ -418,21 +437,24 @@ class FSDPRuntime(ParamProvider):
                 u.full_grad = torch.empty(u.padded, dtype=self.reduce_dtype, device=self.device)
                 if u.padded > u.numel:
                     u.full_grad[u.numel:].zero_()
-                u.norm_grad = torch.zeros(2 * H, dtype=torch.float32, device=self.device)
+                u.norm_grad = torch.zeros(2 * H + (2 * self.cfg.head_dim if self.cfg.qk_norm else 0),
+                                          dtype=torch.float32, device=self.device)
             else:
                 u.full_grad = torch.zeros(u.padded, dtype=torch.float32, device=self.device)
         p = f"layers.{i}."
         g = u.full_grad
         if g.dtype in (torch.bfloat16, torch.float16):
-            ln1, ln2 = u.norm_grad[:H], u.norm_grad[H:]
+            ln1, ln2 = u.norm_grad[:H], u.norm_grad[H:2 * H]
+            qk = self._qk_side(u.norm_grad)
         else:
             ln1 = self._view(u, g, p + "input_layernorm.weight")
             ln2 = self._view(u, g, p + "post_attention_layernorm.weight")
+            qk = self._qk_views(u, g, p)
         return LayerGrads(wqkv=self._view(u, g, p + "attention.q_proj.weight", H + 2 * self.cfg.kv_size, H),
                           wo=self._view(u, g, p + "attention.o_proj.weight", H, H),
                           wgu=self._view(u, g, p + "mlp.gate_proj.weight", 2 * I, H),
                           wdown=self._view(u, g, p + "mlp.down_proj.weight", H, I),
-                          ln1=ln1, ln2=ln2)
+                          ln1=ln1, ln2=ln2, **qk)
 
     def head(self):
         u = self.units["head"]
@@ -492,9 +514,11 @@ class FSDPRuntime(ParamProvider):
             # the norm-weight gradients (fp32 side buffer) into the bf16 send buffer
             H = self.cfg.hidden_size
             p = f"layers.{uid}."
+            qk_dst, qk_src = self._qk_views(u, u.full_grad, p), self._qk_side(u.norm_grad)
             torch._foreach_copy_([self._view(u, u.full_grad, p + "input_layernorm.weight"),
-                                  self._view(u, u.full_grad, p + "post_attention_layernorm.weight")],
-                                 [u.norm_grad[:H], u.norm_grad[H:]])  # one multi-tensor launch
+                                  self._view(u, u.full_grad, p + "post_attention_layernorm.weight"),
+                                  *qk_dst.values()],
+                                 [u.norm_grad[:H], u.norm_grad[H:2 * H], *qk_src.values()])  # one multi-tensor launch
             u.norm_grad = None
         if uid == "head" and u.head_q:
             u.full_grad = u.head_q.pop(0)

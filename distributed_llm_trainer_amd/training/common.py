@@ -219,6 +219,10 @@ def add_model_args(p) -> None:
                    help="grouped-query attention: N key/value heads shared by groups of num_heads / N query "
                         "heads (N must divide num_heads; 1 = multi-query).  Overrides the YAML's "
                         "model.num_kv_heads and the preset (default: num_heads, plain multi-head attention)")
+    p.add_argument("--qk_norm", action="store_true", default=None,
+                   help="QK-norm: an RMSNorm over head_dim on every query and key head before RoPE, with one "
+                        "q_norm and one k_norm weight per layer.  Overrides the YAML's model.qk_norm and the "
+                        "preset (default: off)")
 
 
 def apply_model_args(args, model_config) -> None:
@@ -228,6 +232,8 @@ def apply_model_args(args, model_config) -> None:
         if nkv < 1 or model_config.num_heads % nkv:
             raise ValueError(f"--num_kv_heads {nkv} must divide num_heads ({model_config.num_heads})")
         model_config.num_kv_heads = nkv
+    if getattr(args, "qk_norm", None) is not None:
+        model_config.qk_norm = bool(args.qk_norm)
 
 
 def unwrap_batch(batch):
