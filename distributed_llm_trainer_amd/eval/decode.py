@@ -14,6 +14,10 @@ With grouped-query attention (``num_kv_heads < num_heads``) the cache holds the
 for either layout (:func:`_fused_kind`): the grouped-query one reads every cached K/V
 row once for all query heads of its group and splits the keys over several workgroups.
 
+Sliding-window layers (``cfg.layer_window``) attend to the last ``W`` cached keys only: the
+ATen paths add the lower bound to their masks, the fused step calls the ``window`` forms of
+the two attention kernels.  The cache keeps ``max_seq_len`` rows (no ring buffer).
+
 Weights are read from the engine's provider (bf16 shadows on GPU / FSDP gathered
 units), so generation works the same for single-GPU, DDP and FSDP-trained models.
 """
@@ -69,6 +73,22 @@ def _split_qkv(qkv: torch.Tensor, cfg):
             qkv[..., H + KV:].view(B, T, nkv, hd))
 
 
+def _layer_window(cfg, i: int) -> Optional[int]:
+    """Window of layer ``i`` or None (also for configs from before the field existed)."""
+    lw = getattr(cfg, "layer_window", None)
+    return lw(i) if lw is not None else None
+
+
+def _attn_keys(cfg) -> int:
+    """Keys whose scores the fused attention kernels must hold, the largest need over the
+    layers: ``max_seq_len`` for a global layer, ``min(W, max_seq_len)`` for a windowed one."""
+    W = getattr(cfg, "sliding_window", None)
+    N = getattr(cfg, "sliding_window_pattern", None)
+    if W is None or (N is not None and getattr(cfg, "num_layers", N) >= N):  # some layer is global
+        return cfg.max_seq_len
+    return min(W, cfg.max_seq_len)
+
+
 def _rep_kv(t: torch.Tensor, cfg) -> torch.Tensor:
     """Cached K or V [B, nkv, S, hd] repeated over each group's query heads."""
     G = cfg.num_heads // cfg.num_kv_heads
@@ -105,10 +125,14 @@ def forward_cached(model, ids: torch.Tensor, cache: KVCache) -> torch.Tensor:
         Vv = _rep_kv(cache.v[i][:, :, :p0 + T].float(), cfg)
         qh = q.to(dt).float().transpose(1, 2)  # [B, nh, T, hd]
         s = torch.matmul(qh, K.transpose(-2, -1)) * scale
-        if T > 1:
+        W = _layer_window(cfg, i)
+        if T > 1 or (W is not None and W < p0 + T):
             qpos = torch.arange(p0, p0 + T, device=ids.device)[:, None]
             kpos = torch.arange(0, p0 + T, device=ids.device)[None, :]
-            s = s.masked_fill(kpos > qpos, float("-inf"))
+            hidden = kpos > qpos
+            if W is not None:  # sliding window: the keys at or below qpos - W are out
+                hidden = hidden | (kpos <= qpos - W)
+            s = s.masked_fill(hidden, float("-inf"))
         pr = torch.softmax(s, dim=-1)
         o = torch.matmul(pr, Vv).transpose(1, 2).reshape(B, T, nh * hd).to(dt)
         h = h + torch.matmul(o, w.wo.t()).float()
@@ -195,15 +219,17 @@ class DecodeGraph:
         scale = 1.0 / math.sqrt(cfg.head_dim)
         for i in range(cfg.num_layers):
             w = prov.layer(i)
+            W = _layer_window(cfg, i) or 0
+            wkw = {"window": W} if W else {}  # a global layer calls the kernels it always did
             if self.kind == "gqa":
                 ops.dec_norm_qkv_gqa(self.h, w.ln1, eng.eps, w.wqkv, cos_t, sin_t, self.pos, self.qb, cache.k[i],
                                      cache.v[i], cfg.num_heads, cfg.num_kv_heads)
                 ops.dec_attn_gqa(self.qb, cache.k[i], cache.v[i], self.pos, self.ob, scale, cfg.num_heads,
-                                 splits=self.kv_splits, ws=self.attn_ws)
+                                 splits=self.kv_splits, ws=self.attn_ws, **wkw)
             else:
                 ops.dec_norm_qkv(self.h, w.ln1, eng.eps, w.wqkv, cos_t, sin_t, self.pos, self.qb, cache.k[i],
                                  cache.v[i], cfg.num_heads)
-                ops.dec_attn(self.qb, cache.k[i], cache.v[i], self.pos, self.ob, scale)
+                ops.dec_attn(self.qb, cache.k[i], cache.v[i], self.pos, self.ob, scale, **wkw)
             ops.dec_gemv_res(self.ob, w.wo, self.h)
             ops.dec_norm_gu(self.h, w.ln2, eng.eps, w.wgu, self.sb)
             ops.dec_gemv_res(self.sb, w.wdown, self.h)
@@ -229,9 +255,13 @@ class DecodeGraph:
         hw = prov.head()
         h = hw.embed.index_select(0, self.ids.view(-1)).float().view(B, 1, -1)
         scale = 1.0 / math.sqrt(hd)
-        masked = (self.kpos > self.pos)[None, None, None, :]
+        masked_g = (self.kpos > self.pos)[None, None, None, :]
+        W = getattr(cfg, "sliding_window", None)
+        # the windowed layers' mask: also the keys at or below pos - W (pos stays on the device)
+        masked_w = masked_g if W is None else masked_g | (self.kpos <= self.pos - W)[None, None, None, :]
         for i in range(cfg.num_layers):
             w = prov.layer(i)
+            masked = masked_g if _layer_window(cfg, i) is None else masked_w
             n1 = _rms(h, w.ln1, eng.eps).to(dt)
             q, k, v = _split_qkv(torch.matmul(n1, w.wqkv.t()).float(), cfg)
             q, k = _qk_norm(q, k, w, eng.eps)
@@ -298,7 +328,9 @@ def _fused_kind(model, B: int) -> Optional[str]:
     fit one CU: the norm + GEMV kernels stage one normed bf16 row per batch entry
     (``dec_lds`` in decode.hip); ``k_dec_attn`` keeps all ``max_seq_len`` scores of a
     (batch, head) (maxS * 4 + 1056 B: max_seq_len <= ~40.7k), ``k_dec_attn_gqa`` the scores
-    of a group's query heads over one key chunk at the NS of :func:`_gqa_splits`."""
+    of a group's query heads over one key chunk at the NS of :func:`_gqa_splits`.  Where
+    every layer has a sliding window both hold ``min(W, max_seq_len)`` keys instead
+    (:func:`_attn_keys`); a model with global layers needs what those need."""
     ops = model.engine.ops
     cfg = model.config
     if getattr(cfg, "qk_norm", False):  # no fused norm + QKV kernel applies q_norm / k_norm: the ATen step does
@@ -308,15 +340,16 @@ def _fused_kind(model, B: int) -> Optional[str]:
             and cfg.head_dim == 64 and norm_lds <= DEC_LDS_MAX
             and os.environ.get("DLT_DECODE_FUSED", "1") != "0"):
         return None
+    keys = _attn_keys(cfg)
     if cfg.num_kv_heads == cfg.num_heads:
-        attn_lds = cfg.max_seq_len * 4 + 8 * 4 + 4 * 64 * 4
+        attn_lds = keys * 4 + 8 * 4 + 4 * 64 * 4
         return "mha" if attn_lds <= DEC_LDS_MAX else None
     # the grouped-query kernels are bf16 only: an fp16 / fp32 engine keeps the ATen step it had
     if not hasattr(ops, "dec_attn_gqa") or getattr(model.engine, "act_dtype", torch.bfloat16) != torch.bfloat16:
         return None
     from ..ops.hip import dec_attn_chunk, dec_attn_gqa_lds
     G = cfg.num_heads // cfg.num_kv_heads
-    lds = dec_attn_gqa_lds(G, dec_attn_chunk(cfg.max_seq_len, _gqa_splits(cfg, B)))
+    lds = dec_attn_gqa_lds(G, dec_attn_chunk(keys, _gqa_splits(cfg, B)))
     return "gqa" if lds <= DEC_LDS_MAX else None
 
 

@@ -24,11 +24,13 @@ def pick_device(name: str) -> torch.device:
     return torch.device("cuda" if torch.cuda.is_available() else "cpu")
 
 
-def load_model(path: str, model_size: str = None, device="cpu", num_kv_heads: int = None, qk_norm: bool = None):
+def load_model(path: str, model_size: str = None, device="cpu", num_kv_heads: int = None, qk_norm: bool = None,
+               sliding_window: int = None, sliding_window_pattern: int = None):
     """The model of a checkpoint: built from the checkpoint's own config (which carries
     num_kv_heads for a grouped-query model) unless ``model_size`` names a preset;
     ``num_kv_heads`` overrides either, and so does ``qk_norm`` (the checkpoint's config carries
-    it for a QK-norm model)."""
+    it for a QK-norm model), ``sliding_window`` and ``sliding_window_pattern`` (a windowed model's
+    config carries them too)."""
     ckpt = load_checkpoint(path, map_location="cpu")
     cfg = ckpt.get("model_config")
     if model_size is not None or not isinstance(cfg, GPTConfig):
@@ -37,6 +39,10 @@ def load_model(path: str, model_size: str = None, device="cpu", num_kv_heads: in
         cfg = GPTConfig.from_dict({**cfg.to_dict(), "num_kv_heads": num_kv_heads})
     if qk_norm is not None:
         cfg = GPTConfig.from_dict({**cfg.to_dict(), "qk_norm": bool(qk_norm)})
+    if sliding_window is not None:
+        cfg = GPTConfig.from_dict({**cfg.to_dict(), "sliding_window": sliding_window})
+    if sliding_window_pattern is not None:
+        cfg = GPTConfig.from_dict({**cfg.to_dict(), "sliding_window_pattern": sliding_window_pattern})
     model = GPT(cfg)
     load_model_state(model, ckpt["model"])
     model = model.to(device)
@@ -61,11 +67,16 @@ def main(argv=None):
                    help="key/value heads of a grouped-query checkpoint whose config does not carry them")
     p.add_argument("--qk_norm", action="store_true", default=None,
                    help="the checkpoint is a QK-norm model (q_norm / k_norm weights) whose config does not say so")
+    p.add_argument("--sliding_window", type=int, default=None, metavar="W",
+                   help="window of a sliding-window checkpoint whose config does not carry it")
+    p.add_argument("--sliding_window_pattern", type=int, default=None, metavar="N",
+                   help="every N-th layer of that checkpoint is global (plain causal)")
     args = p.parse_args(argv)
     if args.seed is not None:
         torch.manual_seed(args.seed)
     dev = pick_device(args.device)
-    model = load_model(args.checkpoint, args.model_size, dev, args.num_kv_heads, args.qk_norm)
+    model = load_model(args.checkpoint, args.model_size, dev, args.num_kv_heads, args.qk_norm, args.sliding_window,
+                       args.sliding_window_pattern)
     tok = get_tokenizer(args.tokenizer)
     ids = torch.tensor([tok.encode(args.prompt)], dtype=torch.long, device=dev)
     out = model.generate(ids, max_new_tokens=args.max_new_tokens, temperature=args.temperature, top_k=args.top_k)

@@ -56,6 +56,12 @@ class GPTConfig:
     # the query heads (q_norm) and one for the key heads (k_norm), applied before RoPE.
     qk_norm: bool = False
 
+    # Sliding-window (local) attention: query q sees key k iff q - W < k <= q, W keys with its
+    # own (the Mistral / Gemma rule).  With sliding_window_pattern = N, layer i (0-based) is
+    # global (plain causal) iff (i + 1) % N == 0 (Gemma-3's rule); unset, every layer is windowed.
+    sliding_window: Optional[int] = None
+    sliding_window_pattern: Optional[int] = None
+
     def __post_init__(self) -> None:
         if self.intermediate_size is None:
             self.intermediate_size = 4 * self.hidden_size
@@ -68,6 +74,18 @@ class GPTConfig:
             raise ValueError(
                 f"num_kv_heads ({self.num_kv_heads}) must divide num_heads ({self.num_heads})")
         self.qk_norm = bool(self.qk_norm)
+        if self.sliding_window is not None:
+            if isinstance(self.sliding_window, bool) or int(self.sliding_window) != self.sliding_window \
+                    or self.sliding_window < 1:
+                raise ValueError(f"sliding_window ({self.sliding_window!r}) must be an integer >= 1")
+            self.sliding_window = int(self.sliding_window)
+        if self.sliding_window_pattern is not None:
+            n = self.sliding_window_pattern
+            if self.sliding_window is None:
+                raise ValueError("sliding_window_pattern needs sliding_window")
+            if isinstance(n, bool) or int(n) != n or n < 2:
+                raise ValueError(f"sliding_window_pattern ({n!r}) must be an integer >= 2")
+            self.sliding_window_pattern = int(n)
 
     # ------------------------------------------------------------------ presets
     @classmethod
@@ -113,6 +131,18 @@ class GPTConfig:
         """Width of the K (and of the V) projection: num_kv_heads * head_dim."""
         return self.num_kv_heads * self.head_dim
 
+    def layer_window(self, i: int) -> Optional[int]:
+        """Window of layer ``i`` (0-based), or None when that layer is global (plain causal).
+
+        The one place that decides which layers are windowed."""
+        w = self.__dict__.get("sliding_window")
+        if w is None:
+            return None
+        n = self.__dict__.get("sliding_window_pattern")
+        if n is not None and (i + 1) % n == 0:
+            return None
+        return w
+
     def num_parameters(self) -> int:
         """True trainable parameter count (tied embedding counted once)."""
         h, i = self.hidden_size, self.intermediate_size
@@ -132,12 +162,23 @@ class GPTConfig:
                         recompute: bool = False) -> float:
         """Training FLOPs per token (fwd + bwd = 3x fwd; +1 fwd with recompute).
 
-        Attention score/value FLOPs are counted for the causal half when ``causal``.
+        Attention score/value FLOPs are counted for the causal half when ``causal``; a windowed
+        layer counts the ``W*(2S-W+1)/(2S)`` keys a query sees on average instead of ``(S+1)/2``.
         """
         s = seq_len or self.max_seq_len
         h, i, L, v = self.hidden_size, self.intermediate_size, self.num_layers, self.vocab_size
         dense = 2 * (2 * h * h + 2 * self.kv_size * h + 3 * h * i) * L + 2 * h * v
         attn = 2 * 2 * s * h * L * (0.5 if causal else 1.0)
+        if causal and self.sliding_window is not None:
+            attn = 0.0
+            for li in range(L):
+                w = self.layer_window(li)
+                if w is None:  # a global layer of a pattern model: the causal half, as above
+                    keys = 0.5 * s
+                else:  # sum_q min(q + 1, W) / S
+                    w = min(w, s)
+                    keys = w * (2 * s - w + 1) / (2.0 * s)
+                attn += 2 * 2 * h * keys
         fwd = dense + attn
         return fwd * (4.0 if recompute else 3.0)
 
@@ -148,6 +189,9 @@ class GPTConfig:
             del d["num_kv_heads"]
         if not self.qk_norm:  # ... and so do configs without QK-norm
             del d["qk_norm"]
+        for k in ("sliding_window", "sliding_window_pattern"):  # ... and unwindowed ones
+            if d[k] is None:
+                del d[k]
         return d
 
     # Pickled configs (checkpoints) follow to_dict(): an MHA config carries no num_kv_heads and
@@ -159,6 +203,9 @@ class GPTConfig:
             state.pop("num_kv_heads", None)
         if not state.get("qk_norm"):
             state.pop("qk_norm", None)
+        for k in ("sliding_window", "sliding_window_pattern"):
+            if state.get(k) is None:
+                state.pop(k, None)
         return state
 
     def __setstate__(self, state: Dict[str, Any]) -> None:
@@ -166,6 +213,8 @@ class GPTConfig:
         if self.__dict__.get("num_kv_heads") is None:
             self.num_kv_heads = self.num_heads
         self.qk_norm = bool(self.__dict__.get("qk_norm", False))
+        self.__dict__.setdefault("sliding_window", None)
+        self.__dict__.setdefault("sliding_window_pattern", None)
 
     @classmethod
     def from_dict(cls, d: Dict[str, Any]) -> "GPTConfig":

@@ -48,7 +48,7 @@ from __future__ import annotations
 import contextlib
 import os
 from dataclasses import dataclass, field
-from typing import Any, Callable, List, Optional
+from typing import Any, Callable, Dict, List, Optional
 
 import torch
 
@@ -174,6 +174,7 @@ class _StepState:
     head_acc: Any = None  # chunked head: this micro-step's fp32 lm_head weight gradient
     d_last: Any = None  # bf16 d of last layer (input of final norm)
     doc: Any = None     # document mask bounds (lo, hi) of ids, or None (set_doc_separator)
+    win: Any = None     # bounds of the windowed layers: window_bounds merged with doc, or None
 
 
 class GPTEngine:
@@ -300,6 +301,9 @@ class GPTEngine:
         self.attn_mask_budget = float(os.environ.get("DLT_ATTN_MASK_BUDGET_GB", "32")) * 1e9
         # intra-document attention mask of packed sequences (set_doc_separator): None = off
         self.doc_sep_token: Optional[int] = None
+        # sliding-window layers (cfg.layer_window): their bounds without a separator depend on
+        # (B, S, W, device) only and are built once
+        self._win_cache: Dict[Any, Any] = {}
 
     def set_doc_separator(self, token_id: Optional[int]) -> None:
         """Mask attention inside documents: ``token_id`` ends a document (and belongs to
@@ -449,7 +453,31 @@ class GPTEngine:
                 rng.site_key(self.seed, micro, layer, rng.SITE_MLP))
 
     # ---------------------------------------------------------------- forward
-    def _attn_mask_async(self, B, S, p, key, dev):
+    def _window_bounds(self, st: "_StepState", dev):
+        """``st.win`` of a chain: the bounds of the windowed layers, merged with ``st.doc``
+        (one maximum / minimum per chain); None when the model has no window or it covers the
+        batch (W >= S: those layers then take the plain path, bit for bit)."""
+        W = getattr(self.cfg, "sliding_window", None)
+        if W is None or W >= st.S:
+            return None
+        if st.doc is not None:
+            return self.ops.window_bounds(st.B, st.S, W, dev, doc=st.doc)
+        k = (st.B, st.S, W, str(dev))
+        if k not in self._win_cache:
+            self._win_cache[k] = self.ops.window_bounds(st.B, st.S, W, dev)
+        return self._win_cache[k]
+
+    def _attn_bounds_kw(self, st: "_StepState", i: int) -> Dict[str, Any]:
+        """``doc=`` (and ``window=``) of layer ``i``'s attention forward and backward: a
+        windowed layer gets ``st.win`` and its window (the ops then make banded keep bits), a
+        global one ``st.doc``."""
+        if st.win is not None:
+            W = self.cfg.layer_window(i)
+            if W is not None:
+                return {"doc": st.win, "window": W}
+        return {"doc": st.doc} if st.doc is not None else {}
+
+    def _attn_mask_async(self, B, S, p, key, dev, window=None):
         """(mask, ready-event) built on a side stream (opt-in, ``DLT_MASK_STREAM=1``), or
         (None, None) to let the attention launch build it inline.  Measured neutral on
         the headline config (the GPU is saturated either way), so off by default."""
@@ -462,7 +490,8 @@ class GPTEngine:
         # allocated from the side stream's own pool: no wait on main needed, so the
         # masks of later layers can be produced while earlier layers still compute
         with torch.cuda.stream(self._mask_side):
-            mask = self.ops.attention_dropout_mask(B, self.cfg.num_heads, S, p, key, device=dev)
+            wkw = {"window": window} if window is not None else {}
+            mask = self.ops.attention_dropout_mask(B, self.cfg.num_heads, S, p, key, device=dev, **wkw)
             ev = torch.cuda.Event()
             ev.record()
         mask.record_stream(main)
@@ -521,7 +550,8 @@ class GPTEngine:
         sb = lambda name, n: self._sb(st, i, name, M, n, dv)  # noqa: E731
         # attention keep-bits depend only on the RNG key: build them on a side stream
         # so the VALU-only hashing overlaps the norm + QKV GEMM + RoPE below
-        mask, mask_ev = self._attn_mask_async(B, S, pa, k_attn, dv)
+        bkw = self._attn_bounds_kw(st, i)
+        mask, mask_ev = self._attn_mask_async(B, S, pa, k_attn, dv, bkw.get("window"))
         x, n1, rstd1 = ops.add_dropout_rmsnorm_fwd(r, d, w.ln1, self.eps, p_d, key_d, self.act_dtype,
                                                    y_out=sb("n1", H))
         fused_rope = self.packed_qkv and hasattr(gm, "linear_rope") and not self.gqa and not self.qk_norm
@@ -532,8 +562,7 @@ class GPTEngine:
         if mask is not None:
             torch.cuda.current_stream().wait_event(mask_ev)
         kw = {"mask": mask} if mask is not None else {}
-        if st.doc is not None:
-            kw["doc"] = st.doc
+        kw.update(bkw)
         if pa > 0.0 and getattr(ops, "backend", "") == "hip" and getattr(ops, "attn_backend", "hip") in ("hip", "gemm"):
             # keep this layer's keep bits for the backward only within the memory budget.
             # The masks (two layouts, 1 bit per causal score: 8 * B * nh * S * ceil(S/32) B)
@@ -699,6 +728,7 @@ class GPTEngine:
         st = _StepState(ids=ids, B=B, S=S, micro=micro, train=train, recompute=recompute)
         if self.doc_sep_token is not None:  # once per chain, on this chain's stream
             st.doc = self.ops.doc_bounds(ids, self.doc_sep_token)
+        st.win = self._window_bounds(st, ids.device)
         slot, n_slots, defer = acc if acc is not None else (self.acc_slot, self.acc_slots, self.defer)
         if need_bwd and defer:
             st.slot, st.defer, st.last = slot, True, slot == n_slots - 1
@@ -1099,7 +1129,7 @@ class GPTEngine:
                                       ddelta_out=sb(i, "da", H))
             del dn2
             # attention
-            dkw = {"doc": st.doc} if st.doc is not None else {}
+            dkw = self._attn_bounds_kw(st, i)
             do = gm.linear_dgrad(da, w.wo)
             if c.k is None:  # packed: dq/dk/dv land in [M, 3H] with the inverse RoPE applied
                 dqkv = ops.attention_bwd_packed(c.q, c.o, do, c.lse, pa, k_attn, B, S, cfg.num_heads, cos, sin,

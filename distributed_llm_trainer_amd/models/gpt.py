@@ -79,9 +79,12 @@ def apply_rotary_pos_emb(q, k, cos, sin):
 
 
 class CausalSelfAttention(nn.Module):
-    def __init__(self, config: GPTConfig):
+    def __init__(self, config: GPTConfig, window: Optional[int] = None):
         super().__init__()
         self.config = config
+        # sliding-window attention (config.layer_window of this layer): query q sees the keys
+        # q - window < k <= q; None: plain causal
+        self.window = window
         self.num_heads = config.num_heads
         self.head_dim = config.hidden_size // config.num_heads
         # grouped-query attention: num_kv_heads K/V heads, each shared by a group of
@@ -121,6 +124,10 @@ class CausalSelfAttention(nn.Module):
             G = self.num_heads // self.num_kv_heads
             k = k.repeat_interleave(G, dim=1)
             v = v.repeat_interleave(G, dim=1)
+        if self.window is not None and self.window < S:  # keys k <= q - W are out of the window
+            pos = torch.arange(S, device=hidden_states.device)
+            out_of_window = (pos[None, :] <= pos[:, None] - self.window)[None, None]
+            doc_hidden = out_of_window if doc_hidden is None else doc_hidden | out_of_window
         if self.use_flash and doc_hidden is not None:
             causal = torch.tril(torch.ones(S, S, device=hidden_states.device, dtype=torch.bool))
             out = F.scaled_dot_product_attention(
@@ -160,7 +167,7 @@ class TransformerBlock(nn.Module):
         super().__init__()
         self.layer_idx = layer_idx
         self.input_layernorm = RMSNorm(config.hidden_size)
-        self.attention = CausalSelfAttention(config)
+        self.attention = CausalSelfAttention(config, config.layer_window(layer_idx))
         self.post_attention_layernorm = RMSNorm(config.hidden_size)
         self.mlp = MLP(config)
 
@@ -237,6 +244,8 @@ class GPT(nn.Module):
             ops_mod.check_gqa(dev, self.config.head_dim, act_dtype)  # before anything is re-homed
         if self.config.qk_norm and (ops is None or ops.backend == "hip"):
             ops_mod.check_qk_norm(dev, self.config.head_dim, act_dtype)
+        if self.config.sliding_window is not None and (ops is None or ops.backend == "hip"):
+            ops_mod.check_sliding_window(dev, self.config.head_dim, act_dtype)
         if provider is None:
             from ..parallel.flat import FlatParamStore
             provider = FlatParamStore(self, dev, compute_dtype=compute_dtype)

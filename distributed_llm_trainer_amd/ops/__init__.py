@@ -17,7 +17,7 @@ _FUNCS = ("rope_tables", "embedding_fwd", "embedding_bwd", "add_dropout_rmsnorm_
           "rope_qkv_fwd", "rope_qkv_bwd", "attention_fwd", "attention_bwd", "swiglu_fwd", "swiglu_bwd",
           "cross_entropy_fwd_bwd", "scale_bf16", "rope_qk_inplace", "attention_fwd_packed",
           "attention_bwd_packed", "lmhead_loss", "lmhead_loss_fits", "doc_bounds", "qknorm_rope_inplace",
-          "qknorm_bwd")
+          "qknorm_bwd", "window_bounds")
 
 
 def _namespace(mod, name):
@@ -65,6 +65,24 @@ def check_doc_mask(device, head_dim: int = 64, act_dtype=torch.bfloat16) -> None
     if act_dtype == torch.float32:
         from . import hip_f32
         hip_f32._no_doc(True)
+
+
+def check_sliding_window(device, head_dim: int = 64, act_dtype=torch.bfloat16) -> None:
+    """Raises NotImplementedError when the attention route :func:`for_device` picks for this
+    model has no sliding window (``GPTConfig.sliding_window``).  The window runs on the DOC
+    forms of the 16-bit flash kernels, so the routes are :func:`check_doc_mask`'s: head_dim
+    64 / 128 and smaller heads zero-padded onto them pass; the GEMM-formulated route
+    (head_dim above 128) and the fp32 routes raise.  Called when the engine is enabled, so
+    the error comes before the first step, not inside it."""
+    if torch.device(device).type != "cuda" or os.environ.get("DLT_ALLOW_REFERENCE_ON_GPU") == "1":
+        return
+    from . import attn_gemm
+    from .hip import ATTN_HEAD_DIMS
+    if head_dim not in ATTN_HEAD_DIMS:  # names the padded / GEMM route it would take
+        attn_gemm.check_window(act_dtype, head_dim, True)
+    if act_dtype == torch.float32:
+        from . import hip_f32
+        hip_f32._no_window()
 
 
 def check_gqa(device, head_dim: int = 64, act_dtype=torch.bfloat16) -> None:

@@ -304,8 +304,29 @@ def check_doc(dtype, hd: int, doc) -> None:
         f"(head_dim {hd}, {dtype}); use bf16 or fp16 activations with head_dim <= 128")
 
 
-def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=True, doc=None):
+def check_window(dtype, hd: int, window) -> None:
+    """Sliding-window attention takes the routes the document mask takes (it runs on the same
+    DOC kernels): zero-padded 16-bit heads pass, every other route here raises."""
+    if window is None or (dtype in _HK and pad_dim(dtype, hd)):
+        return
+    raise NotImplementedError(
+        f"sliding-window attention (sliding_window) is not implemented on the {doc_route(dtype, hd)} route "
+        f"(head_dim {hd}, {dtype}); use bf16 or fp16 activations with head_dim <= 128")
+
+
+def _fold_window(window, doc, B, S, dtype, hd, device):
+    """``window=`` of the entry points folded into the bounds the padded flash kernels take
+    (their keep bits stay the full ones: a superset of what the window reads)."""
+    if window is None:
+        return doc
+    check_window(dtype, hd, window)
+    from . import hip
+    return hip._window_doc(window, doc, B, S, device, "attn")[1]
+
+
+def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=True, doc=None, window=None):
     hd = qkv.shape[1] // (3 * nh)
+    doc = _fold_window(window, doc, B, S, qkv.dtype, hd, qkv.device)
     check_doc(qkv.dtype, hd, doc)
     Dp = pad_dim(qkv.dtype, hd)
     H, ld = nh * hd, qkv.stride(0)
@@ -325,8 +346,9 @@ def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=
     return _narrow(o32, qkv.dtype, out), aux
 
 
-def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, doc=None):
+def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, doc=None, window=None):
     hd = qkv.shape[1] // (3 * nh)
+    doc = _fold_window(window, doc, B, S, qkv.dtype, hd, qkv.device)
     check_doc(qkv.dtype, hd, doc)
     Dp = pad_dim(qkv.dtype, hd)
     H, ld = nh * hd, qkv.stride(0)
@@ -354,10 +376,11 @@ def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, 
     return _narrow(hip_f32.rope_qkv_bwd(dq, dk, dv, cos, sin, out=o32), qkv.dtype, out)
 
 
-def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=None, doc=None):
+def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=None, doc=None, window=None):
     if not causal:
         raise NotImplementedError("only causal attention is implemented (the model is a causal LM)")
     B, nh, S, hd = q.shape
+    doc = _fold_window(window, doc, B, S, q.dtype, hd, q.device)
     check_doc(q.dtype, hd, doc)
     Dp = pad_dim(q.dtype, hd)
     hm = (nh * S * hd, hd, S * hd)
@@ -376,8 +399,9 @@ def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=
     return _narrow(o32, q.dtype, out), aux
 
 
-def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, doc=None):
+def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, doc=None, window=None):
     B, nh, S, hd = q.shape
+    doc = _fold_window(window, doc, B, S, q.dtype, hd, q.device)
     check_doc(q.dtype, hd, doc)
     Dp = pad_dim(q.dtype, hd)
     hm = (nh * S * hd, hd, S * hd)

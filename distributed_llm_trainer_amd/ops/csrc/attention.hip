@@ -327,20 +327,40 @@ __device__ __forceinline__ uint32_t bt_stage(uint32_t col, int l) {
   return (col & keep) | (r & ~keep);
 }
 
+// BAND (sliding-window layers): only the tiles a window can read.  The MFMA kernels walk
+// 64-row items over 64-wide tiles (doc_q_range / doc_k_range with lo[q] = max(0, q - W + 1),
+// hi[k] = min(S - 1, k + W - 1)): the item of query block qb starts at K/V tile qb - D, the
+// item of key block kb ends at Q tile kb + D, D = ceil((W - 1) / 64).  Both read the bit tile
+// (r, w) iff r/2 - w/2 <= D, so band r holds the words r - j, j = 0 .. 2D + 1, less the one
+// that falls outside for an even r: a rectangle of 2D + 2 slots per band, tile -> (r, j) by
+// one division.  Tiles outside the band are left as they were; same bits, same layout.
+// The kernel never read its third argument (B * nh is the grid's y extent): the BAND form
+// takes D there, so the full form's arguments, and with them its code, are what they were.
+template <bool BAND = false>
 __global__ __launch_bounds__(256) void k_dropout_bits(uint32_t* __restrict__ mask, uint32_t* __restrict__ maskT,
-                                                      int BH, int S, uint32_t key, uint32_t thr) {
+                                                      int BH_or_D, int S, uint32_t key, uint32_t thr) {
   const int W = (S + 31) >> 5;  // words per row == number of 32-row bands
   const int bh = blockIdx.y;
   const int lane = threadIdx.x & 63, l = lane & 31;
   const int tile = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + (lane >> 5);  // one tile per half-wave
-  const int ntiles = W * (W + 1) / 2;
-  const bool active = tile < ntiles;
-  // tile -> (band r, word w <= r): band r starts at tile r(r+1)/2; the float root is
-  // within one of r for any realistic S, corrected once each way without loops
-  int r = (int)((sqrtf(8.f * (float)tile + 1.f) - 1.f) * 0.5f);
-  r += ((r + 1) * (r + 2) / 2 <= tile) ? 1 : 0;
-  r -= (r * (r + 1) / 2 > tile) ? 1 : 0;
-  const int w = tile - r * (r + 1) / 2;
+  bool active;
+  int r, w;
+  if constexpr (BAND) {
+    const int D = BH_or_D, nb = 2 * D + 2;
+    r = tile / nb;
+    w = r - (tile - r * nb);
+    active = r < W && w >= 0 && (r >> 1) - (w >> 1) <= D;
+    w = max(w, 0);
+  } else {
+    const int ntiles = W * (W + 1) / 2;
+    active = tile < ntiles;
+    // tile -> (band r, word w <= r): band r starts at tile r(r+1)/2; the float root is
+    // within one of r for any realistic S, corrected once each way without loops
+    r = (int)((sqrtf(8.f * (float)tile + 1.f) - 1.f) * 0.5f);
+    r += ((r + 1) * (r + 2) / 2 <= tile) ? 1 : 0;
+    r -= (r * (r + 1) / 2 > tile) ? 1 : 0;
+    w = tile - r * (r + 1) / 2;
+  }
   const int q = r * 32 + l;
   const uint32_t kbh = lowbias32(key + (uint32_t)bh * 0x9E3779B9u);
   uint32_t word = 0;
@@ -1460,7 +1480,22 @@ DLT_API int dlt_attn_dropout_mask(uint32_t* mask, int B, int nh, int S, uint32_t
   const int W = (S + 31) / 32;
   const int ntiles = W * (W + 1) / 2;  // 8 tiles (2 per wave) per block
   uint32_t* maskT = mask + (size_t)B * nh * S * W;
-  k_dropout_bits<<<dim3((ntiles + 7) / 8, B * nh), 256, 0, st>>>(mask, maskT, B * nh, S, key, thr);
+  k_dropout_bits<><<<dim3((ntiles + 7) / 8, B * nh), 256, 0, st>>>(mask, maskT, B * nh, S, key, thr);
+  DLT_CHECK_LAUNCH();
+}
+
+// The keep bits a sliding-window layer of `window` keys reads (k_dropout_bits<true>): the same
+// buffer and the same bits as dlt_attn_dropout_mask inside the band, nothing written outside
+// it.  A band that covers the causal triangle takes the full kernel.
+DLT_API int dlt_attn_dropout_mask_band(uint32_t* mask, int B, int nh, int S, uint32_t key, uint32_t thr, int window,
+                                       hipStream_t st) {
+  if (S <= 0 || !mask || !thr || window < 1) return -1;
+  const int W = (S + 31) / 32;
+  const int D = (int)(((long)window - 1 + 63) / 64 < (long)W ? ((long)window - 1 + 63) / 64 : (long)W);
+  if (2 * D + 2 >= W + 1) return dlt_attn_dropout_mask(mask, B, nh, S, key, thr, st);
+  const long ntiles = (long)W * (2 * D + 2);
+  uint32_t* maskT = mask + (size_t)B * nh * S * W;
+  k_dropout_bits<true><<<dim3((unsigned)((ntiles + 7) / 8), B * nh), 256, 0, st>>>(mask, maskT, D, S, key, thr);
   DLT_CHECK_LAUNCH();
 }
 

@@ -235,19 +235,26 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_norm_qkv(const float* __restrict
 // grid (B * nh): one (b, head).  q [B, H] bf16 (head-major 64-blocks), caches [B, nh, maxS, 64].
 // Scores in fp32 (lane = key), softmax over keys 0..pos, then o (lane = dim) summed across
 // the 4 waves in LDS.
+// WIN (sliding window of `win` keys): the keys are kf..pos, kf = max(0, pos - win + 1); K, V
+// and the score index start at kf, so sc[] holds min(win, maxS) scores and the code below
+// the prologue is the same.
+template <bool WIN = false>
 __global__ __launch_bounds__(DEC_NT) void k_dec_attn(const bf16_t* __restrict__ q, const bf16_t* __restrict__ kc,
                                                      const bf16_t* __restrict__ vc, const long* __restrict__ posp,
-                                                     bf16_t* __restrict__ o, int H, int nh, int maxS, float scale) {
+                                                     bf16_t* __restrict__ o, int H, int nh, int maxS, float scale,
+                                                     int win = 0) {
   extern __shared__ __attribute__((aligned(16))) char dsm[];
-  float* sc = reinterpret_cast<float*>(dsm);       // [maxS] scores -> probabilities
-  float* red = sc + maxS;                          // [8]
+  float* sc = reinterpret_cast<float*>(dsm);       // [maxS] scores -> probabilities (WIN: [min(win, maxS)])
+  float* red = sc + (WIN ? min(win, maxS) : maxS); // [8]
   float* oacc = red + 8;                           // [4][64]
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int b = blockIdx.x / nh, head = blockIdx.x % nh;
   DLT_DASSERT(posp[0] >= 0 && posp[0] < maxS);
-  const int len = (int)(posp[0] < maxS ? posp[0] + 1 : maxS);  // sc[] holds maxS scores
-  const bf16_t* K = kc + ((size_t)b * nh + head) * maxS * 64;
-  const bf16_t* V = vc + ((size_t)b * nh + head) * maxS * 64;
+  const int end = (int)(posp[0] < maxS ? posp[0] + 1 : maxS);  // sc[] holds maxS scores
+  const int kf = WIN ? max(0, end - max(win, 1)) : 0;          // first key; end - kf <= min(win, maxS)
+  const int len = end - kf;
+  const bf16_t* K = kc + (((size_t)b * nh + head) * maxS + kf) * 64;
+  const bf16_t* V = vc + (((size_t)b * nh + head) * maxS + kf) * 64;
   float qv[64];
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
@@ -329,11 +336,14 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_attn(const bf16_t* __restrict__ 
 constexpr int GQA_WS = 66;    // floats per partial: o[64], m, l
 constexpr int GQA_GMAX = 16;  // query heads per workgroup (128 accumulator registers)
 
-template <int GT>
+// WIN (sliding window of `win` keys): the chunks are anchored at the window's first key
+// kf = max(0, pos - win + 1): chunk s is [kf + s C, min(kf + (s + 1) C, pos + 1)) with C fixed on
+// the host from min(win, maxS), so a window shorter than maxS / NS still feeds every workgroup.
+template <int GT, bool WIN = false>
 __global__ __launch_bounds__(DEC_NT) void k_dec_attn_gqa(const bf16_t* __restrict__ q, const bf16_t* __restrict__ kc,
                                                          const bf16_t* __restrict__ vc, const long* __restrict__ posp,
                                                          bf16_t* __restrict__ o, float* __restrict__ ws, int H, int nh,
-                                                         int nkv, int maxS, int NS, int C, float scale) {
+                                                         int nkv, int maxS, int NS, int C, float scale, int win = 0) {
   extern __shared__ __attribute__((aligned(16))) char dsm[];
   float* red = reinterpret_cast<float*>(dsm);  // [2][4][GT] per-wave max, sum
   float* oacc = red + 8 * GT;                  // [4][GT][64]
@@ -351,8 +361,9 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_attn_gqa(const bf16_t* __restric
   const int h0 = kvh * G + sub * GT;     // first query head of this workgroup
   DLT_DASSERT(posp[0] >= 0 && posp[0] < maxS);
   const int len = (int)(posp[0] < maxS ? posp[0] + 1 : maxS);
-  const int lo = s * C, n = min(lo + C, len) - lo;  // n <= C keys of this chunk (<= 0: none)
-  if (n <= 0) {  // (uniform) only with NS > 1: chunk 0 always holds key 0
+  const int kf = WIN ? max(0, len - max(win, 1)) : 0;  // first key of the window
+  const int lo = kf + s * C, n = min(lo + C, len) - lo;  // n <= C keys of this chunk (<= 0: none)
+  if (n <= 0) {  // (uniform) only with NS > 1: chunk 0 always holds key kf
     if (tid < Gl) {
       float* w = ws + (((size_t)b * nh + h0 + tid) * NS + s) * GQA_WS;
       w[64] = -INFINITY;
@@ -1030,13 +1041,15 @@ static int dec_attn_chunk(int maxS, int NS) { return (maxS + NS - 1) / NS; }
 
 // q, o [B, nh * 64] bf16, caches [B, nkv, maxS, 64]; NS in {1, 2, 4, 8} key chunks per K/V
 // head; ws: fp32 [B, nh, NS, 66] (NS > 1).  Two launches on `st` for NS > 1, one otherwise.
-DLT_API int dlt_dec_attn_gqa(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const long* pos, bf16_t* o,
-                             float* ws, int B, int H, int nh, int nkv, int maxS, int NS, float scale,
-                             hipStream_t st) {
-  if (B < 1 || H != nh * 64 || nkv < 1 || nh % nkv || maxS < 1) return -1;
+// window > 0 (dlt_dec_attn_gqa_win): the keys are max(0, pos - window + 1)..pos and the chunks
+// divide min(window, maxS) keys, anchored at the window (k_dec_attn_gqa<GT, true>).
+static int dec_attn_gqa_launch(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const long* pos, bf16_t* o,
+                               float* ws, int B, int H, int nh, int nkv, int maxS, int NS, float scale, int window,
+                               hipStream_t st) {
+  if (B < 1 || H != nh * 64 || nkv < 1 || nh % nkv || maxS < 1 || window < 0) return -1;
   if ((NS != 1 && NS != 2 && NS != 4 && NS != 8) || (NS > 1 && !ws)) return -1;
   const int G = nh / nkv, Gw = G < GQA_GMAX ? G : GQA_GMAX, GS = (G + GQA_GMAX - 1) / GQA_GMAX;
-  const int C = dec_attn_chunk(maxS, NS);
+  const int C = dec_attn_chunk(window > 0 && window < maxS ? window : maxS, NS);
   const int gts[8] = {1, 2, 3, 4, 6, 8, 12, 16};
   int GT = 16;
   for (int i = 7; i >= 0; --i)
@@ -1046,7 +1059,11 @@ DLT_API int dlt_dec_attn_gqa(const bf16_t* q, const bf16_t* kc, const bf16_t* vc
   const int grid = B * nkv * GS * NS;
 #define L(GG)                                                                                                   \
   case GG:                                                                                                      \
-    k_dec_attn_gqa<GG><<<grid, DEC_NT, lds, st>>>(q, kc, vc, pos, o, ws, H, nh, nkv, maxS, NS, C, scale); \
+    if (window > 0)                                                                                             \
+      k_dec_attn_gqa<GG, true><<<grid, DEC_NT, lds, st>>>(q, kc, vc, pos, o, ws, H, nh, nkv, maxS, NS, C,      \
+                                                          scale, window);                                      \
+    else                                                                                                        \
+      k_dec_attn_gqa<GG><<<grid, DEC_NT, lds, st>>>(q, kc, vc, pos, o, ws, H, nh, nkv, maxS, NS, C, scale);     \
     break
   switch (GT) {
     L(1);
@@ -1063,11 +1080,35 @@ DLT_API int dlt_dec_attn_gqa(const bf16_t* q, const bf16_t* kc, const bf16_t* vc
   DLT_CHECK_LAUNCH();
 }
 
+DLT_API int dlt_dec_attn_gqa(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const long* pos, bf16_t* o,
+                             float* ws, int B, int H, int nh, int nkv, int maxS, int NS, float scale,
+                             hipStream_t st) {
+  return dec_attn_gqa_launch(q, kc, vc, pos, o, ws, B, H, nh, nkv, maxS, NS, scale, 0, st);
+}
+
+DLT_API int dlt_dec_attn_gqa_win(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const long* pos, bf16_t* o,
+                                 float* ws, int B, int H, int nh, int nkv, int maxS, int NS, float scale, int window,
+                                 hipStream_t st) {
+  if (window < 1) return -1;
+  return dec_attn_gqa_launch(q, kc, vc, pos, o, ws, B, H, nh, nkv, maxS, NS, scale, window, st);
+}
+
 DLT_API int dlt_dec_attn(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const long* pos, bf16_t* o, int B,
                          int H, int nh, int maxS, float scale, hipStream_t st) {
   const size_t lds = (size_t)maxS * 4 + 8 * 4 + 4 * 64 * 4;
   if (H != nh * 64 || lds > 160 * 1024) return -1;
-  k_dec_attn<<<B * nh, DEC_NT, lds, st>>>(q, kc, vc, pos, o, H, nh, maxS, scale);
+  k_dec_attn<><<<B * nh, DEC_NT, lds, st>>>(q, kc, vc, pos, o, H, nh, maxS, scale);
+  DLT_CHECK_LAUNCH();
+}
+
+// Sliding window of `window` >= 1 keys: the scores of keys max(0, pos - window + 1)..pos only,
+// min(window, maxS) * 4 + 1056 bytes of LDS.
+DLT_API int dlt_dec_attn_win(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const long* pos, bf16_t* o, int B,
+                             int H, int nh, int maxS, float scale, int window, hipStream_t st) {
+  if (window < 1 || maxS < 1 || B < 1) return -1;
+  const size_t lds = (size_t)(window < maxS ? window : maxS) * 4 + 8 * 4 + 4 * 64 * 4;
+  if (H != nh * 64 || lds > 160 * 1024) return -1;
+  k_dec_attn<true><<<B * nh, DEC_NT, lds, st>>>(q, kc, vc, pos, o, H, nh, maxS, scale, window);
   DLT_CHECK_LAUNCH();
 }
 

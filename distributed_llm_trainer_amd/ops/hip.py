@@ -81,6 +81,7 @@ _SIGS = {
     "dlt_attn_fwd": [c_void_p, c_void_p],
     "dlt_attn_bwd": [c_void_p, c_void_p],
     "dlt_attn_dropout_mask": [c_void_p, c_int, c_int, c_int, c_uint32, c_uint32, c_void_p],
+    "dlt_attn_dropout_mask_band": [c_void_p, c_int, c_int, c_int, c_uint32, c_uint32, c_int, c_void_p],
     "dlt_attn_args_size": [],
     "dlt_rope_qk_inplace": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "dlt_qknorm_rope_inplace": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int,
@@ -94,6 +95,10 @@ _SIGS = {
                              c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "dlt_dec_attn_gqa": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                          c_int, c_float, c_void_p],
+    "dlt_dec_attn_win": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int,
+                         c_void_p],
+    "dlt_dec_attn_gqa_win": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                             c_int, c_int, c_float, c_int, c_void_p],
     "dlt_dec_gemv_res": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "dlt_dec_norm_gu": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "dlt_dec_norm_head": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
@@ -163,11 +168,30 @@ def dec_norm_qkv(h, ln, eps, wqkv, cos, sin, pos, q_out, kc, vc, nh):
                                 _p(kc), _p(vc), B, H, nh, maxS, _stream()), "dec_norm_qkv")
 
 
-def dec_attn(q, kc, vc, pos, o_out, scale):
+def _dec_window(window, name: str) -> int:
+    """``window`` of the decode attention wrappers: 0 = none, W >= 1 = keys pos - W + 1 .. pos."""
+    if isinstance(window, bool) or not isinstance(window, int) or window < 0 or window > 0x7FFFFFFF:
+        raise ValueError(f"{name}: window must be an integer >= 0 (0: no window), got {window!r}")
+    return window
+
+
+def dec_attn(q, kc, vc, pos, o_out, scale, window=0):
+    """Decode attention of a multi-head model over keys 0..pos of the caches [B, nh, maxS, 64];
+    ``window`` = W > 0: over keys max(0, pos - W + 1)..pos only (a sliding-window layer)."""
+    window = _dec_window(window, "dec_attn")
     B, nh, maxS, hd = kc.shape
     H = nh * hd
     _req(q, torch.bfloat16, "dec.q", B * H)
     _req(o_out, torch.bfloat16, "dec.o", B * H)
+    if window:
+        if hd != 64 or vc.shape != kc.shape:
+            raise ValueError("dec_attn: caches must be [B, nh, maxS, 64]")
+        _req(kc, torch.bfloat16, "dec.k_cache")
+        _req(vc, torch.bfloat16, "dec.v_cache")
+        _req(pos, torch.int64, "dec.pos", 1)
+        _chk(lib().dlt_dec_attn_win(_p(q), _p(kc), _p(vc), _p(pos), _p(o_out), B, H, nh, maxS, float(scale), window,
+                                    _stream()), "dec_attn_win")
+        return
     _chk(lib().dlt_dec_attn(_p(q), _p(kc), _p(vc), _p(pos), _p(o_out), B, H, nh, maxS, float(scale), _stream()),
          "dec_attn")
 
@@ -217,12 +241,14 @@ def dec_attn_gqa_workspace(B: int, nh: int, splits: int, device) -> torch.Tensor
     return torch.empty(B * nh * splits * DEC_ATTN_WS, dtype=torch.float32, device=device)
 
 
-def dec_attn_gqa(q, kc, vc, pos, o_out, scale, nh, splits=1, ws=None):
+def dec_attn_gqa(q, kc, vc, pos, o_out, scale, nh, splits=1, ws=None, window=0):
     """Decode attention of a grouped-query model: q, o_out [B, nh * 64] bf16, caches
     [B, nkv, maxS, 64]; every K/V row is read once for the nh / nkv query heads of its group.
     ``splits`` > 1 divides the keys over that many workgroups per K/V head (chunks of
     :func:`dec_attn_chunk`) and merges their partials, in order, through ``ws``
-    (:func:`dec_attn_gqa_workspace`)."""
+    (:func:`dec_attn_gqa_workspace`).  ``window`` = W > 0: keys max(0, pos - W + 1)..pos only,
+    in chunks of ``dec_attn_chunk(min(W, maxS), splits)`` anchored at the window's first key."""
+    window = _dec_window(window, "dec_attn_gqa")
     if kc.dim() != 4 or kc.shape[3] != 64 or vc.shape != kc.shape:
         raise ValueError("dec_attn_gqa: caches must be [B, nkv, maxS, 64]")
     B, nkv, maxS, _ = kc.shape
@@ -240,6 +266,11 @@ def dec_attn_gqa(q, kc, vc, pos, o_out, scale, nh, splits=1, ws=None):
         if ws is None:
             raise ValueError("dec_attn_gqa: splits > 1 needs a workspace (dec_attn_gqa_workspace)")
         _req(ws, torch.float32, "dec.attn_ws", B * nh * splits * DEC_ATTN_WS)
+    if window:
+        _chk(lib().dlt_dec_attn_gqa_win(_p(q), _p(kc), _p(vc), _p(pos), _p(o_out), _p(ws if splits > 1 else None), B,
+                                        H, nh, nkv, maxS, splits, float(scale), window, _stream()),
+             "dec_attn_gqa_win")
+        return
     _chk(lib().dlt_dec_attn_gqa(_p(q), _p(kc), _p(vc), _p(pos), _p(o_out), _p(ws if splits > 1 else None), B, H, nh,
                                 nkv, maxS, splits, float(scale), _stream()), "dec_attn_gqa")
 
@@ -681,15 +712,67 @@ class AttnAux(tuple):
 ATTN_HEAD_DIMS = (64, 128)
 
 
-def attention_dropout_mask(B, nh, S, p, key, device=None):
+def _req_window(window, name: str):
+    """``window`` of the attention wrappers: None, or W >= 1 keys per query with its own."""
+    if window is None:
+        return None
+    if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+        raise ValueError(f"{name}: window must be None or an integer >= 1, got {window!r}")
+    return min(window, 0x7FFFFFFF)
+
+
+def attention_dropout_mask(B, nh, S, p, key, device=None, window=None, out=None):
     """Keep-bit masks [2, B*nh, ceil(S/32), S] for attention dropout (None if p == 0).
-    Data-independent, so the engine builds them on a side stream ahead of time."""
+    Data-independent, so the engine builds them on a side stream ahead of time.  ``window``:
+    only the 32x32 bit tiles a sliding-window layer of that many keys reads are hashed and
+    written (the same bits, the same layout; the rest of the buffer is left as it is).
+    ``out``: write into this buffer instead of a new one."""
     thr = rng.keep_threshold(p)
     if not thr:
         return None
-    mask = torch.empty(2, B * nh, (S + 31) // 32, S, dtype=torch.int32, device=device)
-    _chk(lib().dlt_attn_dropout_mask(_p(mask), B, nh, S, key & 0xFFFFFFFF, thr, _stream()), "attn_dropout_mask")
+    window = _req_window(window, "attention_dropout_mask")
+    if out is None:
+        mask = torch.empty(2, B * nh, (S + 31) // 32, S, dtype=torch.int32, device=device)
+    else:
+        mask = out
+        _req(mask, torch.int32, "attn.mask", 2 * B * nh * S * ((S + 31) // 32))
+    if window is not None and window < S:
+        _chk(lib().dlt_attn_dropout_mask_band(_p(mask), B, nh, S, key & 0xFFFFFFFF, thr, window, _stream()),
+             "attn_dropout_mask_band")
+    else:
+        _chk(lib().dlt_attn_dropout_mask(_p(mask), B, nh, S, key & 0xFFFFFFFF, thr, _stream()), "attn_dropout_mask")
     return mask
+
+
+def window_bounds(B: int, S: int, W: int, device, doc=None):
+    """Bounds (lo, hi), int32 [B, S], of a sliding window of ``W`` keys, merged with the
+    document bounds ``doc`` when given -- see ``reference.window_bounds``.  Torch plumbing
+    over B*S ints, as :func:`doc_bounds` is."""
+    from .reference import window_bounds as wb
+    return wb(B, S, W, device, doc=doc)
+
+
+_WINDOW_BOUNDS = {}  # (B, S, W, device) -> bounds without a document mask: built once
+
+
+def _window_doc(window, doc, B: int, S: int, device, name: str):
+    """(window, doc) of an attention wrapper with ``window=``: the window folded into the
+    bounds the DOC kernels take.  A window that covers the sequence is no window."""
+    window = _req_window(window, name)
+    if window is None or window >= S:
+        return None, doc
+    from .reference import WindowBounds
+    if isinstance(doc, WindowBounds) and doc.window == window:  # folded in by the caller
+        return window, doc
+    if doc is not None:
+        _req_doc(doc, B, S, device, name)
+        return window, window_bounds(B, S, window, device, doc=doc)
+    k = (B, S, window, str(device))
+    if k not in _WINDOW_BOUNDS:
+        if len(_WINDOW_BOUNDS) >= 64:
+            _WINDOW_BOUNDS.clear()
+        _WINDOW_BOUNDS[k] = window_bounds(B, S, window, device)
+    return window, _WINDOW_BOUNDS[k]
 
 
 def doc_bounds(ids: torch.Tensor, sep: int):
@@ -752,28 +835,31 @@ class _AttnArgs(ctypes.Structure):
                    ("gen_mask", c_int), ("stride", _AttnStrides)])
 
 
-def _keep_bits_fwd(p, mask, B, nh, S, device):
+def _keep_bits_fwd(p, mask, B, nh, S, device, key=0, window=None):
     """(thr, dscale, mask, gen) of a forward: ``mask`` is the caller's keep bits (gen = 0), a new
-    buffer for the launcher to fill (gen = 1), or None without dropout."""
+    buffer for the launcher to fill (gen = 1), or None without dropout.  With ``window`` the new
+    buffer gets the banded bits here (gen = 2: filled, but this call's own)."""
     thr = rng.keep_threshold(p)
     if not thr:
         return 0, 1.0, None, 1
     if mask is not None:
         _req(mask, torch.int32, "attn.mask", 2 * B * nh * S * ((S + 31) // 32))
         return thr, 1.0 / (1.0 - p), mask, 0
+    if window is not None:
+        return thr, 1.0 / (1.0 - p), attention_dropout_mask(B, nh, S, p, key, device=device, window=window), 2
     # [0] row layout (lane = query), [1] transposed (lane = key) -- see attention.hip;
     # with store_mask=False it only lives for this call (the backward regenerates it)
     mask = torch.empty(2, B * nh, (S + 31) // 32, S, dtype=torch.int32, device=device)
     return thr, 1.0 / (1.0 - p), mask, 1
 
 
-def _keep_bits_bwd(p, key, mask, B, nh, S, device):
+def _keep_bits_bwd(p, key, mask, B, nh, S, device, window=None):
     """(thr, dscale, mask) of a backward; ``mask``: the forward's keep bits or None."""
     thr = rng.keep_threshold(p)
     if not thr:
         return 0, 1.0, None
     if mask is None:  # forward ran with store_mask=False: regenerate the keep bits only
-        mask = attention_dropout_mask(B, nh, S, p, key, device=device)
+        mask = attention_dropout_mask(B, nh, S, p, key, device=device, window=window)
     return thr, 1.0 / (1.0 - p), mask
 
 
@@ -800,7 +886,7 @@ def _attn_fwd_launch(name, src, o, lse, keep, key, lo, B, nh, nkv, S, hd, hk, sc
     (q, k, v), sq, skv = src
     thr, dscale, mask, gen = keep
     a = _AttnArgs(q=q, k=k, v=v, o=_p(o), lse=_p(lse), mask=_p(mask), lo=_p(lo), B=B, nh=nh, nkv=nkv or 0, S=S,
-                  hd=hd, hk=hk, scale=scale, dscale=dscale, key=key & 0xFFFFFFFF, thr=thr, gen_mask=gen,
+                  hd=hd, hk=hk, scale=scale, dscale=dscale, key=key & 0xFFFFFFFF, thr=thr, gen_mask=int(gen == 1),
                   stride=_AttnStrides(q=sq, kv=skv))
     _chk(lib().dlt_attn_fwd(ctypes.byref(a), _stream()), _attn_name(name, nkv, lo))
 
@@ -820,7 +906,7 @@ def _attn_bwd_launch(name, src, dst, o, do, lse, keep, doc, rope, B, nh, nkv, S,
 
 
 def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=None, scale=None, doc=None,
-                  nkv=None):
+                  nkv=None, window=None):
     """Returns (o [B*S, nh*hd] bf16, aux).  With dropout on, the keep bits are written
     to a bitmask consumed by attention_bwd (no re-hashing in the backward); pass
     ``mask`` from ``attention_dropout_mask`` to skip generating it here.  ``scale``:
@@ -828,10 +914,14 @@ def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=
     the unpadded head_dim's).  ``doc`` = (lo, hi) from :func:`doc_bounds`: the
     intra-document mask of packed sequences (DOC kernels of attention.hip).  Grouped-query
     attention: k, v [B, nkv, S, hd] with nkv dividing nh (or ``nkv=`` given: the GQA kernels
-    also for nkv == nh)."""
+    also for nkv == nh).  ``window`` = W: sliding-window attention, query q sees the keys
+    q - W < k <= q (of its document); it runs on the DOC kernels with the bounds of
+    :func:`window_bounds`, and keep bits made here are the banded ones."""
     nkv = _head_major_nkv(q, k, v, nkv, "attn")
     if q.dtype == torch.float32:
         from . import hip_f32
+        if window is not None:
+            hip_f32._no_window()
         if scale is not None:
             raise NotImplementedError("fp32 attention: the score scale is 1/sqrt(head_dim)")
         return hip_f32.attention_fwd(q, k, v, p, key, causal, store_mask=store_mask, out=out, mask=mask, doc=doc)
@@ -840,13 +930,14 @@ def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=
     B, nh, S, hd = q.shape
     for t, n, hh in ((q, "q", nh), (k, "k", nkv or nh), (v, "v", nkv or nh)):
         hk = _req_act(t, q.dtype, "attn." + n, B * hh * S * hd)
+    window, doc = _window_doc(window, doc, B, S, q.device, "attn")
     lo, _ = _req_doc(doc, B, S, q.device, "attn")
     if hd not in ATTN_HEAD_DIMS:
         raise NotImplementedError(f"attention kernels take head_dim {ATTN_HEAD_DIMS} (got {hd})")
     o = torch.empty(B * S, nh * hd, dtype=q.dtype, device=q.device) if out is None else out
     _req(o, q.dtype, "attn.o", B * S * nh * hd)
     lse = torch.empty(B, nh, S, dtype=torch.float32, device=q.device)
-    keep = _keep_bits_fwd(p, mask, B, nh, S, q.device)
+    keep = _keep_bits_fwd(p, mask, B, nh, S, q.device, key, window)
     sc = 1.0 / math.sqrt(hd) if scale is None else float(scale)
     _attn_fwd_launch("attn_fwd", _head_major(q, k, v), o, lse, keep, key, lo, B, nh, nkv, S, hd, hk, sc)
     return o, AttnAux((lse, keep[2] if (store_mask or not keep[3]) else None))
@@ -866,40 +957,48 @@ def _packed_dims(qkv, B, S, nh, nkv=None):
     return M, nh * hd, hd, nk * hd
 
 
-def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=True, doc=None, nkv=None):
+def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=True, doc=None, nkv=None,
+                         window=None):
     """Causal attention reading q/k/v straight from the packed (roped) [B*S, 3H] QKV.
     Returns (o [B*S, H] bf16, aux) like :func:`attention_fwd`.  With ``nkv`` (grouped-query
-    attention) the packed row is [H + 2*KV]; lse and the keep bits stay per query head."""
+    attention) the packed row is [H + 2*KV]; lse and the keep bits stay per query head.
+    ``window``: see :func:`attention_fwd`."""
     if qkv.dtype == torch.float32:
         if nkv is not None:
             _no_gqa_f32("attention_fwd_packed")
         from . import hip_f32
+        if window is not None:
+            hip_f32._no_window()
         return hip_f32.attention_fwd_packed(qkv, B, S, nh, p, key, out=out, mask=mask, store_mask=store_mask,
                                             doc=doc)
     M, H, hd, KV = _packed_dims(qkv, B, S, nh, nkv)
+    window, doc = _window_doc(window, doc, B, S, qkv.device, "attn")
     lo, _ = _req_doc(doc, B, S, qkv.device, "attn")
     o = torch.empty(M, H, dtype=qkv.dtype, device=qkv.device) if out is None else out
     _req(o, qkv.dtype, "attn.o", M * H)
     lse = torch.empty(B, nh, S, dtype=torch.float32, device=qkv.device)
-    keep = _keep_bits_fwd(p, mask, B, nh, S, qkv.device)
+    keep = _keep_bits_fwd(p, mask, B, nh, S, qkv.device, key, window)
     _attn_fwd_launch("attn_fwd_packed", _packed_row(qkv, S, H, hd, KV), o, lse, keep, key, lo, B, nh, nkv, S, hd,
                      _HK[qkv.dtype], 1.0 / math.sqrt(hd))
     return o, AttnAux((lse, keep[2] if (store_mask or not keep[3]) else None))
 
 
-def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, doc=None, nkv=None):
+def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, doc=None, nkv=None, window=None):
     """Backward of :func:`attention_fwd_packed` + the in-place RoPE: returns dqkv
     [B*S, 3H] (gradient w.r.t. the pre-rotation QKV GEMM output); dq/dk/dv are written
     into it by the attention kernels with the inverse rotation in their epilogue.  With
     ``nkv`` qkv and dqkv are [B*S, H + 2*KV]; dk / dv are summed over each group's query
-    heads in registers, in a fixed order."""
+    heads in registers, in a fixed order.  ``window``: the forward's."""
     if qkv.dtype == torch.float32:
         if nkv is not None:
             _no_gqa_f32("attention_bwd_packed")
         from . import hip_f32
+        if window is not None:
+            hip_f32._no_window()
         return hip_f32.attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=out, doc=doc)
     M, H, hd, KV = _packed_dims(qkv, B, S, nh, nkv)
     Wd = H + 2 * KV
+    window, doc = _window_doc(window, doc, B, S, qkv.device, "attn_bwd")
     lo, hi = _req_doc(doc, B, S, qkv.device, "attn_bwd")
     for t, nm in ((o, "o"), (do, "do")):
         _req(t, qkv.dtype, "attn_bwd." + nm, M * H)
@@ -909,7 +1008,7 @@ def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, 
         raise ValueError("rope tables too short")
     _req(cos, torch.float32, "attn_bwd.cos")
     _req(sin, torch.float32, "attn_bwd.sin")
-    keep = _keep_bits_bwd(p, key, mask, B, nh, S, qkv.device)
+    keep = _keep_bits_bwd(p, key, mask, B, nh, S, qkv.device, window)
     dqkv = torch.empty(M, Wd, dtype=qkv.dtype, device=qkv.device) if out is None else out
     _req(dqkv, qkv.dtype, "attn_bwd.dqkv", M * Wd)
     _attn_bwd_launch("attn_bwd_packed", _packed_row(qkv, S, H, hd, KV), _packed_row(dqkv, S, H, hd, KV), o, do, lse,
@@ -917,12 +1016,14 @@ def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, 
     return dqkv
 
 
-def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, scale=None, doc=None, nkv=None):
+def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, scale=None, doc=None, nkv=None, window=None):
     """Returns dq [B, nh, S, hd] and dk, dv in k's shape ([B, nkv, S, hd] under grouped-query
     attention, see :func:`attention_fwd`)."""
     nkv = _head_major_nkv(q, k, v, nkv, "attn_bwd")
     if q.dtype == torch.float32:
         from . import hip_f32
+        if window is not None:
+            hip_f32._no_window()
         if scale is not None:
             raise NotImplementedError("fp32 attention: the score scale is 1/sqrt(head_dim)")
         return hip_f32.attention_bwd(q, k, v, o, do, aux, p, key, causal, doc=doc)
@@ -931,10 +1032,11 @@ def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, scale=None, doc=None
     nk = B * (nkv or nh) * S * hd
     for t, nm, cnt in ((q, "q", n), (k, "k", nk), (v, "v", nk), (o, "o", n), (do, "do", n)):
         hk = _req_act(t, q.dtype, "attn_bwd." + nm, cnt)
+    window, doc = _window_doc(window, doc, B, S, q.device, "attn_bwd")
     lo, hi = _req_doc(doc, B, S, q.device, "attn_bwd")
     lse, mask = aux if isinstance(aux, tuple) else (aux, None)
     _req(lse, torch.float32, "attn_bwd.lse", B * nh * S)
-    keep = _keep_bits_bwd(p, key, mask, B, nh, S, q.device)
+    keep = _keep_bits_bwd(p, key, mask, B, nh, S, q.device, window)
     dq = torch.empty_like(q)
     dk = torch.empty_like(k)
     dv = torch.empty_like(v)

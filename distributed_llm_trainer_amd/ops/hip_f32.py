@@ -378,6 +378,14 @@ def _no_doc(doc) -> None:
             "(fp32 flash / fp32 GEMM formulation); use bf16 or fp16 activations with head_dim <= 128")
 
 
+def _no_window() -> None:
+    """Sliding-window attention runs on the DOC forms of the 16-bit flash kernels; the fp32
+    routes have none."""
+    raise NotImplementedError(
+        "sliding-window attention (sliding_window) is not implemented on the fp32 attention route "
+        "(fp32 flash / fp32 GEMM formulation); use bf16 or fp16 activations with head_dim <= 128")
+
+
 def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=None, doc=None):
     _no_doc(doc)
     if not causal:

@@ -213,17 +213,18 @@ def _split_packed(qkv, B, S, nh, nkv=None):
 
 
 def attention_fwd_packed(qkv: torch.Tensor, B: int, S: int, nh: int, p: float, key: int, out=None, mask=None,
-                         doc=None, nkv=None):
+                         doc=None, nkv=None, window=None):
     """Causal attention straight on the (already roped) packed [B*S, H + 2*KV] QKV."""
     q, k, v = _split_packed(qkv, B, S, nh, nkv)
-    return attention_fwd(q, k, v, p, key, True, out=out, doc=doc)
+    return attention_fwd(q, k, v, p, key, True, out=out, doc=doc, window=window)
 
 
 def attention_bwd_packed(qkv, o, do, lse, p: float, key: int, B: int, S: int, nh: int,
-                         cos: torch.Tensor, sin: torch.Tensor, out=None, doc=None, nkv=None) -> torch.Tensor:
+                         cos: torch.Tensor, sin: torch.Tensor, out=None, doc=None, nkv=None,
+                         window=None) -> torch.Tensor:
     """Backward of attention_fwd_packed + the in-place RoPE: dqkv [B*S, H + 2*KV] (pre-RoPE)."""
     q, k, v = _split_packed(qkv, B, S, nh, nkv)
-    dq, dk, dv = attention_bwd(q, k, v, o, do, lse, p, key, True, doc=doc)
+    dq, dk, dv = attention_bwd(q, k, v, o, do, lse, p, key, True, doc=doc, window=window)
     res = rope_qkv_bwd(dq.float(), dk.float(), dv.float(), cos, sin).to(qkv.dtype)
     if out is not None:
         out.copy_(res)
@@ -252,6 +253,48 @@ def doc_bounds(ids: torch.Tensor, sep: int) -> Tuple[torch.Tensor, torch.Tensor]
     at = torch.where(is_sep, pos, torch.full_like(pos, S - 1))
     hi = torch.cummin(at.flip(1), dim=1).values.flip(1)
     return lo.to(torch.int32).contiguous(), hi.to(torch.int32).contiguous()
+
+
+class WindowBounds(tuple):
+    """``(lo, hi)`` of :func:`window_bounds`, with the window they hold in ``.window``: an
+    attention op given these in ``doc=`` together with ``window=`` does not fold it in twice."""
+
+    def __new__(cls, lo, hi, window: int):
+        self = super().__new__(cls, (lo, hi))
+        self.window = int(window)
+        return self
+
+
+def window_bounds(B: int, S: int, W: int, device, doc=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Bounds of a sliding window of ``W`` >= 1 keys in the form of :func:`doc_bounds`: query q
+    sees key k iff q - W < k <= q, i.e. ``lo[q] = max(0, q - W + 1) <= k <= q``, which is the
+    same as ``k <= q <= hi[k] = min(S - 1, k + W - 1)``.  With ``doc`` = (lo, hi) the two masks
+    are merged (max of the lower, min of the upper bounds): both stay non-decreasing along S
+    and keep the lo / hi equivalence, so the DOC attention kernels take them as they are.
+    Returns int32 contiguous ``(lo, hi)`` [B, S]."""
+    if isinstance(W, bool) or int(W) != W or W < 1:
+        raise ValueError(f"window_bounds: W must be an integer >= 1, got {W!r}")
+    if isinstance(doc, (tuple, list)) and len(doc) == 2 and isinstance(doc[0], torch.Tensor):
+        device = doc[0].device  # "cuda" names the current device, the bounds carry its index
+    pos = torch.arange(S, device=device, dtype=torch.int64)
+    lo = (pos - (int(W) - 1)).clamp_(min=0).to(torch.int32)
+    hi = (pos + (int(W) - 1)).clamp_(max=S - 1).to(torch.int32)
+    lo, hi = lo.expand(B, S), hi.expand(B, S)
+    if doc is not None:
+        dlo, dhi = _check_doc(doc, B, S, device, "window_bounds")
+        lo, hi = torch.maximum(lo, dlo), torch.minimum(hi, dhi)
+    return WindowBounds(lo.contiguous(), hi.contiguous(), W)
+
+
+def _fold_window(window, doc, B: int, S: int, device):
+    """``window=`` of the attention ops folded into ``doc``; a window >= S is no window."""
+    if window is None:
+        return doc
+    if isinstance(window, bool) or int(window) != window or window < 1:
+        raise ValueError(f"attn: window must be None or an integer >= 1, got {window!r}")
+    if window >= S or (isinstance(doc, WindowBounds) and doc.window == window):
+        return doc
+    return window_bounds(B, S, int(window), device, doc=doc)
 
 
 def _check_doc(doc, B: int, S: int, device, name: str):
@@ -300,11 +343,13 @@ def _rep_kv(t: torch.Tensor, G: int) -> torch.Tensor:
 
 
 def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, p: float, key: int,
-                  causal: bool = True, out=None, doc=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                  causal: bool = True, out=None, doc=None, window=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """q [B, nh, S, hd], k, v [B, nkv, S, hd] -> o [B*S, nh*hd] (q dtype), lse [B, nh, S] fp32.
     ``doc`` = (lo, hi) from :func:`doc_bounds` adds the intra-document mask.  nkv < nh is
-    grouped-query attention: query head h attends with kv head h // (nh // nkv)."""
+    grouped-query attention: query head h attends with kv head h // (nh // nkv).  ``window`` = W
+    is sliding-window attention (:func:`window_bounds`, merged with ``doc``)."""
     B, nh, S, hd = q.shape
+    doc = _fold_window(window, doc, B, S, q.device)
     G = _kv_group(q, k, v, "attn")
     scale = 1.0 / math.sqrt(hd)
     k, v = _rep_kv(k.float(), G), _rep_kv(v.float(), G)
@@ -325,10 +370,11 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, p: float, k
     return o, lse
 
 
-def attention_bwd(q, k, v, o, do, lse, p: float, key: int, causal: bool = True, doc=None):
+def attention_bwd(q, k, v, o, do, lse, p: float, key: int, causal: bool = True, doc=None, window=None):
     """Flash-style backward from (o, lse).  do/o are [B*S, H]; returns dq [B,nh,S,hd] and
     dk, dv in k's shape [B,nkv,S,hd] (summed over each kv head's query group in fp32)."""
     B, nh, S, hd = q.shape
+    doc = _fold_window(window, doc, B, S, q.device)
     G = _kv_group(q, k, v, "attn_bwd")
     scale = 1.0 / math.sqrt(hd)
     qf, kf, vf = q.float(), _rep_kv(k.float(), G), _rep_kv(v.float(), G)

@@ -223,6 +223,14 @@ def add_model_args(p) -> None:
                    help="QK-norm: an RMSNorm over head_dim on every query and key head before RoPE, with one "
                         "q_norm and one k_norm weight per layer.  Overrides the YAML's model.qk_norm and the "
                         "preset (default: off)")
+    p.add_argument("--sliding_window", type=int, default=None, metavar="W",
+                   help="sliding-window attention: a token attends to the last W tokens, its own included "
+                        "(W >= 1).  Overrides the YAML's model.sliding_window and the preset (default: plain "
+                        "causal attention)")
+    p.add_argument("--sliding_window_pattern", type=int, default=None, metavar="N",
+                   help="with --sliding_window: every N-th layer (layers N, 2N, ... counted from 1) stays global "
+                        "(plain causal) and the others are windowed (N >= 2).  Overrides the YAML's "
+                        "model.sliding_window_pattern (default: every layer is windowed)")
 
 
 def apply_model_args(args, model_config) -> None:
@@ -234,6 +242,13 @@ def apply_model_args(args, model_config) -> None:
         model_config.num_kv_heads = nkv
     if getattr(args, "qk_norm", None) is not None:
         model_config.qk_norm = bool(args.qk_norm)
+    sw, swp = getattr(args, "sliding_window", None), getattr(args, "sliding_window_pattern", None)
+    if sw is not None or swp is not None:
+        if sw is not None:
+            model_config.sliding_window = sw
+        if swp is not None:
+            model_config.sliding_window_pattern = swp
+        model_config.__post_init__()  # the config's own validation (ValueError)
 
 
 def unwrap_batch(batch):

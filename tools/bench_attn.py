@@ -5,7 +5,10 @@ separator every N tokens (N >= S: no boundary inside the sequence, i.e. trivial 
 the cost of the DOC instantiations themselves), or ``rand:N``: seeded geometric document
 lengths with mean N, different in every batch row.  ``--kv_heads N`` times grouped-query
 attention: N K/V heads shared by groups of nh / N query heads (the GQA kernels; N == nh
-runs them with groups of one, no flag the MHA kernels).  The backward is one call (dQ then
+runs them with groups of one, no flag the MHA kernels).  ``--window W`` times sliding-window
+attention (``window=W``: the DOC kernels on ``window_bounds`` and the banded keep-bit
+kernel) against causal in the same process, the two alternating round by round, and the
+banded against the full keep-bit kernel.  The backward is one call (dQ then
 dK/dV); a kernel trace of this tool (``tools/ab/prof_step.sh`` style: ``rocprofv3
 --kernel-trace --stats``) splits it per kernel."""
 import argparse
@@ -63,6 +66,46 @@ def attended_fraction(doc, S: int) -> float:
     return float((q - lo + 1).sum()) / (lo.shape[0] * S * (S + 1) / 2)
 
 
+def window_ab(a, q, k, v, key, gkw):
+    """causal vs window=W, head-major, alternating: per round fwd (keep bits included), the
+    forward kernel alone on given bits, bwd on stored bits, and the keep-bit kernel alone
+    (full vs banded).  Prints every round and the medians; the spread of the causal rows
+    over the rounds is the noise the ratios have to be read against."""
+    W = a.window
+    cases = {"causal": dict(gkw), f"window {W}": dict(gkw, window=W)}
+    st = {}
+    for name, kw in cases.items():
+        o, aux = hip.attention_fwd(q, k, v, a.p, key, **kw)
+        st[name] = (o, aux, torch.randn_like(o))
+    rows = {n: [] for n in cases}
+    bits = {"full": [], "banded": []}
+    for r in range(a.rounds):
+        for name, kw in cases.items():
+            o, aux, do = st[name]
+            t_f = timeit(lambda: hip.attention_fwd(q, k, v, a.p, key, **kw), a.iters)
+            t_k = timeit(lambda: hip.attention_fwd(q, k, v, a.p, key, mask=aux[1], **kw), a.iters) if a.p > 0 else t_f
+            t_b = timeit(lambda: hip.attention_bwd(q, k, v, o, do, aux, a.p, key, **kw), a.iters)
+            rows[name].append((t_f, t_k, t_b))
+            print(f"round {r} [{name}] fwd incl. keep bits {t_f:.1f} us, fwd kernel {t_k:.1f} us, bwd {t_b:.1f} us", flush=True)
+        if a.p > 0:
+            buf = st["causal"][1][1]
+            for name, wkw in (("full", {}), ("banded", {"window": W})):
+                bits[name].append(timeit(lambda: hip.attention_dropout_mask(a.B, a.nh, a.S, a.p, key, device="cuda",
+                                                                            out=buf, **wkw), a.iters))
+            print(f"round {r} keep-bit kernel: full {bits['full'][-1]:.1f} us, banded {bits['banded'][-1]:.1f} us", flush=True)
+    med = lambda xs: sorted(xs)[len(xs) // 2]  # noqa: E731
+    m = {n: [med([row[i] for row in rows[n]]) for i in range(3)] for n in cases}
+    c, w = m["causal"], m[f"window {W}"]
+    spread = [(max(row[i] for row in rows["causal"]) - min(row[i] for row in rows["causal"])) / c[i] * 100 for i in range(3)]
+    print(f"B{a.B} nh{a.nh} S{a.S} p{a.p} window {W}, medians of {a.rounds} rounds x {a.iters} iterations:")
+    for i, nm in enumerate(("fwd incl. keep bits", "fwd kernel", "bwd (dQ + dK/dV)")):
+        print(f"  {nm}: causal {c[i]:.1f} us, window {w[i]:.1f} us, ratio {c[i] / w[i]:.2f}x "
+              f"(causal spread over the rounds {spread[i]:.1f} %)")
+    if a.p > 0:
+        print(f"  keep-bit kernel: full {med(bits['full']):.1f} us, banded {med(bits['banded']):.1f} us, "
+              f"ratio {med(bits['full']) / med(bits['banded']):.2f}x")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=8)
@@ -77,6 +120,9 @@ def main():
                          "lengths with mean N (rand:N); N >= S gives trivial bounds")
     ap.add_argument("--kv_heads", type=int, default=None, metavar="N",
                     help="grouped-query attention with N K/V heads (must divide --nh); default: the MHA kernels")
+    ap.add_argument("--window", type=int, default=None, metavar="W",
+                    help="also time sliding-window attention of W keys, alternating with causal (--rounds rounds)")
+    ap.add_argument("--rounds", type=int, default=5, help="alternating rounds of the --window comparison")
     ap.add_argument("--only", default="both", choices=("both", "off", "doc"),
                     help="which variants to run (a kernel trace of one variant: --only off / --only doc)")
     a = ap.parse_args()
@@ -97,6 +143,9 @@ def main():
         variants.append((f"doc_len {a.doc_len} ({100 * attended_fraction(doc, a.S):.1f} % of the causal scores)",
                          {"doc": doc}))
     fl = 4 * a.B * a.nh * a.S * a.S / 2 * 64
+    if a.window is not None:
+        window_ab(a, q, k, v, key, gkw)
+        return
     if a.kv_heads is not None:
         nrb = (a.S + 63) // 64
         print(f"kv_heads {nkv} (groups of {a.nh // nkv}): dK/dV runs {a.B * nkv * nrb} work items "

@@ -1,10 +1,13 @@
 """Decode throughput of GPT.generate (KV cache) with and without the HIP-graph step.
-usage: python tools/bench_decode.py [model_size] [batch] [new_tokens] [num_kv_heads] [max_seq_len]
+usage: python tools/bench_decode.py [model_size] [batch] [new_tokens] [num_kv_heads] [max_seq_len] [window]
+("-" leaves an argument at its default)
 
 ``num_kv_heads`` (default: the preset's, multi-head) makes the model grouped-query; the
 run then also prints which fused step it took (``_fused_kind``) and the key splits (NS,
 ``DLT_DECODE_KV_SPLITS``) of its attention, and times the captured step once more at the
-last cache position (every key read).  ``max_seq_len`` overrides the preset's cache length."""
+last cache position (every key read).  ``max_seq_len`` overrides the preset's cache length.
+``window`` makes every layer a sliding-window layer of that many keys (``sliding_window``);
+the same timings are printed, so a run with and one without it compare the captured step."""
 import os
 import sys
 import time
@@ -14,27 +17,37 @@ import torch  # noqa: E402
 
 from distributed_llm_trainer_amd.models import GPT, GPTConfig  # noqa: E402
 
-size = sys.argv[1] if len(sys.argv) > 1 else "small"
-B = int(sys.argv[2]) if len(sys.argv) > 2 else 1
-N = int(sys.argv[3]) if len(sys.argv) > 3 else 200
-NKV = int(sys.argv[4]) if len(sys.argv) > 4 else None
-MAXS = int(sys.argv[5]) if len(sys.argv) > 5 else None
+
+
+def _arg(i, default, conv=int):
+    return conv(sys.argv[i]) if len(sys.argv) > i and sys.argv[i] != "-" else default
+
+
+size = _arg(1, "small", str)
+B = _arg(2, 1)
+N = _arg(3, 200)
+NKV = _arg(4, None)
+MAXS = _arg(5, None)
+WINDOW = _arg(6, None)
 torch.manual_seed(0)
 cfg = GPTConfig.from_preset(size)
 if NKV is not None:
     cfg.num_kv_heads = NKV
 if MAXS is not None:
     cfg.max_seq_len = MAXS
-if NKV is not None or MAXS is not None:
+if WINDOW is not None:
+    cfg.sliding_window = WINDOW
+if NKV is not None or MAXS is not None or WINDOW is not None:
     cfg.__post_init__()
 m = GPT(cfg).to("cuda")
 m.enable_engine()
 from distributed_llm_trainer_amd.eval.decode import DecodeGraph, KVCache, _fused_kind, _gqa_splits, forward_cached  # noqa: E402
-if NKV is not None:
+DETAIL = NKV is not None or MAXS is not None or WINDOW is not None
+if DETAIL:
     kind = _fused_kind(m, B)
     ns = _gqa_splits(m.config, B) if kind == "gqa" else "-"
-    print(f"{size} B={B} nh={m.config.num_heads} nkv={m.config.num_kv_heads} max_seq_len={m.config.max_seq_len}: "
-          f"fused kind {kind}, NS {ns}", flush=True)
+    print(f"{size} B={B} nh={m.config.num_heads} nkv={m.config.num_kv_heads} max_seq_len={m.config.max_seq_len} "
+          f"window={m.config.sliding_window}: fused kind {kind}, NS {ns}", flush=True)
 ids = torch.randint(0, 50257, (B, 32), device="cuda")
 for mode, graph, loop in (("eager", "0", "0"), ("graph, host sampling", "1", "0"), ("graph, device loop", "1", "1")):
     os.environ["DLT_DECODE_GRAPH"] = graph
@@ -60,7 +73,7 @@ with torch.no_grad():
         g.graph.replay()
     torch.cuda.synchronize()
     print(f"graph replay only: {(time.perf_counter() - t) / 100 * 1e3:.3f} ms/step")
-    if NKV is not None:
+    if DETAIL:
         # three windows of 300 replays each, at the prompt's position and over a full cache
         # (the rows beyond the prompt are zero): the spread between windows is the noise
         for name, p in (("prompt position", c.len), ("full cache", m.config.max_seq_len - 1)):
