@@ -61,6 +61,18 @@ def _qk_norm(q: torch.Tensor, k: torch.Tensor, w, eps: float):
     return _rms(q, w.qn, eps), _rms(k, w.kn, eps)
 
 
+def _sink_softmax(s: torch.Tensor, w) -> torch.Tensor:
+    """Softmax over the keys of scores ``s`` [B, nh, T, keys] (fp32, masked entries -inf).  With
+    attention sinks (cfg.attention_sinks: ``w.sk`` is set) the head's sink logit is one more
+    column of the softmax -- it takes part in the denominator and has no value row -- and the
+    key columns are returned."""
+    sk = getattr(w, "sk", None)
+    if sk is None:
+        return torch.softmax(s, dim=-1)
+    col = sk.float().view(1, -1, 1, 1).expand(s.shape[0], -1, s.shape[2], 1)
+    return torch.softmax(torch.cat([s, col], dim=-1), dim=-1)[..., :-1]
+
+
 def _split_qkv(qkv: torch.Tensor, cfg):
     """Packed projection [B, T, H + 2*KV] fp32 -> q [B, T, nh, hd], k, v [B, T, nkv, hd]."""
     B, T, _ = qkv.shape
@@ -133,7 +145,7 @@ def forward_cached(model, ids: torch.Tensor, cache: KVCache) -> torch.Tensor:
             if W is not None:  # sliding window: the keys at or below qpos - W are out
                 hidden = hidden | (kpos <= qpos - W)
             s = s.masked_fill(hidden, float("-inf"))
-        pr = torch.softmax(s, dim=-1)
+        pr = _sink_softmax(s, w)
         o = torch.matmul(pr, Vv).transpose(1, 2).reshape(B, T, nh * hd).to(dt)
         h = h + torch.matmul(o, w.wo.t()).float()
         n2 = _rms(h, w.ln2, eng.eps).to(dt)
@@ -221,6 +233,8 @@ class DecodeGraph:
             w = prov.layer(i)
             W = _layer_window(cfg, i) or 0
             wkw = {"window": W} if W else {}  # a global layer calls the kernels it always did
+            if getattr(w, "sk", None) is not None:  # attention sinks: the kernels' sink= forms
+                wkw["sink"] = w.sk
             if self.kind == "gqa":
                 ops.dec_norm_qkv_gqa(self.h, w.ln1, eng.eps, w.wqkv, cos_t, sin_t, self.pos, self.qb, cache.k[i],
                                      cache.v[i], cfg.num_heads, cfg.num_kv_heads)
@@ -271,7 +285,7 @@ class DecodeGraph:
             cache.v[i].index_copy_(2, self.pos, v.transpose(1, 2).to(dt))
             qh = q.to(dt).transpose(1, 2)  # [B, nh, 1, hd]; bf16 GEMVs straight on the bf16 cache
             s_ = torch.matmul(qh, _rep_kv(cache.k[i], cfg).transpose(-2, -1)).float() * scale
-            pr = torch.softmax(s_.masked_fill(masked, float("-inf")), dim=-1)
+            pr = _sink_softmax(s_.masked_fill(masked, float("-inf")), w)
             o = torch.matmul(pr.to(dt), _rep_kv(cache.v[i], cfg)).transpose(1, 2).reshape(B, 1, nh * hd)
             h = h + torch.matmul(o, w.wo.t()).float()
             n2 = _rms(h, w.ln2, eng.eps).to(dt)

@@ -56,6 +56,10 @@ class GPTConfig:
     # the query heads (q_norm) and one for the key heads (k_norm), applied before RoPE.
     qk_norm: bool = False
 
+    # Attention sinks (gpt-oss form): one learned fp32 logit per query head that takes part in
+    # the softmax denominator and has no value row: p_j = exp(s_j) / (sum_j exp(s_j) + exp(sink)).
+    attention_sinks: bool = False
+
     # Sliding-window (local) attention: query q sees key k iff q - W < k <= q, W keys with its
     # own (the Mistral / Gemma rule).  With sliding_window_pattern = N, layer i (0-based) is
     # global (plain causal) iff (i + 1) % N == 0 (Gemma-3's rule); unset, every layer is windowed.
@@ -74,6 +78,9 @@ class GPTConfig:
             raise ValueError(
                 f"num_kv_heads ({self.num_kv_heads}) must divide num_heads ({self.num_heads})")
         self.qk_norm = bool(self.qk_norm)
+        if not isinstance(self.attention_sinks, (bool, int)) or self.attention_sinks not in (0, 1):
+            raise ValueError(f"attention_sinks ({self.attention_sinks!r}) must be a bool")
+        self.attention_sinks = bool(self.attention_sinks)
         if self.sliding_window is not None:
             if isinstance(self.sliding_window, bool) or int(self.sliding_window) != self.sliding_window \
                     or self.sliding_window < 1:
@@ -149,6 +156,8 @@ class GPTConfig:
         per_layer = 2 * h * h + 2 * self.kv_size * h + 3 * h * i + 2 * h
         if self.qk_norm:
             per_layer += 2 * self.head_dim  # q_norm, k_norm
+        if self.attention_sinks:
+            per_layer += self.num_heads  # sinks
         return self.vocab_size * h + self.num_layers * per_layer + h
 
     def num_parameters_legacy(self) -> int:
@@ -189,20 +198,24 @@ class GPTConfig:
             del d["num_kv_heads"]
         if not self.qk_norm:  # ... and so do configs without QK-norm
             del d["qk_norm"]
+        if not self.attention_sinks:  # ... and configs without attention sinks
+            del d["attention_sinks"]
         for k in ("sliding_window", "sliding_window_pattern"):  # ... and unwindowed ones
             if d[k] is None:
                 del d[k]
         return d
 
-    # Pickled configs (checkpoints) follow to_dict(): an MHA config carries no num_kv_heads and
-    # one without QK-norm no qk_norm, so their pickles are what they were before the fields
-    # existed and older pickles load.
+    # Pickled configs (checkpoints) follow to_dict(): an MHA config carries no num_kv_heads, one
+    # without QK-norm no qk_norm and one without sinks no attention_sinks, so their pickles are
+    # what they were before the fields existed and older pickles load.
     def __getstate__(self) -> Dict[str, Any]:
         state = dict(self.__dict__)
         if state.get("num_kv_heads") == state.get("num_heads"):
             state.pop("num_kv_heads", None)
         if not state.get("qk_norm"):
             state.pop("qk_norm", None)
+        if not state.get("attention_sinks"):
+            state.pop("attention_sinks", None)
         for k in ("sliding_window", "sliding_window_pattern"):
             if state.get(k) is None:
                 state.pop(k, None)
@@ -213,6 +226,7 @@ class GPTConfig:
         if self.__dict__.get("num_kv_heads") is None:
             self.num_kv_heads = self.num_heads
         self.qk_norm = bool(self.__dict__.get("qk_norm", False))
+        self.attention_sinks = bool(self.__dict__.get("attention_sinks", False))
         self.__dict__.setdefault("sliding_window", None)
         self.__dict__.setdefault("sliding_window_pattern", None)
 

@@ -74,6 +74,7 @@ class LayerWeights:
     ln2: torch.Tensor    # [H]
     qn: Any = None       # QK-norm (cfg.qk_norm): q_norm / k_norm weights [head_dim], else None
     kn: Any = None
+    sk: Any = None       # attention sinks (cfg.attention_sinks): [num_heads] logits, else None
 
 
 @dataclass
@@ -86,6 +87,7 @@ class LayerGrads:
     ln2: torch.Tensor
     qn: Any = None       # fp32 [head_dim] gradients of q_norm / k_norm (cfg.qk_norm)
     kn: Any = None
+    sk: Any = None       # fp32 [num_heads] gradient of the attention sinks (cfg.attention_sinks)
 
 
 @dataclass
@@ -273,6 +275,14 @@ class GPTEngine:
             if not self.packed_qkv:
                 raise NotImplementedError("QK-norm on the GPU runs on the packed QKV layout "
                                           "(DLT_PACKED_QKV=0 is not supported with qk_norm)")
+        # attention sinks (cfg.attention_sinks): the attention forward takes sink=w.sk (the SINK
+        # kernels fold it into the softmax denominator and lse) and the backward dsink=gr.sk
+        # (k_attn_sink_bwd, from lse and the delta workspace); o and lse are kept anyway, so
+        # activation checkpointing keeps nothing new
+        self.sinks = bool(getattr(cfg, "attention_sinks", False))
+        if self.sinks and getattr(ops, "backend", "") == "hip":
+            from ..ops import check_attention_sinks
+            check_attention_sinks("cuda", cfg.head_dim, act_dtype)
         # last layers of the deferred-wgrad backward whose weight gradients run on the
         # current stream instead of the side stream (see _backward_gen)
         self.main_wgrad_layers = int(os.environ.get("DLT_MAIN_WGRAD_LAYERS", "1"))
@@ -582,11 +592,15 @@ class GPTEngine:
         if self.packed_qkv:
             if not fused_rope and raw is None:
                 ops.rope_qk_inplace(qkv, B, S, cfg.num_heads, cos, sin, **self.gqa_kw)
+            if self.sinks:
+                kw["sink"] = w.sk
             o, lse = ops.attention_fwd_packed(qkv, B, S, cfg.num_heads, pa, k_attn, out=sb("o", H), **kw,
                                               **self.gqa_kw)
             q, k, v = qkv, None, None
         else:
             q, k, v = ops.rope_qkv_fwd(qkv, B, S, cfg.num_heads, *self._split_tables(raw, cos, sin), **self.gqa_kw)
+            if self.sinks:
+                kw["sink"] = w.sk
             o, lse = ops.attention_fwd(q, k, v, pa, k_attn, True, out=sb("o", H), **kw)
         del qkv
         a = gm.linear(o, w.wo)
@@ -1130,6 +1144,10 @@ class GPTEngine:
             del dn2
             # attention
             dkw = self._attn_bounds_kw(st, i)
+            if self.sinks:
+                # gr.sk is shared with the other micro-steps like gr.ln1 / gr.ln2: the
+                # accumulation lies between wait_prev(i) and mark(i)
+                dkw.update(sink=w.sk, dsink=gr.sk)
             do = gm.linear_dgrad(da, w.wo)
             if c.k is None:  # packed: dq/dk/dv land in [M, 3H] with the inverse RoPE applied
                 dqkv = ops.attention_bwd_packed(c.q, c.o, do, c.lse, pa, k_attn, B, S, cfg.num_heads, cos, sin,

@@ -102,6 +102,11 @@ class CausalSelfAttention(nn.Module):
         if self.qk_norm:
             self.q_norm = RMSNorm(self.head_dim)
             self.k_norm = RMSNorm(self.head_dim)
+        # Attention sinks (config.attention_sinks): one learned fp32 logit per query head in the
+        # softmax denominator, no value row.  Without the flag the parameter does not exist.
+        self.attention_sinks = config.attention_sinks
+        if self.attention_sinks:
+            self.sinks = nn.Parameter(torch.zeros(self.num_heads, dtype=torch.float32))
         self.attn_dropout = nn.Dropout(config.attention_dropout)
         self.resid_dropout = nn.Dropout(config.dropout)
         self.rotary_emb = RotaryPositionEmbedding(self.head_dim, config.max_seq_len)
@@ -128,7 +133,16 @@ class CausalSelfAttention(nn.Module):
             pos = torch.arange(S, device=hidden_states.device)
             out_of_window = (pos[None, :] <= pos[:, None] - self.window)[None, None]
             doc_hidden = out_of_window if doc_hidden is None else doc_hidden | out_of_window
-        if self.use_flash and doc_hidden is not None:
+        if self.attention_sinks:  # SDPA cannot express the sink: the explicit formula in either setting
+            scores = torch.matmul(q, k.transpose(-2, -1)) / math.sqrt(self.head_dim)
+            mask = torch.triu(torch.ones(S, S, device=hidden_states.device, dtype=torch.bool), diagonal=1)
+            mask = mask[None, None] if doc_hidden is None else mask[None, None] | doc_hidden
+            scores = scores.masked_fill(mask, float("-inf"))
+            # the sink is one more score column (not scaled, per query head, no value row)
+            sink = self.sinks.float().view(1, self.num_heads, 1, 1).expand(B, -1, S, 1)
+            probs = F.softmax(torch.cat([scores.float(), sink], dim=-1), dim=-1)[..., :S].to(scores.dtype)
+            out = self.attn_dropout(probs) @ v
+        elif self.use_flash and doc_hidden is not None:
             causal = torch.tril(torch.ones(S, S, device=hidden_states.device, dtype=torch.bool))
             out = F.scaled_dot_product_attention(
                 q, k, v, attn_mask=causal[None, None] & ~doc_hidden,
@@ -244,6 +258,8 @@ class GPT(nn.Module):
             ops_mod.check_gqa(dev, self.config.head_dim, act_dtype)  # before anything is re-homed
         if self.config.qk_norm and (ops is None or ops.backend == "hip"):
             ops_mod.check_qk_norm(dev, self.config.head_dim, act_dtype)
+        if self.config.attention_sinks and (ops is None or ops.backend == "hip"):
+            ops_mod.check_attention_sinks(dev, self.config.head_dim, act_dtype)
         if self.config.sliding_window is not None and (ops is None or ops.backend == "hip"):
             ops_mod.check_sliding_window(dev, self.config.head_dim, act_dtype)
         if provider is None:

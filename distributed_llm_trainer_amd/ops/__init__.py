@@ -121,6 +121,24 @@ def check_qk_norm(device, head_dim: int = 64, act_dtype=torch.bfloat16) -> None:
                                   f"QK-norm kernel")
 
 
+def check_attention_sinks(device, head_dim: int = 64, act_dtype=torch.bfloat16) -> None:
+    """Raises NotImplementedError when the attention route :func:`for_device` picks for this
+    model has no attention sinks (``GPTConfig.attention_sinks``, ``sink=``).  The sink is a
+    ``SINK`` form of the 16-bit flash forward plus ``k_attn_sink_bwd``, so the routes are
+    :func:`check_doc_mask`'s: head_dim 64 / 128 and smaller heads zero-padded onto them pass;
+    the GEMM-formulated route (head_dim above 128) and the fp32 routes raise.  Called when the
+    engine is enabled, so the error comes before the first step, not inside it."""
+    if torch.device(device).type != "cuda" or os.environ.get("DLT_ALLOW_REFERENCE_ON_GPU") == "1":
+        return
+    from . import attn_gemm
+    from .hip import ATTN_HEAD_DIMS
+    if act_dtype == torch.float32:
+        raise NotImplementedError("attention sinks (attention_sinks) are not implemented for fp32 activations on "
+                                  "the GPU: use bf16 or fp16")
+    if head_dim not in ATTN_HEAD_DIMS:  # names the padded / GEMM route it would take
+        attn_gemm.check_sink(act_dtype, head_dim, True)
+
+
 def for_device(device, head_dim: int = 64, act_dtype=torch.bfloat16) -> types.SimpleNamespace:
     """Op namespace for ``device``.  On the GPU every op is a HIP kernel: bf16 / fp16
     activations on the 16-bit kernels, fp32 (``--mixed_precision fp32``) on the fp32

@@ -101,10 +101,10 @@ def _rows_padded(t, B, S, nh, hd, Dp):
     return out
 
 
-def _fwd_pad(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask, dt, doc=None):
+def _fwd_pad(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask, dt, doc=None, sink=None):
     from . import hip
     o_p, aux = hip.attention_fwd(q4p[0], q4p[1], q4p[2], p, key, True, store_mask=store_mask, mask=mask,
-                                 scale=1.0 / math.sqrt(hd), doc=doc)
+                                 scale=1.0 / math.sqrt(hd), doc=doc, sink=sink)
     H = nh * hd
     o = torch.empty(B * S, H, dtype=dt, device=q4p.device) if out is None else out
     if o.dtype != dt or not o.is_contiguous() or o.numel() != B * S * H:
@@ -113,12 +113,12 @@ def _fwd_pad(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask, dt, doc=None)
     return o, aux
 
 
-def _bwd_pad(q4p, o, do, aux, B, S, nh, hd, Dp, p, key, doc=None):
+def _bwd_pad(q4p, o, do, aux, B, S, nh, hd, Dp, p, key, doc=None, sink=None, dsink=None):
     """(dq, dk, dv) [3, B, nh, S, hd] from the padded flash backward."""
     from . import hip
     dq, dk, dv = hip.attention_bwd(q4p[0], q4p[1], q4p[2], _rows_padded(o, B, S, nh, hd, Dp),
                                    _rows_padded(do, B, S, nh, hd, Dp), aux, p, key, scale=1.0 / math.sqrt(hd),
-                                   doc=doc)
+                                   doc=doc, sink=sink, dsink=dsink)
     g = torch.empty(3, B, nh, S, hd, dtype=dq.dtype, device=dq.device)
     for j, t in enumerate((dq, dk, dv)):
         _relayout16(t, (nh * S * Dp, Dp, S * Dp), g[j], (nh * S * hd, hd, S * hd), B, S, nh, hd, 1)
@@ -314,6 +314,16 @@ def check_window(dtype, hd: int, window) -> None:
         f"(head_dim {hd}, {dtype}); use bf16 or fp16 activations with head_dim <= 128")
 
 
+def check_sink(dtype, hd: int, sink) -> None:
+    """Attention sinks take the routes the document mask takes: zero-padded 16-bit heads pass
+    ``sink=`` through to the flash kernels (the padding is exact), every other route here raises."""
+    if sink is None or (dtype in _HK and pad_dim(dtype, hd)):
+        return
+    raise NotImplementedError(
+        f"attention sinks (attention_sinks) are not implemented on the {doc_route(dtype, hd)} route "
+        f"(head_dim {hd}, {dtype}); use bf16 or fp16 activations with head_dim <= 128")
+
+
 def _fold_window(window, doc, B, S, dtype, hd, device):
     """``window=`` of the entry points folded into the bounds the padded flash kernels take
     (their keep bits stay the full ones: a superset of what the window reads)."""
@@ -324,8 +334,10 @@ def _fold_window(window, doc, B, S, dtype, hd, device):
     return hip._window_doc(window, doc, B, S, device, "attn")[1]
 
 
-def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=True, doc=None, window=None):
+def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=True, doc=None, window=None,
+                         sink=None):
     hd = qkv.shape[1] // (3 * nh)
+    check_sink(qkv.dtype, hd, sink)
     doc = _fold_window(window, doc, B, S, qkv.dtype, hd, qkv.device)
     check_doc(qkv.dtype, hd, doc)
     Dp = pad_dim(qkv.dtype, hd)
@@ -335,7 +347,7 @@ def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=
         return _fwd_pad32(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask)
     if Dp:
         q4p = _pad16(qkv, (S * ld, ld, hd), B, S, nh, hd, Dp, 3, nh * hd)
-        return _fwd_pad(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask, qkv.dtype, doc)
+        return _fwd_pad(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask, qkv.dtype, doc, sink)
     _need_fit(B, nh, S, hd)
     if use16(qkv.dtype, B, nh, S, hd):
         q4, k4, v4 = _heads16(qkv, B, S, nh, hd, 3)
@@ -346,8 +358,10 @@ def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=
     return _narrow(o32, qkv.dtype, out), aux
 
 
-def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, doc=None, window=None):
+def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, doc=None, window=None, sink=None,
+                         dsink=None):
     hd = qkv.shape[1] // (3 * nh)
+    check_sink(qkv.dtype, hd, sink)
     doc = _fold_window(window, doc, B, S, qkv.dtype, hd, qkv.device)
     check_doc(qkv.dtype, hd, doc)
     Dp = pad_dim(qkv.dtype, hd)
@@ -359,7 +373,7 @@ def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, 
         return _rope_bwd(g[0], g[1], g[2], cos, sin, out=out)
     if Dp:
         q4p = _pad16(qkv, (S * ld, ld, hd), B, S, nh, hd, Dp, 3, nh * hd)
-        g = _bwd_pad(q4p, o, do, aux, B, S, nh, hd, Dp, p, key, doc)
+        g = _bwd_pad(q4p, o, do, aux, B, S, nh, hd, Dp, p, key, doc, sink, dsink)
         del q4p
         return _rope_bwd(g[0], g[1], g[2], cos, sin, out=out)
     _need_fit(B, nh, S, hd)
@@ -376,10 +390,12 @@ def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, 
     return _narrow(hip_f32.rope_qkv_bwd(dq, dk, dv, cos, sin, out=o32), qkv.dtype, out)
 
 
-def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=None, doc=None, window=None):
+def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=None, doc=None, window=None,
+                  sink=None):
     if not causal:
         raise NotImplementedError("only causal attention is implemented (the model is a causal LM)")
     B, nh, S, hd = q.shape
+    check_sink(q.dtype, hd, sink)
     doc = _fold_window(window, doc, B, S, q.dtype, hd, q.device)
     check_doc(q.dtype, hd, doc)
     Dp = pad_dim(q.dtype, hd)
@@ -390,7 +406,7 @@ def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=
         return _fwd_pad32(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask)
     if Dp:
         q4p = torch.stack([_pad16(t.contiguous(), hm, B, S, nh, hd, Dp, 1, 0)[0] for t in (q, k, v)])
-        return _fwd_pad(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask, q.dtype, doc)
+        return _fwd_pad(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask, q.dtype, doc, sink)
     _need_fit(B, nh, S, hd)
     if use16(q.dtype, B, nh, S, hd):
         return _fwd16(q.contiguous(), k.contiguous(), v.contiguous(), B, nh, S, hd, p, key, out, mask, store_mask)
@@ -399,8 +415,9 @@ def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=
     return _narrow(o32, q.dtype, out), aux
 
 
-def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, doc=None, window=None):
+def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, doc=None, window=None, sink=None, dsink=None):
     B, nh, S, hd = q.shape
+    check_sink(q.dtype, hd, sink)
     doc = _fold_window(window, doc, B, S, q.dtype, hd, q.device)
     check_doc(q.dtype, hd, doc)
     Dp = pad_dim(q.dtype, hd)
@@ -411,7 +428,7 @@ def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, doc=None, window=Non
         return tuple(_bwd_pad32(q4p, o, do, aux, B, S, nh, hd, Dp, p, key).unbind(0))
     if Dp:
         q4p = torch.stack([_pad16(t.contiguous(), hm, B, S, nh, hd, Dp, 1, 0)[0] for t in (q, k, v)])
-        return tuple(_bwd_pad(q4p, o, do, aux, B, S, nh, hd, Dp, p, key, doc).unbind(0))
+        return tuple(_bwd_pad(q4p, o, do, aux, B, S, nh, hd, Dp, p, key, doc, sink, dsink).unbind(0))
     _need_fit(B, nh, S, hd)
     if use16(q.dtype, B, nh, S, hd):
         return _bwd16(q.contiguous(), k.contiguous(), v.contiguous(), o, do, aux, B, nh, S, hd, p, key)

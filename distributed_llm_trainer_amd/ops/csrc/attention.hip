@@ -42,235 +42,11 @@
 // Layouts: q, k, v, dq, dk, dv: strided views -- head-major [B*nh, S, 64] or the
 // packed [B*S, 3, nh, 64] QKV GEMM output (see dlt_attn_stride); o, do: [B, S, nh, 64]
 // bf16 (= the [M, H] GEMM layout);  lse, delta: [B*nh, S] fp32 (natural-log lse).
-#include "common.h"
+#include "attention.h"
 
-#ifndef DLT_ATTN_KREAD_ASM
-#define DLT_ATTN_KREAD_ASM 1
+#ifdef DLT_ATTN_FWD_TIMING
+__device__ unsigned long long* g_attn_ftim;  // forward diagnostics, see attention.h
 #endif
-
-#include <type_traits>
-
-#define KVB 64     // keys per staged tile (fwd / dQ)
-#define RB 64      // rows (queries for fwd / dQ, keys for dK/dV) per work item: 2 waves x 32
-#define QSTEP 64   // queries per staged tile (dK/dV)
-#define NT 128     // threads per workgroup
-#define LOG2E 1.44269504088896340736f
-
-typedef __attribute__((address_space(3))) shortx4_t lds_shortx4_t;
-typedef short shortx8_t __attribute__((ext_vector_type(8)));
-
-// LDS tile: [64 rows][D bf16].  D = 64: 128-B rows, 16-B chunk c of row r stored at
-// chunk c ^ ((r >> 1) & 7) -- row pairs fill the 64 banks, so 16 consecutive rows of a
-// ds_read_b128 row-fragment read are conflict-free.  D = 128: 256-B rows (every row
-// starts at bank 0), chunk c ^ (r & 15) gives 16 consecutive rows 16 distinct chunks.
-template <int D>
-__device__ __forceinline__ int swz_x(int row) { return D == 64 ? ((row >> 1) & 7) : (row & 15); }
-template <int D>
-__device__ __forceinline__ int swz_off(int row, int col) {
-  return row * D + ((((col >> 3) ^ swz_x<D>(row))) << 3) + (col & 7);
-}
-
-template <int D>
-__device__ __forceinline__ bf16x8_t lds_row8(const bf16_t* T, int row, int col) {
-  return *reinterpret_cast<const bf16x8_t*>(T + swz_off<D>(row, col));
-}
-
-template <int D>
-__device__ __forceinline__ shortx4_t lds_tr4(const bf16_t* T, int row, int col) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_shortx4_t*)(T + swz_off<D>(row, col)));
-}
-
-// A operand A[d][k] (k = rows of T) in the permuted k order that matches accumulator
-// registers 8s..8s+7 used as the B operand: element j of lane-half h <-> row
-// 16*kk + 8*(j>>2) + 4*h + (j&3)  (cdna_hip_programming.md §3).
-template <int D>
-__device__ __forceinline__ bf16x8_t tr_frag(const bf16_t* T, int kk, int dt, int lane) {
-  const int h = lane >> 5, i = lane & 15;
-  const int col = 32 * dt + 16 * ((lane >> 4) & 1) + 4 * (i & 3);
-  const int r1 = 16 * kk + 4 * h + (i >> 2);
-  const shortx4_t a = lds_tr4<D>(T, r1, col);
-  const shortx4_t b = lds_tr4<D>(T, r1 + 8, col);
-  shortx8_t c = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  return __builtin_bit_cast(bf16x8_t, c);
-}
-
-// The same fragment read through inline asm.  hipcc conservatively drains vmcnt(0)
-// before any ds_read_b64_tr_b16 *intrinsic* while a global_load_lds is in flight
-// (it cannot prove the DMA target and the read disjoint), which serialises the next
-// tile's LDS-DMA with this tile's compute.  Asm reads are invisible to that alias
-// check; the protocol that makes them safe is explicit: every tile step ends with
-// `s_waitcnt vmcnt(0)` + barrier (tile_barrier), so a tile is complete before any
-// wave reads it, and tr_wait() retires the reads before their registers are used.
-template <int D>
-__device__ __forceinline__ shortx4_t lds_tr4_asm(const bf16_t* T, int row, int col) {
-  shortx4_t r;
-  const uint32_t addr = (uint32_t)(uintptr_t)(T + swz_off<D>(row, col));
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(addr));
-  return r;
-}
-template <int D>
-__device__ __forceinline__ bf16x8_t tr_frag_asm(const bf16_t* T, int kk, int dt, int lane) {
-  const int h = lane >> 5, i = lane & 15;
-  const int col = 32 * dt + 16 * ((lane >> 4) & 1) + 4 * (i & 3);
-  const int r1 = 16 * kk + 4 * h + (i >> 2);
-  const shortx4_t a = lds_tr4_asm<D>(T, r1, col);
-  const shortx4_t b = lds_tr4_asm<D>(T, r1 + 8, col);
-  shortx8_t c = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  return __builtin_bit_cast(bf16x8_t, c);
-}
-// Row-fragment read through inline asm (see lds_tr4_asm for the protocol), so several
-// reads can be in flight under one counted wait (the intrinsic form drew one
-// lgkmcnt(0) per MFMA pair).
-template <int D>
-__device__ __forceinline__ bf16x8_t lds_row8_asm(const bf16_t* T, int row, int col) {
-  bf16x8_t r;
-  const uint32_t addr = (uint32_t)(uintptr_t)(T + swz_off<D>(row, col));
-  asm volatile("ds_read_b128 %0, %1" : "=v"(r) : "v"(addr));
-  return r;
-}
-// Oldest four of eight outstanding LDS reads retired (LDS returns in order; no SMEM
-// load is issued inside a tile step).
-__device__ __forceinline__ void lgkm_wait4(bf16x8_t& a, bf16x8_t& b, bf16x8_t& c, bf16x8_t& d) {
-  asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)::"memory");
-}
-// D = 128 forms: the oldest eight of sixteen reads retired; pin4 keeps four more
-// fragments' consumers below the preceding wait (volatile asm stays in order).
-__device__ __forceinline__ void lgkm_wait8(bf16x8_t& a, bf16x8_t& b, bf16x8_t& c, bf16x8_t& d) {
-  asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)::"memory");
-}
-__device__ __forceinline__ void pin4(bf16x8_t& a, bf16x8_t& b, bf16x8_t& c, bf16x8_t& d) {
-  asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
-}
-// Retire every outstanding LDS read, holding the consumers of all N fragments below it.
-template <int N>
-__device__ __forceinline__ void tr_wait_all(bf16x8_t (&f)[N]) {
-  static_assert(N % 4 == 0, "groups of four");
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3])::"memory");
-#pragma unroll
-  for (int j = 4; j < N; j += 4) pin4(f[j], f[j + 1], f[j + 2], f[j + 3]);
-}
-__device__ __forceinline__ float max16(const floatx16_t& a) {
-  const float m0 = fmaxf(fmaxf(a[0], a[1]), a[2]), m1 = fmaxf(fmaxf(a[3], a[4]), a[5]);
-  const float m2 = fmaxf(fmaxf(a[6], a[7]), a[8]), m3 = fmaxf(fmaxf(a[9], a[10]), a[11]);
-  const float m4 = fmaxf(fmaxf(a[12], a[13]), a[14]);
-  return fmaxf(fmaxf(fmaxf(m0, m1), m2), fmaxf(fmaxf(m3, m4), a[15]));
-}
-// Retire outstanding LDS reads; the fragments are in/out operands so no consumer can
-// be scheduled above the wait.
-__device__ __forceinline__ void tr_wait(bf16x8_t& a, bf16x8_t& b, bf16x8_t& c, bf16x8_t& d) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)::"memory");
-}
-// End of a tile step: this wave's LDS-DMA writes have landed, then the workgroup syncs.
-__device__ __forceinline__ void tile_barrier() {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-}
-
-// Accumulator registers 8s..8s+7 as a bf16 MFMA operand: one v_cvt_pk_bf16_f32 per
-// pair (an element-wise cast after a select made hipcc emit one cvt per element plus
-// a v_perm per pair).
-typedef float floatx8_t __attribute__((ext_vector_type(8)));
-// HK = 1 (fp16 activations): the same registers as fp16 (RNE), kept in the bf16x8_t
-// container type -- fragments are raw 16-byte operands; only mfma<HK> reads their format.
-template <int HK = 0>
-__device__ __forceinline__ bf16x8_t acc_frag(const floatx16_t& acc, int s) {
-  const floatx8_t f = s ? acc.s89abcdef : acc.s01234567;
-  if constexpr (HK == 0) return __builtin_convertvector(f, bf16x8_t);
-  else return __builtin_bit_cast(bf16x8_t, __builtin_convertvector(f, f16x8_t));
-}
-// element j of a 16-bit fragment as float
-template <int HK>
-__device__ __forceinline__ float frag_f(const bf16x8_t& v, int j) {
-  if constexpr (HK == 0) return (float)v[j];
-  else return (float)__builtin_bit_cast(f16x8_t, v)[j];
-}
-
-// Dropout select on the fp32 bit pattern: all-ones / all-zeros from keep bit `bit` of
-// `word` (v_bfe_i32), then one AND -- 2 VALU per element instead of and + cmp +
-// cndmask.  A dropped element becomes +0.0f.
-__device__ __forceinline__ uint32_t keep_ones(uint32_t word, int bit) {
-  uint32_t m = (uint32_t)__builtin_amdgcn_sbfe((int)word, bit, 1);
-  // Empty asm (no instruction, so nothing for the hazard recognizer to miss): hides
-  // that m is 0 / ~0, which stops LLVM from rewriting bfe + and as and + cmp + cndmask.
-  asm("" : "+v"(m));
-  return m;
-}
-__device__ __forceinline__ float keep_and(float x, uint32_t ones) {
-#ifdef DLT_ATTN_NOSEL  // diagnostic upper bound only (tools/ab): drops nothing, wrong numerics
-  return x;
-#endif
-  return __uint_as_float(__float_as_uint(x) & ones);
-}
-
-template <int HK = 0>
-__device__ __forceinline__ floatx16_t mfma(const bf16x8_t& a, const bf16x8_t& b, const floatx16_t& c) {
-  if constexpr (HK == 0) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0,
-                                                  0, 0);
-}
-
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-// row (within a 32x32 tile) of accumulator register i for lane-half h
-__device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
-
-__device__ __forceinline__ floatx16_t zero16() {
-  floatx16_t z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
-
-// Direct global->LDS tile copy (global_load_lds_dwordx4, no staging registers): one
-// wave-instruction writes 1 KiB = 1024 / (2D) rows contiguously (lane l -> row
-// l / (D/8), 16-B slot l % (D/8)), so the XOR swizzle is applied on the SOURCE
-// address: slot s of row r holds global chunk s ^ swz_x(r), exactly the image
-// swz_off() reads.  64 rows = 8 (D = 64) or 16 (D = 128) instructions, split over the
-// 2 waves.  Completion is tracked by vmcnt; the __syncthreads() that ends every tile
-// step waits for it.
-typedef __attribute__((address_space(3))) void* lds_vptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_cvptr_t;
-template <int D>
-__device__ __forceinline__ void glds_tile(const bf16_t* __restrict__ base, int row0, int S, int rstride, bf16_t* T,
-                                          int wid, int lane) {
-  // 32-bit offsets (a head's rows span < 4 GB) on the wave-uniform base: the DMA takes
-  // the saddr form and no 64-bit address arithmetic runs per tile (fwd / dQ).
-  constexpr int CPR = D / 8, RPI = 64 / CPR, NI = 32 / RPI;  // chunks / row, rows / instr, instr / wave
-  const char* b = reinterpret_cast<const char*>(base);
-#pragma unroll
-  for (int j = 0; j < NI; ++j) {
-    const int rr = (wid * NI + j) * RPI;  // first row of this 1 KiB piece (wave-uniform)
-    const int row = rr + lane / CPR;
-    const int c = (lane % CPR) ^ swz_x<D>(row);
-    const uint32_t off = (uint32_t)(min(row0 + row, S - 1) * rstride + c * 8) * 2u;
-    __builtin_amdgcn_global_load_lds((gbl_cvptr_t)(b + off), (lds_vptr_t)(T + rr * D), 16, 0, 0);
-  }
-}
-// The same copy with 64-bit row addressing: fewer live registers in dK/dV, which stages
-// two operands with different row strides and sits at the VGPR limit.
-template <int D>
-__device__ __forceinline__ void glds_tile64(const bf16_t* __restrict__ base, int row0, int S, int rstride, bf16_t* T,
-                                            int wid, int lane) {
-  constexpr int CPR = D / 8, RPI = 64 / CPR, NI = 32 / RPI;
-#pragma unroll
-  for (int j = 0; j < NI; ++j) {
-    const int rr = (wid * NI + j) * RPI;
-    const int row = rr + lane / CPR;
-    const int c = (lane % CPR) ^ swz_x<D>(row);
-    const bf16_t* g = base + (size_t)min(row0 + row, S - 1) * rstride + c * 8;
-    __builtin_amdgcn_global_load_lds((gbl_cvptr_t)g, (lds_vptr_t)(T + rr * D), 16, 0, 0);
-  }
-}
-
-__device__ __forceinline__ bf16x8_t load_row8(const bf16_t* __restrict__ p, bool ok) {
-  bf16x8_t v = *reinterpret_cast<const bf16x8_t*>(p);
-  if (!ok) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (__bf16)0.f;
-  }
-  return v;
-}
 
 // ============================================================================ dropout bits
 // Keep-bit words in two layouts (one hash per element pair, computed once):
@@ -404,239 +180,10 @@ __global__ __launch_bounds__(256) void k_dropout_bits(uint32_t* __restrict__ mas
   if (active && kk < S) maskT[((size_t)bh * W + r) * S + kk] = col;
 }
 
-// ============================================================================ work map
-// The MFMA kernels run a 1-D grid of (head, item-pair) work items.  The dispatcher deals
-// consecutive workgroup ids round-robin to the 8 XCDs, each with its own 4 MB L2; with
-// the natural order (pair fastest) XCD x would get pair x of EVERY head, so no two
-// workgroups on an XCD share a K/V (fwd, dQ) or Q/dO (dK/dV) stream and every tile is
-// fetched once per pair from the fabric.  The XCD-aware map gives each XCD a contiguous
-// range of items instead -- all pairs of a head on one XCD, reading the head's tiles
-// through the same L2 (bijective for any grid size, like the GEMM's tile map).
-__device__ __forceinline__ bool work_item(int nrb, int sched, int& bh, int& pair) {
-  const int bid = blockIdx.x;
-  if (sched & 2) {
-    // LPT: one 64-row item per workgroup, longest first (block ids ascend in dispatch
-    // order), so short items fill the slots the long ones leave -- many more, shorter
-    // waves than the pairing.  bid % 8 == bh % 8 when B*nh % 8 == 0: a head stays on
-    // one XCD (its K/V or Q/dO tiles through one L2).
-    const int BH = gridDim.x / nrb;
-    pair = bid / BH;  // rank: 0 = longest item
-    bh = bid - pair * BH;
-    return true;
-  }
-  const int npairs = (nrb + 1) / 2;
-  int wg = bid;
-  if (sched & 1) {
-    const int nwg = gridDim.x, xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  }
-  bh = wg / npairs;
-  pair = wg - bh * npairs;
-  return false;
-}
-
 // ============================================================================ forward
-// Cross-half (lane i <-> i^32) exchange without LDS: v_permlane32_swap (CDNA4).
-__device__ __forceinline__ float xhalf_max(float x) {
-  const uint32_t u = __float_as_uint(x);
-  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float xhalf_sum(float x) {
-  const uint32_t u = __float_as_uint(x);
-  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-// 16-byte row stores from the split-lane accumulator layout.  Lane (row, h) holds dims
-// 32dt + 8g + 4h + [0, 4) (w[dt][g], 4 bf16 = 2 dwords).  One v_permlane32_swap of the
-// (g = 2m, 2m + 1) pair -- own g = 2m stays in the low lanes' vdst, the high lanes' g = 2m
-// lands there; own g = 2m + 1 stays in the high lanes' vsrc -- leaves lane h holding
-// dims 16m + 8h + [0, 8): 4 dwordx4 stores per row instead of 8 dwordx2 (the epilogue's
-// store issue is the tail of every work item).
-template <int D>
-__device__ __forceinline__ void store_row16(bf16_t* __restrict__ row, const uint2 (&w)[D / 32][4], int h) {
-#pragma unroll
-  for (int dt = 0; dt < D / 32; ++dt)
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      const auto rx = __builtin_amdgcn_permlane32_swap(w[dt][2 * m].x, w[dt][2 * m + 1].x, false, false);
-      const auto ry = __builtin_amdgcn_permlane32_swap(w[dt][2 * m].y, w[dt][2 * m + 1].y, false, false);
-      *reinterpret_cast<uint4*>(row + 32 * dt + 16 * m + 8 * h) = make_uint4(rx[0], ry[0], rx[1], ry[1]);
-    }
-}
-
-// Rescale threshold (log2 units): the running max is only moved when some row's max
-// grew by more than 2^RESCALE_LOG2 (P is then bounded by 2^8 = 256 instead of 1,
-// exact in fp32 l/O and the same relative bf16 precision for P).  Almost every
-// rescale after a row's first tile is skipped.
-#define RESCALE_LOG2 8.0f
-// Running max of a row that has seen no live key yet.  Causal-only rows meet key 0 in
-// their first tile, so -inf never survives it.  Under a document mask the later rows
-// of an item can have whole leading tiles masked; with m = -inf such a tile gives
-// mx - m = -inf - -inf = NaN (and exp2(-inf * c + inf) = NaN).  The DOC kernels start
-// from this finite value instead: a dead tile leaves m alone and adds p = exp2(-inf) = 0
-// to l and O, and the first live tile rescales by alpha = exp2(-huge) = 0 exactly as
-// from -inf, so trivial bounds reproduce the causal kernel bit for bit.
-#define M_DEAD (-1e30f)
-
-template <int D>
-struct FwdState {
-  floatx16_t o[D / 32];
-  float m, l;  // running max (raw score units) and per-lane partial row sum
-};
-
-template <bool MASK, bool DROP, int HK, int D, bool DOC = false>
-__device__ __forceinline__ void fwd_tile(FwdState<D>& fs, const bf16_t* Kt, const bf16_t* Vt,
-                                         const bf16x8_t (&qf)[D / 16], int k0, int qa, int S, int lane, float c_log2,
-                                         uint2 mw, int lo = 0) {
-  // One 64-key tile as ONE online-softmax step: S = K.Q^T of both 32-key halves first
-  // (two independent MFMA chains), one row max / rescale decision for the tile, then
-  // per half exp -> dropout -> P.V; the second half's softmax VALU runs while the
-  // first half's P.V MFMAs execute.  The row sum uses two partial sums (the single
-  // running sum was a 16-deep dependent add chain per half).
-  const int h = lane >> 5, ql = lane & 31;
-  // keep-bit words of this tile (prefetched with the previous tile's staging loads,
-  // so no vmcnt wait lands inside the tile); this lane-half's 16 bits per half-tile
-  // sit at (i&3) + 8(i>>2)
-  const uint32_t words[2] = {mw.x >> (4 * h), mw.y >> (4 * h)};
-  constexpr int NS = D / 16;  // 16-dim contraction steps of S = K.Q^T
-  floatx16_t sacc[2];
-  {
-    bf16x8_t kf[2][NS];
-#if DLT_ATTN_KREAD_ASM
-    // all K fragments of the tile in flight at once, one counted wait per half
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int s = 0; s < NS; ++s) kf[t][s] = lds_row8_asm<D>(Kt, 32 * t + ql, 16 * s + 8 * h);
-    if constexpr (D == 64) {
-      lgkm_wait4(kf[0][0], kf[0][1], kf[0][2], kf[0][3]);
-    } else {
-      lgkm_wait8(kf[0][0], kf[0][1], kf[0][2], kf[0][3]);
-      pin4(kf[0][4], kf[0][5], kf[0][6], kf[0][7]);
-    }
-    sacc[0] = zero16();
-#pragma unroll
-    for (int s = 0; s < NS; ++s) sacc[0] = mfma<HK>(kf[0][s], qf[s], sacc[0]);
-    tr_wait_all(kf[1]);
-    sacc[1] = zero16();
-#pragma unroll
-    for (int s = 0; s < NS; ++s) sacc[1] = mfma<HK>(kf[1][s], qf[s], sacc[1]);
-#else
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      kf[0][s] = lds_row8<D>(Kt, ql, 16 * s + 8 * h);
-      kf[1][s] = lds_row8<D>(Kt, 32 + ql, 16 * s + 8 * h);
-    }
-    sacc[0] = zero16();
-    sacc[1] = zero16();
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      sacc[0] = mfma<HK>(kf[0][s], qf[s], sacc[0]);
-      sacc[1] = mfma<HK>(kf[1][s], qf[s], sacc[1]);
-    }
-#endif
-  }
-  if (MASK) {
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int ka = k0 + 32 * t + acc_row(i, h);
-        sacc[t][i] = (ka > qa || ka >= S || (DOC && ka < lo)) ? -INFINITY : sacc[t][i];
-      }
-  }
-  // row max as a depth-3 max3 tree per half (a linear fmaxf chain is 9 dependent ops)
-  const float mx = xhalf_max(fmaxf(max16(sacc[0]), max16(sacc[1])));
-  if (!__all((mx - fs.m) * c_log2 <= RESCALE_LOG2)) {  // rare: a row's max grew by > 2^8
-    const float m_new = fmaxf(fs.m, mx);
-    const float alpha = fast_exp2((fs.m - m_new) * c_log2);
-    fs.m = m_new;
-    fs.l *= alpha;
-#pragma unroll
-    for (int dt = 0; dt < D / 32; ++dt)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) fs.o[dt][i] *= alpha;
-  }
-  const float nmc = -fs.m * c_log2;
-  float l0 = 0.f, l1 = 0.f;
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    bf16x8_t vf[2][D / 32];
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-      for (int dt = 0; dt < D / 32; ++dt) vf[kk][dt] = tr_frag_asm<D>(Vt, 2 * t + kk, dt, lane);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const float p = fast_exp2(fmaf(sacc[t][i], c_log2, nmc));
-      if (i & 1) l1 += p;
-      else l0 += p;
-      if (DROP) sacc[t][i] = keep_and(p, keep_ones(words[t], (i & 3) + 8 * (i >> 2)));  // 1/(1-p) at the end
-      else sacc[t][i] = p;
-    }
-    if constexpr (D == 64) {
-      tr_wait(vf[0][0], vf[0][1], vf[1][0], vf[1][1]);
-    } else {
-      tr_wait(vf[0][0], vf[0][1], vf[0][2], vf[0][3]);
-      pin4(vf[1][0], vf[1][1], vf[1][2], vf[1][3]);
-    }
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const bf16x8_t pb = acc_frag<HK>(sacc[t], kk);
-#pragma unroll
-      for (int dt = 0; dt < D / 32; ++dt) fs.o[dt] = mfma<HK>(vf[kk][dt], pb, fs.o[dt]);
-    }
-  }
-  fs.l += l0 + l1;
-}
-
-// Work decomposition (causal balance): a workgroup = 2 waves = one 64-query item.
-// Default schedule (work_item, LPT): one item per workgroup, longest first, so the
-// short items fill in behind the long ones.  Alternative (DLT_ATTN_SCHED=pair): each
-// workgroup processes the PAIR of items (nrb-1-p, p), equal work per workgroup but
-// only ~1.5 long waves per SIMD -- a half-empty last round at 2 waves/SIMD (PMC:
-// ~1.1 resident waves per SIMD on average at B16).  Round 1 measured one item per
-// workgroup in the NATURAL order 1.8x slower than the pairing (equal-length items
-// stacked on a CU); longest-first does not stack them.
-// Forward diagnostics (tools/cpp/attn_fwd_timing.cpp, -DDLT_ATTN_FWD_TIMING only): per
-// wave, the shader cycles inside the tile compute and inside the per-tile DMA wait +
-// barrier, and the tile count, written by lane 0 with vector stores.
-#ifdef DLT_ATTN_FWD_TIMING
-__device__ unsigned long long* g_attn_ftim;
-#define FWD_T(v) const unsigned long long v = __builtin_amdgcn_s_memtime()
-#define FWD_ACC(c, w) (f_comp += (c), f_wait += (w), ++f_tiles)
-#else
-#define FWD_T(v) ((void)0)
-#define FWD_ACC(c, w) ((void)0)
-#endif
-
-// DOC tile range of the 64-query item qb (fwd, dQ).  lo is non-decreasing, so the
-// item's smallest / largest bound are those of its first / last valid query: two
-// workgroup-uniform loads, no reduction.  ks = first K/V tile any row needs, kdoc =
-// first tile at or above every row's bound; both clamped into the causal range
-// [0, qb], so the loop stays inside the sequence whatever the arrays hold.
-__device__ __forceinline__ void doc_q_range(const int* __restrict__ lrow, int qb, int S, int& ks, int& kdoc) {
-  const int lo_min = lrow[qb * RB], lo_max = lrow[min(S, qb * RB + RB) - 1];
-  ks = min(max(lo_min, 0) / KVB, qb);
-  kdoc = min((max(lo_max, 0) + KVB - 1) / KVB, qb);
-}
-// The mirror image for the 64-key item kblk of dK/dV: hi of its first / last valid key.
-// nqe = end of the query-tile loop (the tile after the one holding the largest hi),
-// t_unm = first tile that reaches past the smallest hi; clamped to (kblk, nqt].
-__device__ __forceinline__ void doc_k_range(const int* __restrict__ hrow, int kblk, int S, int nqt, int& nqe,
-                                            int& t_unm) {
-  const int hi_min = hrow[kblk * RB], hi_max = hrow[min(S, kblk * RB + RB) - 1];
-  nqe = min(max(hi_max / QSTEP, kblk) + 1, nqt);
-  t_unm = min(max(hi_min + 1, 0) / QSTEP, S / QSTEP);
-}
-
-// D = 128 doubles the O accumulators and Q / K / V fragments: 256 VGPRs would spill,
-// so its instantiation may take the whole 512-register file (one wave per SIMD).
-#define ATTN_WAVES(D) __attribute__((amdgpu_waves_per_eu(D == 64 ? 2 : 1, 2)))
 // DOC: dlo = lo [B, S] of the document mask (see the header); unused otherwise.
 // GQA: k / v have nh / G heads with their own strides (kv_bs, kv_hs, kv_rs); unused otherwise.
+// The body is attention_fwd_body.h, shared with the SINK forms of attention_sink.hip.
 template <bool DROP, int HK, int D, bool DOC = false, bool GQA = false>
 __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_fwd(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                     const bf16_t* __restrict__ v, bf16_t* __restrict__ o,
@@ -645,149 +192,11 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_fwd(const bf16_t* __r
                                                     int in_hs, int in_rs, int xcd_map,
                                                     const int* __restrict__ dlo = nullptr, int G = 1,
                                                     long kv_bs = 0, int kv_hs = 0, int kv_rs = 0) {
-  __shared__ __attribute__((aligned(16))) bf16_t lds[2 * 2 * KVB * D];  // [buf][K|V][64][D]
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int h = lane >> 5, ql = lane & 31;
-  const int nrb = (S + RB - 1) / RB;
-  int bh, pair;
-  const bool lpt = work_item(nrb, xcd_map, bh, pair);
-  const int b = bh / nh, head = bh % nh;
-  const size_t hin = (size_t)b * in_bs + (size_t)head * in_hs;  // (b, head) base of q / k / v
-  // GQA: k / v base of kv head head / G; everything else stays per query head
-  const size_t hkv = GQA ? (size_t)b * kv_bs + (size_t)(head / G) * kv_hs : hin;
-  const int krs = GQA ? kv_rs : in_rs;
-  const int W = (S + 31) >> 5;
-  using B0 = std::integral_constant<int, 0>;
-  using B1 = std::integral_constant<int, 1>;
-  using UNM = std::integral_constant<bool, false>;
-  using MSK = std::integral_constant<bool, true>;
-#ifdef DLT_ATTN_FWD_TIMING
-  unsigned long long f_comp = 0, f_wait = 0, f_tiles = 0;
-  const unsigned long long f_t0 = __builtin_amdgcn_s_memtime();
-#endif
-
-#pragma unroll 1
-  for (int it = 0; it < 2; ++it) {
-    const int qb = (lpt || it == 0) ? nrb - 1 - pair : pair;  // long item first
-    if (it == 1 && (lpt || qb >= nrb - 1 - pair)) break;       // odd nrb: middle item once
-    const int q0 = qb * RB + wid * 32;  // this wave's first query (wave-uniform)
-    const int qa = q0 + ql;
-    const uint32_t* mrow = mask ? mask + (size_t)bh * W * S + min(qa, S - 1) : nullptr;  // word j at mrow[j*S]
-
-    bf16x8_t qf[D / 16];
-#pragma unroll
-    for (int s = 0; s < D / 16; ++s)
-      qf[s] = load_row8(q + hin + (size_t)min(qa, S - 1) * in_rs + 16 * s + 8 * h, qa < S);
-
-    FwdState<D> fs;
-#pragma unroll
-    for (int dt = 0; dt < D / 32; ++dt) fs.o[dt] = zero16();
-    fs.m = DOC ? M_DEAD : -INFINITY;
-    fs.l = 0.f;
-
-    // DOC: this lane's bound, the wave's smallest (its first query's), and the item's
-    // tile range: the loop starts at tile ks, tiles below kdoc straddle some row's bound
-    int lo_q = 0, lo_w = 0, ks = 0, kdoc = 0;
-    if constexpr (DOC) {
-      const int* lrow = dlo + (size_t)b * S;
-      lo_q = lrow[min(qa, S - 1)];
-      lo_w = __builtin_amdgcn_readfirstlane(lo_q);
-      doc_q_range(lrow, qb, S, ks, kdoc);
-    }
-
-    const int nkv = (min(S, qb * RB + RB) + KVB - 1) / KVB;  // = qb + 1 except at a ragged end
-    glds_tile<D>(k + hkv, ks * KVB, S, krs, lds, wid, lane);
-    glds_tile<D>(v + hkv, ks * KVB, S, krs, lds + KVB * D, wid, lane);
-    __syncthreads();
-
-    // One K/V tile per step.  BUF is a compile-time LDS buffer index and MASKED a
-    // compile-time tile kind: tiles kb < qb lie entirely below every query of the
-    // item (straight-line unmasked loop, unrolled by two so every LDS address is
-    // lane-base + immediate); tile qb holds the diagonal.
-    uint2 mw_cur = make_uint2(0u, 0u), mw_next = make_uint2(0u, 0u);
-    if (DROP) {  // words of the first tile
-      if constexpr (DOC) mw_cur = make_uint2(mrow[(size_t)(2 * ks) * S], 2 * ks + 1 < W ? mrow[(size_t)(2 * ks + 1) * S] : 0u);
-      else mw_cur = make_uint2(mrow[0], W > 1 ? mrow[S] : 0u);
-    }
-    auto step = [&](auto bufc, auto maskc, int kb) {
-      constexpr int BUF = decltype(bufc)::value;
-      constexpr bool MASKED = decltype(maskc)::value;
-      FWD_T(ta);
-      const bool more = kb + 1 < nkv;
-      if (more) {  // next tile straight into the other buffer (read by nobody since the last barrier)
-        bf16_t* Kn = lds + (BUF ^ 1) * 2 * KVB * D;
-        glds_tile<D>(k + hkv, (kb + 1) * KVB, S, krs, Kn, wid, lane);
-        glds_tile<D>(v + hkv, (kb + 1) * KVB, S, krs, Kn + KVB * D, wid, lane);
-        if (DROP) mw_next = make_uint2(mrow[(size_t)(2 * (kb + 1)) * S], 2 * (kb + 1) + 1 < W ? mrow[(size_t)(2 * (kb + 1) + 1) * S] : 0u);
-      }
-      const bf16_t* Kt = lds + BUF * 2 * KVB * D;
-      const bf16_t* Vt = Kt + KVB * D;
-      const int k0 = kb * KVB;
-      if (!MASKED)
-        fwd_tile<false, DROP, HK, D>(fs, Kt, Vt, qf, k0, qa, S, lane, c_log2, mw_cur);
-      else if (k0 <= q0 + 31 && (!DOC || k0 + KVB > lo_w))  // DOC: not wholly below this wave's documents
-        fwd_tile<true, DROP, HK, D, DOC>(fs, Kt, Vt, qf, k0, qa, S, lane, c_log2, mw_cur, lo_q);
-      mw_cur = mw_next;
-      FWD_T(tb);
-      tile_barrier();
-      FWD_T(tc);
-      FWD_ACC(tb - ta, tc - tb);
-    };
-    const int nfull = min(qb, nkv);
-    if constexpr (DOC) {
-      // Tile kb sits in buffer (kb - ks) & 1.  [ks, kdoc): masked by some row's bound;
-      // [kdoc, nfull): unmasked; [nfull, nkv): the diagonal.  One body per (buffer, kind),
-      // picked by two wave-uniform scalar branches per tile.
-      for (int kb = ks; kb < nkv; ++kb) {
-        const bool msk = kb < kdoc || kb >= nfull;
-        if ((kb - ks) & 1) {
-          if (msk) step(B1{}, MSK{}, kb);
-          else step(B1{}, UNM{}, kb);
-        } else {
-          if (msk) step(B0{}, MSK{}, kb);
-          else step(B0{}, UNM{}, kb);
-        }
-      }
-    } else {
-      int kb = 0;
-      for (; kb + 1 < nfull; kb += 2) {
-        step(B0{}, UNM{}, kb);
-        step(B1{}, UNM{}, kb + 1);
-      }
-      if (kb < nfull) {  // odd count: last unmasked tile in buffer 0, diagonal in buffer 1
-        step(B0{}, UNM{}, kb);
-        if (kb + 1 < nkv) step(B1{}, MSK{}, kb + 1);
-      } else if (kb < nkv) {
-        step(B0{}, MSK{}, kb);
-      }
-    }
-
-    const float l_tot = xhalf_sum(fs.l);
-    const float inv_l = (DROP ? dscale : 1.f) / l_tot;
-    if (qa < S) {
-      if (h == 0) lse[(size_t)bh * S + qa] = fs.m * (c_log2 / LOG2E) + __logf(l_tot);
-      bf16_t* orow = o + (((size_t)b * S + qa) * nh + head) * D;
-      uint2 w[D / 32][4];
-#pragma unroll
-      for (int dt = 0; dt < D / 32; ++dt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          u16x4 t;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) t.v[e] = f2h<HK>(fs.o[dt][4 * g + e] * inv_l);
-          w[dt][g] = __builtin_bit_cast(uint2, t);
-        }
-      store_row16<D>(orow, w, h);
-    }
-  }
-#ifdef DLT_ATTN_FWD_TIMING
-  const unsigned long long f_t1 = __builtin_amdgcn_s_memtime();
-  if (lane == 0) {
-    unsigned long long* r = g_attn_ftim + ((size_t)blockIdx.x * 2 + wid) * 6;
-    r[0] = f_t0; r[1] = f_t1; r[2] = f_comp; r[3] = f_wait; r[4] = f_tiles;
-  }
-#endif
+  // the fragment reads this kernel's parameters and template arguments by name (its header
+  // lists them) plus these two; with SINK false it never reads `sink`
+  constexpr bool SINK = false;
+  const float* sink = nullptr;
+#include "attention_fwd_body.h"
 }
 
 // ============================================================================ backward
@@ -1428,47 +837,44 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_bwd_dq(const bf16_t* 
   }
 }
 
-// ============================================================================ launchers
-#include <cstdlib>
-// head_dim dispatch: HDC = 64 or 128 inside the body
-#define DLT_HD_DISPATCH(hd, ...) \
-  do {                           \
-    if ((hd) == 128) {           \
-      constexpr int HDC = 128;   \
-      __VA_ARGS__;               \
-    } else {                     \
-      constexpr int HDC = 64;    \
-      __VA_ARGS__;               \
-    }                            \
-  } while (0)
-static inline bool attn_hd_ok(int hd) { return hd == 64 || hd == 128; }
-// boolean dispatch: defines `constexpr bool NAME` = (cond) inside the body
-#define DLT_BOOL_DISPATCH(NAME, cond, ...) \
-  do {                                     \
-    if (cond) {                            \
-      constexpr bool NAME = true;          \
-      __VA_ARGS__;                         \
-    } else {                               \
-      constexpr bool NAME = false;         \
-      __VA_ARGS__;                         \
-    }                                      \
-  } while (0)
-// XCD-aware work map on by default; DLT_ATTN_XCD=0 restores the natural order (A/B).
-static int xcd_map_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("DLT_ATTN_XCD");
-    v = (e && atoi(e) == 0) ? 0 : 1;
-    // default: one item per workgroup, longest first (see work_item; measured B8 nh12
-    // S1024: fwd 63 -> 60 us incl. the keep bits, bwd 108 -> 96 us; B16: 117 -> 105,
-    // 218 -> 197); DLT_ATTN_SCHED=pair restores the paired items
-    const char* sch = getenv("DLT_ATTN_SCHED");
-    if (!(sch && sch[0] == 'p')) v |= 2;
+// ============================================================================ sink gradient
+// Gradient of the attention sinks (k_attn_fwd_sink, attention_sink.hip): with p_sink = exp(sink[h] - lse[b,h,q])
+// the sink column has dP = 0, so dS_sink = -p_sink * delta and
+//   dsink[h] += -sum_{b,q} p_sink[b,h,q] * delta[b,h,q],
+// delta the raw rowsum(dO * O) that dQ leaves in the workspace (the 1 / dscale of dK/dV is
+// not part of it).  One workgroup per head: thread t adds the rows t, t + SB_NT, ... of the
+// flattened (b, q) index in that order, then the partials are summed by a wave butterfly
+// and the waves in wave order through LDS.  No float atomics: two calls give the same bits,
+// and the one += per head makes a second call on the same inputs double the first exactly
+// (dsink = 0 before).
+#define SB_NT 1024
+__global__ __launch_bounds__(SB_NT) void k_attn_sink_bwd(const float* __restrict__ lse,
+                                                         const float* __restrict__ delta,
+                                                         const float* __restrict__ sink,
+                                                         float* __restrict__ dsink, int B, int nh, int S) {
+  __shared__ float part[SB_NT / 64];
+  const int head = blockIdx.x, tid = threadIdx.x;
+  const float sk = sink[head];
+  const long n = (long)B * S;
+  float acc = 0.f;
+  for (long i = tid; i < n; i += SB_NT) {
+    const long b = i / S, r = i - b * S;
+    const size_t at = ((size_t)b * nh + head) * S + r;
+    acc += fast_exp2((sk - lse[at]) * LOG2E) * delta[at];
   }
-  return v;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if ((tid & 63) == 0) part[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    float t = 0.f;
+#pragma unroll
+    for (int w = 0; w < SB_NT / 64; ++w) t += part[w];
+    dsink[head] -= t;
+  }
 }
-// grid of the MFMA kernels for a work schedule
-static inline int attn_grid(int nrb, int BH, int sched) { return (sched & 2) ? nrb * BH : ((nrb + 1) / 2) * BH; }
+
+// ============================================================================ launchers
 // mask: uint32 [2][B*nh, ceil(S/32), S] keep-bits written by the forward when dropout
 // is on -- [0] row layout (lane = query), [1] transposed (lane = key), see
 // k_dropout_bits.
@@ -1499,47 +905,7 @@ DLT_API int dlt_attn_dropout_mask_band(uint32_t* mask, int B, int nh, int S, uin
   DLT_CHECK_LAUNCH();
 }
 
-// One tensor's layout: element (b, head, row, d) lives at base + b*b + head*h + row*r + d.
-// Head-major [B*nh, S, hd]: {nh*S*hd, S*hd, hd}; inside the packed [B*S, 3H] QKV GEMM
-// output: {S*3H, hd, 3H} with k, v = q + H, q + 2H.
-struct dlt_attn_stride {
-  long b;
-  int h, r;
-};
-// Arguments of dlt_attn_fwd and dlt_attn_bwd; the forward ignores the backward's fields.
-struct dlt_attn_args {
-  const bf16_t *q, *k, *v;
-  bf16_t* o;    // [B*S, nh*hd]: written by the forward, read by the backward
-  float* lse;   // [B, nh, S], per query head
-  // uint32 [2][B*nh, ceil(S/32), S] keep bits, needed when thr != 0 -- [0] row layout
-  // (lane = query), [1] transposed (lane = key), see k_dropout_bits; per query head
-  uint32_t* mask;
-  const bf16_t* dout;
-  float* delta_ws;  // [B, nh, S] workspace: rowsum(dO * O), written by dQ for dK/dV
-  bf16_t *dq, *dk, *dv;
-  // document mask's bounds, int32 [B, S]; null = causal only.  The forward and dQ read lo,
-  // dK/dV reads hi: the backward takes both or neither
-  const int *lo, *hi;
-  // [>= S, 32] fp32, both or neither: the backward applies the inverse RoPE rotation to dq
-  // and dk in the store (the gradient w.r.t. the pre-rotation q/k of the packed QKV)
-  const float *cosT, *sinT;
-  int B, nh;
-  // 0: the MHA kernels.  > 0: the GQA kernels (also for nkv == nh) -- k / v, dk / dv hold nkv
-  // heads (nkv divides nh; query head h reads kv head h / (nh / nkv)) with the kv / dkv
-  // strides, which the MHA kernels do not read (k, v follow q's strides, dk, dv follow dq's)
-  int nkv;
-  int S, hd, hk;
-  float scale, dscale;
-  uint32_t key, thr;  // thr != 0: dropout on
-  int gen_mask;       // forward; 0: the keep bits are already in `mask` (dlt_attn_dropout_mask)
-  struct {
-    dlt_attn_stride q, kv, dq, dkv;
-  } stride;
-};
-// ops/hip.py mirrors the struct field by field: a field added on one side only must not load
-static_assert(sizeof(dlt_attn_args) == 232, "dlt_attn_args changed: update _AttnArgs in ops/hip.py");
 DLT_API int dlt_attn_args_size() { return (int)sizeof(dlt_attn_args); }
-static inline bool attn_stride_ok(const dlt_attn_stride& s, int m) { return !(s.r % m || s.h % m || s.b % m); }
 
 DLT_API int dlt_attn_fwd(const dlt_attn_args* a, hipStream_t st) {
   const int nh = a->nh, nkv = a->nkv, S = a->S;
@@ -1556,6 +922,7 @@ DLT_API int dlt_attn_fwd(const dlt_attn_args* a, hipStream_t st) {
     const int rc = dlt_attn_dropout_mask(a->mask, a->B, nh, S, a->key, a->thr, st);
     if (rc) return rc;
   }
+  if (a->sink) return attn_fwd_sink_launch(a, st);  // the SINK forms: attention_sink.hip
   DLT_BOOL_DISPATCH(DROPC, a->thr, DLT_BOOL_DISPATCH(GQAC, nkv, DLT_BOOL_DISPATCH(DOCC, a->lo,
       DLT_HD_DISPATCH(a->hd, DLT_HK_DISPATCH(a->hk, k_attn_fwd<DROPC, HKC, HDC, DOCC, GQAC><<<grid, NT, 0, st>>>(
           a->q, a->k, a->v, a->o, a->lse, DROPC ? a->mask : nullptr, S, nh, c_log2, a->dscale, sq.b, sq.h, sq.r, xm,
@@ -1572,6 +939,7 @@ DLT_API int dlt_attn_bwd(const dlt_attn_args* a, hipStream_t st) {
   const int G = nkv ? nh / nkv : 1;
   if (!attn_hd_ok(a->hd) || S <= 0 || !attn_stride_ok(sq, 8) || !attn_stride_ok(sdq, 4)) return -1;
   if ((a->cosT == nullptr) != (a->sinT == nullptr)) return -3;
+  if ((a->sink == nullptr) != (a->dsink == nullptr)) return -6;
   if (a->thr && !a->mask) return -2;
   const float scale = a->scale, dscale = a->dscale, c_log2 = scale * LOG2E;
   const int nrb = (S + RB - 1) / RB;
@@ -1599,5 +967,7 @@ DLT_API int dlt_attn_bwd(const dlt_attn_args* a, hipStream_t st) {
               a->q, a->k, a->v, a->dout, a->lse, a->delta_ws, maskT, a->dk, a->dv, S, nh, c_log2, scale, dscale, sq.b,
               sq.h, sq.r, sdq.b, sdq.h, sdq.r, a->cosT, a->sinT, xm, a->hi))));
   });
+  // the sink gradient reads lse and the delta dQ has just written (same stream)
+  if (a->sink) k_attn_sink_bwd<<<nh, SB_NT, 0, st>>>(a->lse, a->delta_ws, a->sink, a->dsink, a->B, nh, S);
   DLT_CHECK_LAUNCH();
 }

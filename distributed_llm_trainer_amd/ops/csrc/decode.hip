@@ -238,11 +238,14 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_norm_qkv(const float* __restrict
 // WIN (sliding window of `win` keys): the keys are kf..pos, kf = max(0, pos - win + 1); K, V
 // and the score index start at kf, so sc[] holds min(win, maxS) scores and the code below
 // the prologue is the same.
+// sink (nullable, fp32 [nh]): the head's attention-sink logit, one more term of the softmax
+// denominator with no value row.  It joins the max after the reduction and the sum before the
+// reciprocal; a null pointer leaves every instruction's inputs as they were.
 template <bool WIN = false>
 __global__ __launch_bounds__(DEC_NT) void k_dec_attn(const bf16_t* __restrict__ q, const bf16_t* __restrict__ kc,
                                                      const bf16_t* __restrict__ vc, const long* __restrict__ posp,
                                                      bf16_t* __restrict__ o, int H, int nh, int maxS, float scale,
-                                                     int win = 0) {
+                                                     int win = 0, const float* __restrict__ sink = nullptr) {
   extern __shared__ __attribute__((aligned(16))) char dsm[];
   float* sc = reinterpret_cast<float*>(dsm);       // [maxS] scores -> probabilities (WIN: [min(win, maxS)])
   float* red = sc + (WIN ? min(win, maxS) : maxS); // [8]
@@ -280,6 +283,8 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_attn(const bf16_t* __restrict__ 
   if (lane == 0) red[wid] = mx;
   __syncthreads();
   mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  const float sk = sink ? sink[head] : -INFINITY;
+  if (sink) mx = fmaxf(mx, sk);
   float sum = 0.f;
   for (int j = tid; j < len; j += DEC_NT) {
     const float p = __expf(sc[j] - mx);
@@ -290,7 +295,9 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_attn(const bf16_t* __restrict__ 
   __syncthreads();  // every red[] max read before it is overwritten
   if (lane == 0) red[4 + wid] = sum;
   __syncthreads();
-  const float inv = 1.f / (red[4] + red[5] + red[6] + red[7]);
+  float den = red[4] + red[5] + red[6] + red[7];
+  if (sink) den += __expf(sk - mx);
+  const float inv = 1.f / den;
   // o[d] = sum_j p_j v_j[d]: lane (js, dc) = (tid / 8, tid % 8) loads dims 8dc..8dc+7 of
   // keys j = js, js + 32, ... (16-byte loads, all in flight), then the 32 key slots are
   // summed: 3 xor-shuffle steps inside the wave, the 4 waves through LDS.
@@ -339,11 +346,15 @@ constexpr int GQA_GMAX = 16;  // query heads per workgroup (128 accumulator regi
 // WIN (sliding window of `win` keys): the chunks are anchored at the window's first key
 // kf = max(0, pos - win + 1): chunk s is [kf + s C, min(kf + (s + 1) C, pos + 1)) with C fixed on
 // the host from min(win, maxS), so a window shorter than maxS / NS still feeds every workgroup.
+// sink (nullable, fp32 [nh], per QUERY head): with NS == 1 it joins each head's max after the
+// reduction and its sum before the reciprocal, as in k_dec_attn; with NS > 1 the chunk
+// workgroups leave it out and k_dec_attn_combine adds it once.  Null: nothing changes.
 template <int GT, bool WIN = false>
 __global__ __launch_bounds__(DEC_NT) void k_dec_attn_gqa(const bf16_t* __restrict__ q, const bf16_t* __restrict__ kc,
                                                          const bf16_t* __restrict__ vc, const long* __restrict__ posp,
                                                          bf16_t* __restrict__ o, float* __restrict__ ws, int H, int nh,
-                                                         int nkv, int maxS, int NS, int C, float scale, int win = 0) {
+                                                         int nkv, int maxS, int NS, int C, float scale, int win = 0,
+                                                         const float* __restrict__ sink = nullptr) {
   extern __shared__ __attribute__((aligned(16))) char dsm[];
   float* red = reinterpret_cast<float*>(dsm);  // [2][4][GT] per-wave max, sum
   float* oacc = red + 8 * GT;                  // [4][GT][64]
@@ -438,6 +449,7 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_attn_gqa(const bf16_t* __restric
 #pragma unroll
   for (int g = 0; g < GT; ++g) {
     mx[g] = fmaxf(fmaxf(red[g], red[GT + g]), fmaxf(red[2 * GT + g], red[3 * GT + g]));
+    if (sink && NS == 1) mx[g] = fmaxf(mx[g], sink[h0 + min(g, Gl - 1)]);  // a padded head repeats the last
     sum[g] = 0.f;
   }
   for (int j = tid; j < n; j += DEC_NT) {  // the thread's own scores: no barrier since the writes
@@ -509,7 +521,13 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_attn_gqa(const bf16_t* __restric
     const int g = i >> 6;
     const float r = oacc[i] + oacc[GT * 64 + i] + oacc[2 * GT * 64 + i] + oacc[3 * GT * 64 + i];
     if (NS == 1) {
-      const float inv = 1.f / (red[4 * GT + g] + red[5 * GT + g] + red[6 * GT + g] + red[7 * GT + g]);
+      float den = red[4 * GT + g] + red[5 * GT + g] + red[6 * GT + g] + red[7 * GT + g];
+      if (sink) {  // the head's max as the softmax above took it
+        const float sk = sink[h0 + g];
+        const float m = fmaxf(fmaxf(fmaxf(red[g], red[GT + g]), fmaxf(red[2 * GT + g], red[3 * GT + g])), sk);
+        den += __expf(sk - m);
+      }
+      const float inv = 1.f / den;
       o[(size_t)b * H + h0 * 64 + i] = f2bf(r * inv);
     } else {
       ws[(((size_t)b * nh + h0 + g) * NS + s) * GQA_WS + (i & 63)] = r;
@@ -525,11 +543,16 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_attn_gqa(const bf16_t* __restric
 // grid (B * nh), one wave: lane = dim.  The NS partials of a (b, query head) are merged in
 // the fixed order s = 0 .. NS - 1, each rescaled by exp(m_s - M); an empty chunk (l == 0) is
 // skipped without reading its o.  No atomics and no arrival order: the same bits every run.
+// sink (nullable, fp32 [nh]): the query head's sink logit enters here ONCE, as one more
+// partial with l = 1 and no o: M = max(M, sink), L += exp(sink - M).
 __global__ __launch_bounds__(64) void k_dec_attn_combine(const float* __restrict__ ws, bf16_t* __restrict__ o,
-                                                         int NS) {
+                                                         int NS, const float* __restrict__ sink = nullptr,
+                                                         int nh = 1) {
   const float* w = ws + (size_t)blockIdx.x * NS * GQA_WS;
   float M = -INFINITY;
   for (int s = 0; s < NS; ++s) M = fmaxf(M, w[s * GQA_WS + 64]);
+  const float sk = sink ? sink[blockIdx.x % nh] : -INFINITY;
+  if (sink) M = fmaxf(M, sk);
   float L = 0.f, r = 0.f;
   for (int s = 0; s < NS; ++s) {
     const float l = w[s * GQA_WS + 65];
@@ -539,6 +562,7 @@ __global__ __launch_bounds__(64) void k_dec_attn_combine(const float* __restrict
       r = fmaf(w[s * GQA_WS + threadIdx.x], f, r);
     }
   }
+  if (sink) L += __expf(sk - M);
   o[(size_t)blockIdx.x * 64 + threadIdx.x] = f2bf(r / L);
 }
 
@@ -1045,7 +1069,7 @@ static int dec_attn_chunk(int maxS, int NS) { return (maxS + NS - 1) / NS; }
 // divide min(window, maxS) keys, anchored at the window (k_dec_attn_gqa<GT, true>).
 static int dec_attn_gqa_launch(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const long* pos, bf16_t* o,
                                float* ws, int B, int H, int nh, int nkv, int maxS, int NS, float scale, int window,
-                               hipStream_t st) {
+                               hipStream_t st, const float* sink = nullptr) {
   if (B < 1 || H != nh * 64 || nkv < 1 || nh % nkv || maxS < 1 || window < 0) return -1;
   if ((NS != 1 && NS != 2 && NS != 4 && NS != 8) || (NS > 1 && !ws)) return -1;
   const int G = nh / nkv, Gw = G < GQA_GMAX ? G : GQA_GMAX, GS = (G + GQA_GMAX - 1) / GQA_GMAX;
@@ -1061,9 +1085,10 @@ static int dec_attn_gqa_launch(const bf16_t* q, const bf16_t* kc, const bf16_t* 
   case GG:                                                                                                      \
     if (window > 0)                                                                                             \
       k_dec_attn_gqa<GG, true><<<grid, DEC_NT, lds, st>>>(q, kc, vc, pos, o, ws, H, nh, nkv, maxS, NS, C,      \
-                                                          scale, window);                                      \
+                                                          scale, window, sink);                                \
     else                                                                                                        \
-      k_dec_attn_gqa<GG><<<grid, DEC_NT, lds, st>>>(q, kc, vc, pos, o, ws, H, nh, nkv, maxS, NS, C, scale);     \
+      k_dec_attn_gqa<GG><<<grid, DEC_NT, lds, st>>>(q, kc, vc, pos, o, ws, H, nh, nkv, maxS, NS, C, scale, 0,   \
+                                                    sink);                                                      \
     break
   switch (GT) {
     L(1);
@@ -1076,7 +1101,7 @@ static int dec_attn_gqa_launch(const bf16_t* q, const bf16_t* kc, const bf16_t* 
     L(16);
   }
 #undef L
-  if (NS > 1) k_dec_attn_combine<<<B * nh, 64, 0, st>>>(ws, o, NS);
+  if (NS > 1) k_dec_attn_combine<<<B * nh, 64, 0, st>>>(ws, o, NS, sink, nh);
   DLT_CHECK_LAUNCH();
 }
 
@@ -1091,6 +1116,14 @@ DLT_API int dlt_dec_attn_gqa_win(const bf16_t* q, const bf16_t* kc, const bf16_t
                                  hipStream_t st) {
   if (window < 1) return -1;
   return dec_attn_gqa_launch(q, kc, vc, pos, o, ws, B, H, nh, nkv, maxS, NS, scale, window, st);
+}
+
+// The grouped-query step with attention sinks: sink fp32 [nh] (one logit per query head, null =
+// none); window 0 = every key up to pos, else dlt_dec_attn_gqa_win's.
+DLT_API int dlt_dec_attn_gqa_sink(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const long* pos, bf16_t* o,
+                                  float* ws, int B, int H, int nh, int nkv, int maxS, int NS, float scale, int window,
+                                  const float* sink, hipStream_t st) {
+  return dec_attn_gqa_launch(q, kc, vc, pos, o, ws, B, H, nh, nkv, maxS, NS, scale, window, st, sink);
 }
 
 DLT_API int dlt_dec_attn(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const long* pos, bf16_t* o, int B,
@@ -1109,6 +1142,19 @@ DLT_API int dlt_dec_attn_win(const bf16_t* q, const bf16_t* kc, const bf16_t* vc
   const size_t lds = (size_t)(window < maxS ? window : maxS) * 4 + 8 * 4 + 4 * 64 * 4;
   if (H != nh * 64 || lds > 160 * 1024) return -1;
   k_dec_attn<true><<<B * nh, DEC_NT, lds, st>>>(q, kc, vc, pos, o, H, nh, maxS, scale, window);
+  DLT_CHECK_LAUNCH();
+}
+
+// dlt_dec_attn / dlt_dec_attn_win (window 0 / >= 1) with attention sinks: sink fp32 [nh], null = none.
+DLT_API int dlt_dec_attn_sink(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const long* pos, bf16_t* o, int B,
+                              int H, int nh, int maxS, float scale, int window, const float* sink, hipStream_t st) {
+  if (window < 0 || maxS < 1 || B < 1) return -1;
+  const size_t lds = (size_t)(window > 0 && window < maxS ? window : maxS) * 4 + 8 * 4 + 4 * 64 * 4;
+  if (H != nh * 64 || lds > 160 * 1024) return -1;
+  if (window > 0)
+    k_dec_attn<true><<<B * nh, DEC_NT, lds, st>>>(q, kc, vc, pos, o, H, nh, maxS, scale, window, sink);
+  else
+    k_dec_attn<><<<B * nh, DEC_NT, lds, st>>>(q, kc, vc, pos, o, H, nh, maxS, scale, 0, sink);
   DLT_CHECK_LAUNCH();
 }
 

@@ -99,6 +99,10 @@ _SIGS = {
                          c_void_p],
     "dlt_dec_attn_gqa_win": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                              c_int, c_int, c_float, c_int, c_void_p],
+    "dlt_dec_attn_sink": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int,
+                          c_void_p, c_void_p],
+    "dlt_dec_attn_gqa_sink": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                              c_int, c_int, c_float, c_int, c_void_p, c_void_p],
     "dlt_dec_gemv_res": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "dlt_dec_norm_gu": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "dlt_dec_norm_head": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
@@ -175,14 +179,40 @@ def _dec_window(window, name: str) -> int:
     return window
 
 
-def dec_attn(q, kc, vc, pos, o_out, scale, window=0):
+def _dec_sink(sink, nh: int, device, name: str) -> torch.Tensor:
+    """``sink`` of the decode attention wrappers: the layer's attention-sink logits, one per
+    query head, as the kernels read them (fp32 [nh] on the caches' device; a 16-bit tensor is
+    upcast).  Under a captured graph pass the fp32 parameter itself, so replays read it."""
+    if not isinstance(sink, torch.Tensor) or not sink.is_floating_point() or tuple(sink.shape) != (nh,):
+        raise ValueError(f"{name}: sink must be a floating-point [{nh}] tensor (one logit per query head)")
+    if sink.device != device:
+        raise ValueError(f"{name}: sink must be on {device}, got {sink.device}")
+    if sink.dtype != torch.float32:
+        sink = sink.float()
+    if not sink.is_contiguous() or sink.data_ptr() % 4:
+        sink = sink.contiguous().clone()
+    return sink
+
+
+def dec_attn(q, kc, vc, pos, o_out, scale, window=0, sink=None):
     """Decode attention of a multi-head model over keys 0..pos of the caches [B, nh, maxS, 64];
-    ``window`` = W > 0: over keys max(0, pos - W + 1)..pos only (a sliding-window layer)."""
+    ``window`` = W > 0: over keys max(0, pos - W + 1)..pos only (a sliding-window layer).
+    ``sink`` (fp32 [nh]): attention sinks, one more softmax logit per head with no value row."""
     window = _dec_window(window, "dec_attn")
     B, nh, maxS, hd = kc.shape
     H = nh * hd
     _req(q, torch.bfloat16, "dec.q", B * H)
     _req(o_out, torch.bfloat16, "dec.o", B * H)
+    if sink is not None:
+        sink = _dec_sink(sink, nh, kc.device, "dec_attn")
+        if hd != 64 or vc.shape != kc.shape:
+            raise ValueError("dec_attn: caches must be [B, nh, maxS, 64]")
+        _req(kc, torch.bfloat16, "dec.k_cache")
+        _req(vc, torch.bfloat16, "dec.v_cache")
+        _req(pos, torch.int64, "dec.pos", 1)
+        _chk(lib().dlt_dec_attn_sink(_p(q), _p(kc), _p(vc), _p(pos), _p(o_out), B, H, nh, maxS, float(scale), window,
+                                     _p(sink), _stream()), "dec_attn_sink")
+        return
     if window:
         if hd != 64 or vc.shape != kc.shape:
             raise ValueError("dec_attn: caches must be [B, nh, maxS, 64]")
@@ -241,13 +271,15 @@ def dec_attn_gqa_workspace(B: int, nh: int, splits: int, device) -> torch.Tensor
     return torch.empty(B * nh * splits * DEC_ATTN_WS, dtype=torch.float32, device=device)
 
 
-def dec_attn_gqa(q, kc, vc, pos, o_out, scale, nh, splits=1, ws=None, window=0):
+def dec_attn_gqa(q, kc, vc, pos, o_out, scale, nh, splits=1, ws=None, window=0, sink=None):
     """Decode attention of a grouped-query model: q, o_out [B, nh * 64] bf16, caches
     [B, nkv, maxS, 64]; every K/V row is read once for the nh / nkv query heads of its group.
     ``splits`` > 1 divides the keys over that many workgroups per K/V head (chunks of
     :func:`dec_attn_chunk`) and merges their partials, in order, through ``ws``
     (:func:`dec_attn_gqa_workspace`).  ``window`` = W > 0: keys max(0, pos - W + 1)..pos only,
-    in chunks of ``dec_attn_chunk(min(W, maxS), splits)`` anchored at the window's first key."""
+    in chunks of ``dec_attn_chunk(min(W, maxS), splits)`` anchored at the window's first key.
+    ``sink`` (fp32 [nh], per query head): attention sinks; with ``splits`` > 1 the merge adds the
+    sink once."""
     window = _dec_window(window, "dec_attn_gqa")
     if kc.dim() != 4 or kc.shape[3] != 64 or vc.shape != kc.shape:
         raise ValueError("dec_attn_gqa: caches must be [B, nkv, maxS, 64]")
@@ -266,6 +298,12 @@ def dec_attn_gqa(q, kc, vc, pos, o_out, scale, nh, splits=1, ws=None, window=0):
         if ws is None:
             raise ValueError("dec_attn_gqa: splits > 1 needs a workspace (dec_attn_gqa_workspace)")
         _req(ws, torch.float32, "dec.attn_ws", B * nh * splits * DEC_ATTN_WS)
+    if sink is not None:
+        sink = _dec_sink(sink, nh, kc.device, "dec_attn_gqa")
+        _chk(lib().dlt_dec_attn_gqa_sink(_p(q), _p(kc), _p(vc), _p(pos), _p(o_out), _p(ws if splits > 1 else None), B,
+                                         H, nh, nkv, maxS, splits, float(scale), window, _p(sink), _stream()),
+             "dec_attn_gqa_sink")
+        return
     if window:
         _chk(lib().dlt_dec_attn_gqa_win(_p(q), _p(kc), _p(vc), _p(pos), _p(o_out), _p(ws if splits > 1 else None), B,
                                         H, nh, nkv, maxS, splits, float(scale), window, _stream()),
@@ -832,7 +870,7 @@ class _AttnArgs(ctypes.Structure):
                                          "lo", "hi", "cosT", "sinT")]
                 + [(n, c_int) for n in ("B", "nh", "nkv", "S", "hd", "hk")]
                 + [("scale", c_float), ("dscale", c_float), ("key", c_uint32), ("thr", c_uint32),
-                   ("gen_mask", c_int), ("stride", _AttnStrides)])
+                   ("gen_mask", c_int), ("stride", _AttnStrides), ("sink", c_void_p), ("dsink", c_void_p)])
 
 
 def _keep_bits_fwd(p, mask, B, nh, S, device, key=0, window=None):
@@ -880,33 +918,65 @@ def _attn_name(name, nkv, doc):
     return name + ("_gqa" if nkv is not None else "" if doc is None else "_doc")
 
 
-def _attn_fwd_launch(name, src, o, lse, keep, key, lo, B, nh, nkv, S, hd, hk, scale):
+def _attn_sink(sink, nh: int, device, name: str, grad: bool = False):
+    """``sink=`` / ``dsink=`` of the attention wrappers (None passes): the attention-sink
+    logits, one per query head, as the kernels read them -- fp32 [nh], contiguous, on the
+    activations' device.  A 16-bit ``sink`` (a gathered FSDP unit) is upcast, nh elements;
+    ``dsink`` is the fp32 accumulator itself (``grad``) and is never copied."""
+    if sink is None:
+        return None
+    if not isinstance(sink, torch.Tensor) or not sink.is_cuda or not sink.is_floating_point() \
+            or tuple(sink.shape) != (nh,):
+        raise ValueError(f"{name}: expected a floating-point GPU tensor of shape [{nh}] (one logit per query head)")
+    if sink.device != device:
+        raise ValueError(f"{name}: expected device {device}, got {sink.device}")
+    if grad:
+        if sink.dtype != torch.float32 or not sink.is_contiguous():
+            raise ValueError(f"{name}: expected a contiguous fp32 tensor")
+        return sink
+    if sink.dtype != torch.float32:
+        sink = sink.float()
+    if not sink.is_contiguous():
+        sink = sink.contiguous()
+    return sink
+
+
+def _no_sink_f32(sink, name: str):
+    if sink is not None:
+        raise NotImplementedError(f"{name}: attention sinks are not implemented for fp32 activations on the GPU")
+
+
+def _attn_fwd_launch(name, src, o, lse, keep, key, lo, B, nh, nkv, S, hd, hk, scale, sink=None):
     """dlt_attn_fwd on q / k / v of layout ``src`` (:func:`_head_major`, :func:`_packed_row`)
-    with ``keep`` of :func:`_keep_bits_fwd`; nkv None: the MHA kernels."""
+    with ``keep`` of :func:`_keep_bits_fwd`; nkv None: the MHA kernels; ``sink``: the SINK forms."""
     (q, k, v), sq, skv = src
     thr, dscale, mask, gen = keep
     a = _AttnArgs(q=q, k=k, v=v, o=_p(o), lse=_p(lse), mask=_p(mask), lo=_p(lo), B=B, nh=nh, nkv=nkv or 0, S=S,
                   hd=hd, hk=hk, scale=scale, dscale=dscale, key=key & 0xFFFFFFFF, thr=thr, gen_mask=int(gen == 1),
-                  stride=_AttnStrides(q=sq, kv=skv))
+                  stride=_AttnStrides(q=sq, kv=skv), sink=_p(sink))
     _chk(lib().dlt_attn_fwd(ctypes.byref(a), _stream()), _attn_name(name, nkv, lo))
 
 
-def _attn_bwd_launch(name, src, dst, o, do, lse, keep, doc, rope, B, nh, nkv, S, hd, hk, scale):
+def _attn_bwd_launch(name, src, dst, o, do, lse, keep, doc, rope, B, nh, nkv, S, hd, hk, scale, sink=None,
+                     dsink=None):
     """dlt_attn_bwd: dq / dk / dv into layout ``dst``; ``keep`` of :func:`_keep_bits_bwd`,
-    ``doc`` = (lo, hi), ``rope`` = (cos, sin) or (None, None)."""
+    ``doc`` = (lo, hi), ``rope`` = (cos, sin) or (None, None).  With ``sink`` / ``dsink`` the
+    launch ends with k_attn_sink_bwd, which reads lse and the delta workspace dQ wrote."""
     (q, k, v), sq, skv = src
     (dq, dk, dv), sdq, sdkv = dst
     thr, dscale, mask = keep
+    if (sink is None) != (dsink is None):
+        raise ValueError(f"{name}: sink and dsink go together")
     delta = torch.empty(B, nh, S, dtype=torch.float32, device=lse.device)
     a = _AttnArgs(q=q, k=k, v=v, o=_p(o), lse=_p(lse), mask=_p(mask), dout=_p(do), delta_ws=_p(delta), dq=dq, dk=dk,
                   dv=dv, lo=_p(doc[0]), hi=_p(doc[1]), cosT=_p(rope[0]), sinT=_p(rope[1]), B=B, nh=nh, nkv=nkv or 0,
                   S=S, hd=hd, hk=hk, scale=scale, dscale=dscale, thr=thr,
-                  stride=_AttnStrides(q=sq, kv=skv, dq=sdq, dkv=sdkv))
+                  stride=_AttnStrides(q=sq, kv=skv, dq=sdq, dkv=sdkv), sink=_p(sink), dsink=_p(dsink))
     _chk(lib().dlt_attn_bwd(ctypes.byref(a), _stream()), _attn_name(name, nkv, doc[0]))
 
 
 def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=None, scale=None, doc=None,
-                  nkv=None, window=None):
+                  nkv=None, window=None, sink=None):
     """Returns (o [B*S, nh*hd] bf16, aux).  With dropout on, the keep bits are written
     to a bitmask consumed by attention_bwd (no re-hashing in the backward); pass
     ``mask`` from ``attention_dropout_mask`` to skip generating it here.  ``scale``:
@@ -916,9 +986,12 @@ def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=
     attention: k, v [B, nkv, S, hd] with nkv dividing nh (or ``nkv=`` given: the GQA kernels
     also for nkv == nh).  ``window`` = W: sliding-window attention, query q sees the keys
     q - W < k <= q (of its document); it runs on the DOC kernels with the bounds of
-    :func:`window_bounds`, and keep bits made here are the banded ones."""
+    :func:`window_bounds`, and keep bits made here are the banded ones.  ``sink`` (fp32 [nh]):
+    attention sinks, one more logit per query head in the softmax denominator (not scaled, no
+    value row; the SINK kernels); the returned lse holds it."""
     nkv = _head_major_nkv(q, k, v, nkv, "attn")
     if q.dtype == torch.float32:
+        _no_sink_f32(sink, "attention_fwd")
         from . import hip_f32
         if window is not None:
             hip_f32._no_window()
@@ -939,7 +1012,8 @@ def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=
     lse = torch.empty(B, nh, S, dtype=torch.float32, device=q.device)
     keep = _keep_bits_fwd(p, mask, B, nh, S, q.device, key, window)
     sc = 1.0 / math.sqrt(hd) if scale is None else float(scale)
-    _attn_fwd_launch("attn_fwd", _head_major(q, k, v), o, lse, keep, key, lo, B, nh, nkv, S, hd, hk, sc)
+    sink = _attn_sink(sink, nh, q.device, "attn.sink")
+    _attn_fwd_launch("attn_fwd", _head_major(q, k, v), o, lse, keep, key, lo, B, nh, nkv, S, hd, hk, sc, sink)
     return o, AttnAux((lse, keep[2] if (store_mask or not keep[3]) else None))
 
 
@@ -958,12 +1032,13 @@ def _packed_dims(qkv, B, S, nh, nkv=None):
 
 
 def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=True, doc=None, nkv=None,
-                         window=None):
+                         window=None, sink=None):
     """Causal attention reading q/k/v straight from the packed (roped) [B*S, 3H] QKV.
     Returns (o [B*S, H] bf16, aux) like :func:`attention_fwd`.  With ``nkv`` (grouped-query
     attention) the packed row is [H + 2*KV]; lse and the keep bits stay per query head.
-    ``window``: see :func:`attention_fwd`."""
+    ``window``, ``sink``: see :func:`attention_fwd`."""
     if qkv.dtype == torch.float32:
+        _no_sink_f32(sink, "attention_fwd_packed")
         if nkv is not None:
             _no_gqa_f32("attention_fwd_packed")
         from . import hip_f32
@@ -978,18 +1053,24 @@ def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=
     _req(o, qkv.dtype, "attn.o", M * H)
     lse = torch.empty(B, nh, S, dtype=torch.float32, device=qkv.device)
     keep = _keep_bits_fwd(p, mask, B, nh, S, qkv.device, key, window)
+    sink = _attn_sink(sink, nh, qkv.device, "attn.sink")
     _attn_fwd_launch("attn_fwd_packed", _packed_row(qkv, S, H, hd, KV), o, lse, keep, key, lo, B, nh, nkv, S, hd,
-                     _HK[qkv.dtype], 1.0 / math.sqrt(hd))
+                     _HK[qkv.dtype], 1.0 / math.sqrt(hd), sink)
     return o, AttnAux((lse, keep[2] if (store_mask or not keep[3]) else None))
 
 
-def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, doc=None, nkv=None, window=None):
+def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, doc=None, nkv=None, window=None,
+                         sink=None, dsink=None):
     """Backward of :func:`attention_fwd_packed` + the in-place RoPE: returns dqkv
     [B*S, 3H] (gradient w.r.t. the pre-rotation QKV GEMM output); dq/dk/dv are written
     into it by the attention kernels with the inverse rotation in their epilogue.  With
     ``nkv`` qkv and dqkv are [B*S, H + 2*KV]; dk / dv are summed over each group's query
-    heads in registers, in a fixed order.  ``window``: the forward's."""
+    heads in registers, in a fixed order.  ``window``: the forward's.  ``sink`` / ``dsink`` (fp32
+    [nh], both or neither): the forward's sinks and their gradient accumulator,
+    ``dsink[h] += -sum_{b,q} exp(sink[h] - lse) * rowsum(dO * O)`` in a fixed order (no atomics);
+    dq / dk / dv need only the forward's lse."""
     if qkv.dtype == torch.float32:
+        _no_sink_f32(sink, "attention_bwd_packed")
         if nkv is not None:
             _no_gqa_f32("attention_bwd_packed")
         from . import hip_f32
@@ -1011,16 +1092,20 @@ def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, 
     keep = _keep_bits_bwd(p, key, mask, B, nh, S, qkv.device, window)
     dqkv = torch.empty(M, Wd, dtype=qkv.dtype, device=qkv.device) if out is None else out
     _req(dqkv, qkv.dtype, "attn_bwd.dqkv", M * Wd)
+    sink = _attn_sink(sink, nh, qkv.device, "attn_bwd.sink")
+    dsink = _attn_sink(dsink, nh, qkv.device, "attn_bwd.dsink", grad=True)
     _attn_bwd_launch("attn_bwd_packed", _packed_row(qkv, S, H, hd, KV), _packed_row(dqkv, S, H, hd, KV), o, do, lse,
-                     keep, (lo, hi), (cos, sin), B, nh, nkv, S, hd, _HK[qkv.dtype], 1.0 / math.sqrt(hd))
+                     keep, (lo, hi), (cos, sin), B, nh, nkv, S, hd, _HK[qkv.dtype], 1.0 / math.sqrt(hd), sink, dsink)
     return dqkv
 
 
-def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, scale=None, doc=None, nkv=None, window=None):
+def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, scale=None, doc=None, nkv=None, window=None,
+                  sink=None, dsink=None):
     """Returns dq [B, nh, S, hd] and dk, dv in k's shape ([B, nkv, S, hd] under grouped-query
-    attention, see :func:`attention_fwd`)."""
+    attention, see :func:`attention_fwd`).  ``sink`` / ``dsink``: see :func:`attention_bwd_packed`."""
     nkv = _head_major_nkv(q, k, v, nkv, "attn_bwd")
     if q.dtype == torch.float32:
+        _no_sink_f32(sink, "attention_bwd")
         from . import hip_f32
         if window is not None:
             hip_f32._no_window()
@@ -1041,8 +1126,10 @@ def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, scale=None, doc=None
     dk = torch.empty_like(k)
     dv = torch.empty_like(v)
     sc = 1.0 / math.sqrt(hd) if scale is None else float(scale)
+    sink = _attn_sink(sink, nh, q.device, "attn_bwd.sink")
+    dsink = _attn_sink(dsink, nh, q.device, "attn_bwd.dsink", grad=True)
     _attn_bwd_launch("attn_bwd", _head_major(q, k, v), _head_major(dq, dk, dv), o, do, lse, keep, (lo, hi),
-                     (None, None), B, nh, nkv, S, hd, hk, sc)
+                     (None, None), B, nh, nkv, S, hd, hk, sc, sink, dsink)
     return dq, dk, dv
 
 

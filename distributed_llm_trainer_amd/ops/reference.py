@@ -213,18 +213,18 @@ def _split_packed(qkv, B, S, nh, nkv=None):
 
 
 def attention_fwd_packed(qkv: torch.Tensor, B: int, S: int, nh: int, p: float, key: int, out=None, mask=None,
-                         doc=None, nkv=None, window=None):
+                         doc=None, nkv=None, window=None, sink=None):
     """Causal attention straight on the (already roped) packed [B*S, H + 2*KV] QKV."""
     q, k, v = _split_packed(qkv, B, S, nh, nkv)
-    return attention_fwd(q, k, v, p, key, True, out=out, doc=doc, window=window)
+    return attention_fwd(q, k, v, p, key, True, out=out, doc=doc, window=window, sink=sink)
 
 
 def attention_bwd_packed(qkv, o, do, lse, p: float, key: int, B: int, S: int, nh: int,
                          cos: torch.Tensor, sin: torch.Tensor, out=None, doc=None, nkv=None,
-                         window=None) -> torch.Tensor:
+                         window=None, sink=None, dsink=None) -> torch.Tensor:
     """Backward of attention_fwd_packed + the in-place RoPE: dqkv [B*S, H + 2*KV] (pre-RoPE)."""
     q, k, v = _split_packed(qkv, B, S, nh, nkv)
-    dq, dk, dv = attention_bwd(q, k, v, o, do, lse, p, key, True, doc=doc, window=window)
+    dq, dk, dv = attention_bwd(q, k, v, o, do, lse, p, key, True, doc=doc, window=window, sink=sink, dsink=dsink)
     res = rope_qkv_bwd(dq.float(), dk.float(), dv.float(), cos, sin).to(qkv.dtype)
     if out is not None:
         out.copy_(res)
@@ -342,12 +342,28 @@ def _rep_kv(t: torch.Tensor, G: int) -> torch.Tensor:
     return t if G == 1 else t.repeat_interleave(G, dim=1)
 
 
+def _check_sink(sink, nh: int, device, name: str, grad: bool = False) -> torch.Tensor:
+    """``sink`` of the attention ops: one logit per query head, [nh], on ``device``; fp32 (a
+    gathered 16-bit FSDP unit is upcast).  ``grad``: the fp32 gradient accumulator, as it is."""
+    if not isinstance(sink, torch.Tensor) or not sink.is_floating_point() or tuple(sink.shape) != (nh,):
+        raise ValueError(f"{name}: expected a floating-point [{nh}] tensor (one logit per query head)")
+    if grad and sink.dtype != torch.float32:
+        raise ValueError(f"{name}: expected an fp32 tensor, got {sink.dtype}")
+    if sink.device != torch.device(device):
+        raise ValueError(f"{name}: expected device {device}, got {sink.device}")
+    return sink.float()
+
+
 def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, p: float, key: int,
-                  causal: bool = True, out=None, doc=None, window=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                  causal: bool = True, out=None, doc=None, window=None,
+                  sink=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """q [B, nh, S, hd], k, v [B, nkv, S, hd] -> o [B*S, nh*hd] (q dtype), lse [B, nh, S] fp32.
     ``doc`` = (lo, hi) from :func:`doc_bounds` adds the intra-document mask.  nkv < nh is
     grouped-query attention: query head h attends with kv head h // (nh // nkv).  ``window`` = W
-    is sliding-window attention (:func:`window_bounds`, merged with ``doc``)."""
+    is sliding-window attention (:func:`window_bounds`, merged with ``doc``).  ``sink`` (fp32
+    [nh]) is one more logit per query head in the softmax denominator, not scaled and with no
+    value row: p_j = exp(s_j) / (sum_j exp(s_j) + exp(sink[h])), lse = log of that denominator;
+    dropout applies to the p_j only."""
     B, nh, S, hd = q.shape
     doc = _fold_window(window, doc, B, S, q.device)
     G = _kv_group(q, k, v, "attn")
@@ -358,6 +374,8 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, p: float, k
     if mask is not None:
         s = s.masked_fill(mask, float("-inf"))
     lse = torch.logsumexp(s, dim=-1)
+    if sink is not None:
+        lse = torch.logaddexp(lse, _check_sink(sink, nh, q.device, "attn.sink").view(1, nh, 1).expand_as(lse))
     prob = torch.exp(s - lse.unsqueeze(-1))
     if p > 0.0:
         keep = rng.attn_keep_mask(B * nh, S, S, key, p, device=q.device).view(B, nh, S, S)
@@ -370,10 +388,16 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, p: float, k
     return o, lse
 
 
-def attention_bwd(q, k, v, o, do, lse, p: float, key: int, causal: bool = True, doc=None, window=None):
+def attention_bwd(q, k, v, o, do, lse, p: float, key: int, causal: bool = True, doc=None, window=None,
+                  sink=None, dsink=None):
     """Flash-style backward from (o, lse).  do/o are [B*S, H]; returns dq [B,nh,S,hd] and
-    dk, dv in k's shape [B,nkv,S,hd] (summed over each kv head's query group in fp32)."""
+    dk, dv in k's shape [B,nkv,S,hd] (summed over each kv head's query group in fp32).
+    With ``sink`` the forward's ``lse`` already holds the sink, so dq / dk / dv need nothing
+    else (the sink column has dP = 0 and delta = rowsum(dO * O) already is sum_j P_j dP_j);
+    ``dsink`` (fp32 [nh]) += -sum_{b,q} exp(sink[h] - lse[b,h,q]) * delta[b,h,q]."""
     B, nh, S, hd = q.shape
+    if (sink is None) != (dsink is None):
+        raise ValueError("attn_bwd: sink and dsink go together")
     doc = _fold_window(window, doc, B, S, q.device)
     G = _kv_group(q, k, v, "attn_bwd")
     scale = 1.0 / math.sqrt(hd)
@@ -394,6 +418,11 @@ def attention_bwd(q, k, v, o, do, lse, p: float, key: int, causal: bool = True, 
     dpd = torch.matmul(dof, vf.transpose(-2, -1))
     dp = torch.where(keep, dpd / (1.0 - p), torch.zeros((), device=q.device)) if keep is not None else dpd
     delta = (dof * of).sum(dim=-1, keepdim=True)
+    if sink is not None:
+        sink = _check_sink(sink, nh, q.device, "attn_bwd.sink")
+        _check_sink(dsink, nh, q.device, "attn_bwd.dsink", grad=True)
+        p_sink = torch.exp(sink.view(1, nh, 1) - lse)
+        dsink += -(p_sink * delta.squeeze(-1)).sum(dim=(0, 2))
     ds = prob * (dp - delta)
     dq = torch.matmul(ds, kf) * scale
     dk = torch.matmul(ds.transpose(-2, -1), qf) * scale

@@ -35,6 +35,11 @@ class Segment:
     shape: Tuple[int, ...]
 
 
+def sinks_alloc(num_heads: int) -> int:
+    """Elements allocated for a layer's [num_heads] attention sinks: rounded up to 8."""
+    return (num_heads + 7) // 8 * 8
+
+
 class FlatLayout:
     """Ordered segments of the flat buffer for one GPT model."""
 
@@ -75,6 +80,12 @@ class FlatLayout:
             if cfg.qk_norm:  # QK-norm weights ride with the layer's norm weights (no decay)
                 add(f"layers.{i}.attention.q_norm.weight", (cfg.head_dim,))
                 add(f"layers.{i}.attention.k_norm.weight", (cfg.head_dim,))
+            if cfg.attention_sinks:
+                # [num_heads] sink logits (no decay), after the layer's norm weights.  num_heads
+                # can be 12 or 25: the segment is allocated rounded up to 8 elements, so every
+                # later segment stays 16-byte aligned in the fp32 buffers and the bf16 shadow.
+                # The padding is zero and stays zero under AdamW (zero gradient, no decay).
+                add(f"layers.{i}.attention.sinks", (cfg.num_heads,), alloc=sinks_alloc(cfg.num_heads))
         add("norm.weight", (H,))
         self.total = off
         self.segments = segs
@@ -148,7 +159,8 @@ class FlatParamStore(ParamProvider):
                 ln1=vec(self.flat, p + "input_layernorm.weight"),
                 ln2=vec(self.flat, p + "post_attention_layernorm.weight"),
                 qn=vec(self.flat, p + "attention.q_norm.weight") if cfg.qk_norm else None,
-                kn=vec(self.flat, p + "attention.k_norm.weight") if cfg.qk_norm else None))
+                kn=vec(self.flat, p + "attention.k_norm.weight") if cfg.qk_norm else None,
+                sk=vec(self.flat, p + "attention.sinks") if cfg.attention_sinks else None))
             self._lgrads.append(LayerGrads(
                 wqkv=v(self.grad, p + "attention.q_proj.weight", QKV, H),
                 wo=v(self.grad, p + "attention.o_proj.weight", H, H),
@@ -157,7 +169,8 @@ class FlatParamStore(ParamProvider):
                 ln1=vec(self.grad, p + "input_layernorm.weight"),
                 ln2=vec(self.grad, p + "post_attention_layernorm.weight"),
                 qn=vec(self.grad, p + "attention.q_norm.weight") if cfg.qk_norm else None,
-                kn=vec(self.grad, p + "attention.k_norm.weight") if cfg.qk_norm else None))
+                kn=vec(self.grad, p + "attention.k_norm.weight") if cfg.qk_norm else None,
+                sk=vec(self.grad, p + "attention.sinks") if cfg.attention_sinks else None))
         e = bn["embed_tokens.weight"]
         self._head = HeadWeights(
             embed=self.flat[e.offset:e.offset + e.numel].view(e.shape),
@@ -185,6 +198,10 @@ class FlatParamStore(ParamProvider):
                 kn = bn[f"layers.{i}.attention.k_norm.weight"]
                 assert bn[f"layers.{i}.attention.q_norm.weight"].offset == end
                 end = kn.offset + kn.numel
+            if self.cfg.attention_sinks:  # then the sinks, with their padding
+                sk = bn[f"layers.{i}.attention.sinks"]
+                assert sk.offset == end
+                end = sk.offset + sinks_alloc(sk.numel)
             units[i] = [(a, b), (n1.offset, end)]
         return units
 

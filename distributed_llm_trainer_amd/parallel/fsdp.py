@@ -12,9 +12,9 @@ one gather in flight beyond the one being consumed (``limit_all_gathers``).
 
 MI355X-specific design choices:
 
-* Unit = one flat buffer laid out ``[q|k|v|o|gate|up|down|ln1|ln2]`` (``|q_norm|k_norm`` with QK-norm) so the
-  gathered bf16 buffer is directly the packed QKV / gate|up GEMM operands (no
-  unflatten copies).  The root unit ``[embed(Vp rows)|norm]`` keeps the padded
+* Unit = one flat buffer laid out ``[q|k|v|o|gate|up|down|ln1|ln2]`` (``|q_norm|k_norm`` with
+  QK-norm, ``|sinks`` with attention sinks) so the gathered bf16 buffer is directly the
+  packed QKV / gate|up GEMM operands (no unflatten copies).  The root unit ``[embed(Vp rows)|norm]`` keeps the padded
   vocabulary rows so the gathered buffer IS the lm_head operand.
 * The executor calls ``pre_forward/post_forward/pre_backward/post_backward`` per
   unit, so the next unit's all-gather is issued on RCCL's stream BEFORE the current
@@ -44,6 +44,7 @@ import torch
 import torch.distributed as dist
 
 from ..models.engine import HeadGrads, HeadWeights, LayerGrads, LayerWeights, ParamProvider
+from .flat import sinks_alloc
 
 STRATEGIES = ("FULL_SHARD", "SHARD_GRAD_OP", "NO_SHARD", "HYBRID_SHARD")
 
@@ -88,7 +89,7 @@ class FlatUnit:
         self.host_bufs = []      # cpu_offload: pinned staging buffers, one per pending reduce
         self.refs = 0            # chains (forward / backward of a micro-step) using `full`
         self.ready_ev = None     # HIP event: `full` is complete (recorded after the gather wait)
-        self.norm_grad = None    # bf16-gradient mode: fp32 ln1 | ln2 (| q_norm | k_norm) gradients of the micro-step
+        self.norm_grad = None    # bf16-gradient mode: fp32 ln1 | ln2 (| q_norm | k_norm | sinks) gradients
         self.head_q = []         # root unit: gradient buffers of backwards issued but not yet reduced
 
     def local_slice(self) -> Tuple[int, int]:
@@ -195,6 +196,8 @@ class FSDPRuntime(ParamProvider):
             if cfg.qk_norm:  # QK-norm weights: part of the layer's unit, after its norm weights
                 add(p + "attention.q_norm.weight", (cfg.head_dim,))
                 add(p + "attention.k_norm.weight", (cfg.head_dim,))
+            if cfg.attention_sinks:  # [num_heads] sink logits, allocated rounded up to 8 (FlatLayout)
+                add(p + "attention.sinks", (cfg.num_heads,), alloc=sinks_alloc(cfg.num_heads))
         return segs, off
 
     @torch.no_grad()
@@ -401,19 +404,32 @@ class FSDPRuntime(ParamProvider):
         raise KeyError(name)
 
     def _qk_views(self, u: FlatUnit, buf: torch.Tensor, p: str) -> dict:
-        """The qn / kn fields (QK-norm weights or gradients) of a layer unit's buffer; empty
-        without cfg.qk_norm."""
-        if not self.cfg.qk_norm:
-            return {}
-        return {"qn": self._view(u, buf, p + "attention.q_norm.weight"),
-                "kn": self._view(u, buf, p + "attention.k_norm.weight")}
+        """The qn / kn fields (QK-norm weights or gradients) and the sk field (attention sinks)
+        of a layer unit's buffer; empty without cfg.qk_norm / cfg.attention_sinks."""
+        d = {}
+        if self.cfg.qk_norm:
+            d["qn"] = self._view(u, buf, p + "attention.q_norm.weight")
+            d["kn"] = self._view(u, buf, p + "attention.k_norm.weight")
+        if self.cfg.attention_sinks:
+            d["sk"] = self._view(u, buf, p + "attention.sinks")
+        return d
+
+    def _side_numel(self) -> int:
+        """Elements of the fp32 side buffer of the bf16-gradient mode: ln1 | ln2 | q_norm | k_norm | sinks."""
+        cfg = self.cfg
+        return 2 * cfg.hidden_size + (2 * cfg.head_dim if cfg.qk_norm else 0) + \
+            (cfg.num_heads if cfg.attention_sinks else 0)
 
     def _qk_side(self, norm_grad: torch.Tensor) -> dict:
         """The same fields in the fp32 side buffer of the bf16-gradient mode (after ln1 | ln2)."""
-        if not self.cfg.qk_norm:
-            return {}
-        H, hd = self.cfg.hidden_size, self.cfg.head_dim
-        return {"qn": norm_grad[2 * H:2 * H + hd], "kn": norm_grad[2 * H + hd:]}
+        cfg = self.cfg
+        d, off = {}, 2 * cfg.hidden_size
+        if cfg.qk_norm:
+            d["qn"], d["kn"] = norm_grad[off:off + cfg.head_dim], norm_grad[off + cfg.head_dim:off + 2 * cfg.head_dim]
+            off += 2 * cfg.head_dim
+        if cfg.attention_sinks:
+            d["sk"] = norm_grad[off:off + cfg.num_heads]
+        return d
 
     def layer(self, i):
         u = self.units[i]
@@ -437,8 +453,11 @@ class FSDPRuntime(ParamProvider):
                 u.full_grad = torch.empty(u.padded, dtype=self.reduce_dtype, device=self.device)
                 if u.padded > u.numel:
                     u.full_grad[u.numel:].zero_()
-                u.norm_grad = torch.zeros(2 * H + (2 * self.cfg.head_dim if self.cfg.qk_norm else 0),
-                                          dtype=torch.float32, device=self.device)
+                if self.cfg.attention_sinks:  # the padding of the sinks segment is written by nobody
+                    for s in u.segs:
+                        if s.name.endswith("attention.sinks"):
+                            u.full_grad[s.offset:s.offset + sinks_alloc(s.numel)].zero_()
+                u.norm_grad = torch.zeros(self._side_numel(), dtype=torch.float32, device=self.device)
             else:
                 u.full_grad = torch.zeros(u.padded, dtype=torch.float32, device=self.device)
         p = f"layers.{i}."

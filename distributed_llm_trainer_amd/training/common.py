@@ -231,6 +231,10 @@ def add_model_args(p) -> None:
                    help="with --sliding_window: every N-th layer (layers N, 2N, ... counted from 1) stays global "
                         "(plain causal) and the others are windowed (N >= 2).  Overrides the YAML's "
                         "model.sliding_window_pattern (default: every layer is windowed)")
+    p.add_argument("--attention_sinks", action="store_true", default=None,
+                   help="attention sinks: one learned fp32 logit per query head and layer that takes part in the "
+                        "softmax denominator and has no value row (the gpt-oss form).  Overrides the YAML's "
+                        "model.attention_sinks and the preset (default: off)")
 
 
 def apply_model_args(args, model_config) -> None:
@@ -242,6 +246,8 @@ def apply_model_args(args, model_config) -> None:
         model_config.num_kv_heads = nkv
     if getattr(args, "qk_norm", None) is not None:
         model_config.qk_norm = bool(args.qk_norm)
+    if getattr(args, "attention_sinks", None) is not None:
+        model_config.attention_sinks = bool(args.attention_sinks)
     sw, swp = getattr(args, "sliding_window", None), getattr(args, "sliding_window_pattern", None)
     if sw is not None or swp is not None:
         if sw is not None:

@@ -294,7 +294,8 @@ def flat_store_optimizer(store, lr: float, betas, eps: float, weight_decay: floa
 
     if split_no_decay:
         regions = [(0, lay.decay_end, weight_decay), (lay.decay_end, lay.total, 0.0)]
-        nd = lambda n: ("bias" in n) or ("norm" in n)  # noqa: E731 (reference rule)
+        # the reference rule, plus the attention sinks (they live after decay_end with the norm weights)
+        nd = lambda n: ("bias" in n) or ("norm" in n) or n.endswith("attention.sinks")  # noqa: E731
         param_map = [pm(lambda n: not nd(n)), pm(nd)]
     else:
         regions = [(0, lay.total, weight_decay)]

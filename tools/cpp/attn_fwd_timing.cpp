@@ -3,6 +3,7 @@
 //   hipcc -O3 --offload-arch=gfx950 -mllvm -amdgpu-mfma-vgpr-form -DDLT_ATTN_FWD_TIMING \
 //     tools/cpp/attn_fwd_timing.cpp -o tools/cpp/attn_fwd_timing
 #include "../../distributed_llm_trainer_amd/ops/csrc/attention.hip"
+#include "../../distributed_llm_trainer_amd/ops/csrc/attention_sink.hip"  // dlt_attn_fwd's SINK launcher
 #include <algorithm>
 #include <cstdio>
 #include <vector>

@@ -1,5 +1,6 @@
 // Timing of the attention keep-bit kernel (B8 nh12 S1024) -- used for layout experiments.
 #include "../../distributed_llm_trainer_amd/ops/csrc/attention.hip"
+#include "../../distributed_llm_trainer_amd/ops/csrc/attention_sink.hip"  // dlt_attn_fwd's SINK launcher
 #include <cstdio>
 int main() {
   int B = 8, nh = 12, S = 1024, W = S / 32;
