@@ -52,7 +52,7 @@ from typing import Any, Callable, Dict, List, Optional
 
 import torch
 
-from ..ops import rng
+from ..ops import attn_routes, rng
 
 
 def _drain(gen):
@@ -259,30 +259,18 @@ class GPTEngine:
         self.qkv_width = cfg.hidden_size + 2 * cfg.kv_size
         self.gqa = cfg.num_kv_heads != cfg.num_heads
         self.gqa_kw = {"nkv": cfg.num_kv_heads} if self.gqa else {}
-        if self.gqa and getattr(ops, "backend", "") == "hip":
-            from ..ops import check_gqa
-            check_gqa("cuda", cfg.head_dim, act_dtype)
-            if not self.packed_qkv:
-                raise NotImplementedError("grouped-query attention on the GPU runs on the packed QKV layout "
-                                          "(DLT_PACKED_QKV=0 is not supported with num_kv_heads < num_heads)")
         # QK-norm (cfg.qk_norm): the QKV GEMM is followed by qknorm_rope_inplace (norm + RoPE
         # in place, pre-norm q|k copied to ``raw``) instead of the RoPE forms, and qknorm_bwd
         # runs between the attention backward and the QKV data-gradient GEMM
         self.qk_norm = bool(cfg.qk_norm)
-        if self.qk_norm and getattr(ops, "backend", "") == "hip":
-            from ..ops import check_qk_norm
-            check_qk_norm("cuda", cfg.head_dim, act_dtype)
-            if not self.packed_qkv:
-                raise NotImplementedError("QK-norm on the GPU runs on the packed QKV layout "
-                                          "(DLT_PACKED_QKV=0 is not supported with qk_norm)")
         # attention sinks (cfg.attention_sinks): the attention forward takes sink=w.sk (the SINK
         # kernels fold it into the softmax denominator and lse) and the backward dsink=gr.sk
         # (k_attn_sink_bwd, from lse and the delta workspace); o and lse are kept anyway, so
         # activation checkpointing keeps nothing new
         self.sinks = bool(getattr(cfg, "attention_sinks", False))
-        if self.sinks and getattr(ops, "backend", "") == "hip":
-            from ..ops import check_attention_sinks
-            check_attention_sinks("cuda", cfg.head_dim, act_dtype)
+        if getattr(ops, "backend", "") == "hip":  # the GPU routes; the reference ops have every feature
+            attn_routes.check_attention_features("cuda", cfg.head_dim, act_dtype, attn_routes.config_features(cfg),
+                                                 self.packed_qkv)
         # last layers of the deferred-wgrad backward whose weight gradients run on the
         # current stream instead of the side stream (see _backward_gen)
         self.main_wgrad_layers = int(os.environ.get("DLT_MAIN_WGRAD_LAYERS", "1"))
@@ -324,10 +312,9 @@ class GPTEngine:
         NotImplementedError here -- before any step -- when this model's attention route
         has no mask (head_dim above 128, fp32 activations on the GPU)."""
         if token_id is not None:
-            from ..ops import check_doc_mask
             token_id = int(token_id)
             if getattr(self.ops, "backend", "") == "hip":  # the GPU routes; reference ops mask densely
-                check_doc_mask("cuda", self.cfg.head_dim, self.act_dtype)
+                attn_routes.check_attention_features("cuda", self.cfg.head_dim, self.act_dtype, {"doc"})
         self.doc_sep_token = token_id
 
     def set_loss_segments(self, n: int) -> None:
@@ -477,15 +464,23 @@ class GPTEngine:
             self._win_cache[k] = self.ops.window_bounds(st.B, st.S, W, dev)
         return self._win_cache[k]
 
-    def _attn_bounds_kw(self, st: "_StepState", i: int) -> Dict[str, Any]:
-        """``doc=`` (and ``window=``) of layer ``i``'s attention forward and backward: a
-        windowed layer gets ``st.win`` and its window (the ops then make banded keep bits), a
-        global one ``st.doc``."""
-        if st.win is not None:
-            W = self.cfg.layer_window(i)
-            if W is not None:
-                return {"doc": st.win, "window": W}
-        return {"doc": st.doc} if st.doc is not None else {}
+    def _attn_kw(self, st: "_StepState", i: int, w, grads=None) -> Dict[str, Any]:
+        """The feature keywords of layer ``i``'s (weights ``w``) attention forward and, with
+        the layer's ``grads``, backward.  ``doc=`` (and ``window=``): a windowed layer gets
+        ``st.win`` and its window (the ops then make banded keep bits), a global one ``st.doc``.
+        ``nkv=``: grouped-query attention on the packed layout (the split one shows it in k's
+        shape; MHA passes no keyword, so its calls are what they were).  ``sink=``, and
+        ``dsink=`` in the backward: gr.sk is shared with the other micro-steps like gr.ln1 /
+        gr.ln2, so the accumulation lies between wait_prev(i) and mark(i)."""
+        W = self.cfg.layer_window(i) if st.win is not None else None
+        kw = {"doc": st.win, "window": W} if W is not None else {"doc": st.doc} if st.doc is not None else {}
+        if self.packed_qkv:
+            kw.update(self.gqa_kw)
+        if self.sinks:
+            kw["sink"] = w.sk
+            if grads is not None:
+                kw["dsink"] = grads.sk
+        return kw
 
     def _attn_mask_async(self, B, S, p, key, dev, window=None):
         """(mask, ready-event) built on a side stream (opt-in, ``DLT_MASK_STREAM=1``), or
@@ -545,6 +540,41 @@ class GPTEngine:
             return cos, sin
         return torch.ones_like(cos), torch.zeros_like(sin)
 
+    def _qkv(self, st: "_StepState", w, n1, cos, sin, kept=None):
+        """(q, k, v, raw) of a layer, in its forward and in its recompute: the QKV projection
+        of ``n1`` with QK-norm (``raw``: its pre-norm q|k, else None) and RoPE applied.  Packed
+        layout: ``q`` is the packed [M, H + 2*KV] QKV and k = v = None.  ``kept`` = (q, raw) of
+        the forward when it kept the QKV output (_ac_keep): returned as it is."""
+        if kept is not None:
+            return kept[0], None, None, kept[1]
+        ops, gm, nh = self.ops, self.gemm, self.cfg.num_heads
+        B, S = st.B, st.S
+        if self.packed_qkv and hasattr(gm, "linear_rope") and not self.gqa and not self.qk_norm:
+            # QKV GEMM with RoPE on q/k in its epilogue (when that races faster)
+            return gm.linear_rope(n1, w.wqkv, B, S, nh, cos, sin, ops), None, None, None
+        qkv = gm.linear(n1, w.wqkv)
+        raw = self._qknorm_fwd(qkv, w, B, S, cos, sin) if self.qk_norm else None
+        if not self.packed_qkv:
+            return (*ops.rope_qkv_fwd(qkv, B, S, nh, *self._split_tables(raw, cos, sin), **self.gqa_kw), raw)
+        if raw is None:
+            ops.rope_qk_inplace(qkv, B, S, nh, cos, sin, **self.gqa_kw)
+        return qkv, None, None, raw
+
+    def _gate_up(self, st: "_StepState", i: int, w, n2, kept=None, need_s: bool = True):
+        """(gu, s) of a layer's MLP: the gate/up projection of ``n2`` (``kept``: the forward's,
+        when it kept it, _ac_keep) and its SwiGLU, fused into the GEMM's epilogue when that is
+        faster.  s goes to the layer's slot, or to a temporary when it lives in the slot ring
+        (the backward rewrites it there); ``need_s=False`` (the recompute under the ring)
+        returns None for it and launches no SwiGLU of its own."""
+        ops, gm = self.ops, self.gemm
+        slot = None if self._s_in_ring(st) else self._sb(st, i, "s", n2.shape[0], self.cfg.intermediate_size,
+                                                         n2.device)
+        if kept is None and hasattr(gm, "linear_swiglu"):
+            gu, s = gm.linear_swiglu(n2, w.wgu, ops, s_out=slot)
+            return gu, s if need_s else None
+        gu = gm.linear(n2, w.wgu) if kept is None else kept
+        return gu, ops.swiglu_fwd(gu, out=slot) if need_s else None
+
     def _layer_forward(self, st: _StepState, i: int, r, d, key_d: int, p_d: float,
                        save: bool):
         ops, gm, cfg = self.ops, self.gemm, self.cfg
@@ -555,24 +585,16 @@ class GPTEngine:
         k_attn, k_resid, k_mlp = self._keys(st.micro, i)
         cos, sin = self.rope(S, r.device)
 
-        M, H, I = B * S, cfg.hidden_size, cfg.intermediate_size
+        M, H = B * S, cfg.hidden_size
         dv = r.device
         sb = lambda name, n: self._sb(st, i, name, M, n, dv)  # noqa: E731
         # attention keep-bits depend only on the RNG key: build them on a side stream
         # so the VALU-only hashing overlaps the norm + QKV GEMM + RoPE below
-        bkw = self._attn_bounds_kw(st, i)
-        mask, mask_ev = self._attn_mask_async(B, S, pa, k_attn, dv, bkw.get("window"))
+        kw = self._attn_kw(st, i, w)
+        mask, mask_ev = self._attn_mask_async(B, S, pa, k_attn, dv, kw.get("window"))
         x, n1, rstd1 = ops.add_dropout_rmsnorm_fwd(r, d, w.ln1, self.eps, p_d, key_d, self.act_dtype,
                                                    y_out=sb("n1", H))
-        fused_rope = self.packed_qkv and hasattr(gm, "linear_rope") and not self.gqa and not self.qk_norm
-        if fused_rope:  # QKV GEMM with RoPE on q/k in its epilogue (when that races faster)
-            qkv = gm.linear_rope(n1, w.wqkv, B, S, cfg.num_heads, cos, sin, ops)
-        else:
-            qkv = gm.linear(n1, w.wqkv)
-        if mask is not None:
-            torch.cuda.current_stream().wait_event(mask_ev)
-        kw = {"mask": mask} if mask is not None else {}
-        kw.update(bkw)
+        q, k, v, raw = self._qkv(st, w, n1, cos, sin)
         if pa > 0.0 and getattr(ops, "backend", "") == "hip" and getattr(ops, "attn_backend", "hip") in ("hip", "gemm"):
             # keep this layer's keep bits for the backward only within the memory budget.
             # The masks (two layouts, 1 bit per causal score: 8 * B * nh * S * ceil(S/32) B)
@@ -586,36 +608,20 @@ class GPTEngine:
             if st.recompute:
                 keep = keep and mask_bytes <= M * H * 4
             kw["store_mask"] = keep
-        raw = None
-        if self.qk_norm:
-            raw = self._qknorm_fwd(qkv, w, B, S, cos, sin)
-        if self.packed_qkv:
-            if not fused_rope and raw is None:
-                ops.rope_qk_inplace(qkv, B, S, cfg.num_heads, cos, sin, **self.gqa_kw)
-            if self.sinks:
-                kw["sink"] = w.sk
-            o, lse = ops.attention_fwd_packed(qkv, B, S, cfg.num_heads, pa, k_attn, out=sb("o", H), **kw,
-                                              **self.gqa_kw)
-            q, k, v = qkv, None, None
+        if mask is not None:  # the attention launch is the mask's only consumer
+            torch.cuda.current_stream().wait_event(mask_ev)
+            kw["mask"] = mask
+        if k is None:
+            o, lse = ops.attention_fwd_packed(q, B, S, cfg.num_heads, pa, k_attn, out=sb("o", H), **kw)
         else:
-            q, k, v = ops.rope_qkv_fwd(qkv, B, S, cfg.num_heads, *self._split_tables(raw, cos, sin), **self.gqa_kw)
-            if self.sinks:
-                kw["sink"] = w.sk
             o, lse = ops.attention_fwd(q, k, v, pa, k_attn, True, out=sb("o", H), **kw)
-        del qkv
         a = gm.linear(o, w.wo)
         x2, n2, rstd2 = ops.add_dropout_rmsnorm_fwd(x, a, w.ln2, self.eps, ph, k_resid, self.act_dtype,
                                                     y_out=sb("n2", H))
         del a
-        s_ring = self._s_in_ring(st)  # s is a temporary: the backward refills its ring slot
-        s_slot = None if s_ring else sb("s", I)
-        if hasattr(gm, "linear_swiglu"):  # gate/up GEMM with SwiGLU in its epilogue (when faster)
-            gu, s = gm.linear_swiglu(n2, w.wgu, ops, s_out=s_slot)
-        else:
-            gu = gm.linear(n2, w.wgu)
-            s = ops.swiglu_fwd(gu, out=s_slot)
+        gu, s = self._gate_up(st, i, w, n2)
         d_out = gm.linear(s, w.wdown)
-        if s_ring or self._refill_s(st):
+        if self._s_in_ring(st) or self._refill_s(st):  # a temporary: the backward rewrites s
             s = None
         if save:
             c = _LayerCache(x=x, rstd1=rstd1, n1=n1, q=q, raw=raw, k=k, v=v, o=o, lse=lse,
@@ -646,51 +652,19 @@ class GPTEngine:
             return self._layer_forward(st, i, c.x, None, 0, 0.0, save=True)[2]
         if c.n1 is not None and c.s is not None and c.q is not None and c.gu is not None:
             return c  # the forward kept everything (_ac_keep within the budget)
-        ops, gm, cfg = self.ops, self.gemm, self.cfg
+        ops = self.ops
         B, S = st.B, st.S
         w = self.provider.layer(i)
         cos, sin = self.rope(S, c.x.device)
-        M, H, I = B * S, cfg.hidden_size, cfg.intermediate_size
+        M, H = B * S, self.cfg.hidden_size
         dv = c.x.device
         sb = lambda name, n: self._sb(st, i, name, M, n, dv)  # noqa: E731
         _, n1, rstd1 = ops.add_dropout_rmsnorm_fwd(c.x, None, w.ln1, self.eps, 0.0, 0, self.act_dtype,
                                                    y_out=sb("n1", H))
-        raw = c.raw
-        if c.q is not None:  # QKV output kept by the forward (_ac_keep)
-            qkv = c.q
-            q, k, v = qkv, None, None
-        elif self.qk_norm:
-            qkv = gm.linear(n1, w.wqkv)
-            raw = self._qknorm_fwd(qkv, w, B, S, cos, sin)
-            if self.packed_qkv:
-                q, k, v = qkv, None, None
-            else:
-                q, k, v = ops.rope_qkv_fwd(qkv, B, S, cfg.num_heads, *self._split_tables(raw, cos, sin),
-                                           **self.gqa_kw)
-        elif self.packed_qkv and hasattr(gm, "linear_rope") and not self.gqa:
-            qkv = gm.linear_rope(n1, w.wqkv, B, S, cfg.num_heads, cos, sin, ops)
-            q, k, v = qkv, None, None
-        elif self.packed_qkv:
-            qkv = gm.linear(n1, w.wqkv)
-            ops.rope_qk_inplace(qkv, B, S, cfg.num_heads, cos, sin, **self.gqa_kw)
-            q, k, v = qkv, None, None
-        else:
-            qkv = gm.linear(n1, w.wqkv)
-            q, k, v = ops.rope_qkv_fwd(qkv, B, S, cfg.num_heads, cos, sin, **self.gqa_kw)
-        del qkv
+        q, k, v, raw = self._qkv(st, w, n1, cos, sin, kept=(c.q, c.raw) if c.q is not None else None)
         _, n2, rstd2 = ops.add_dropout_rmsnorm_fwd(c.x2, None, w.ln2, self.eps, 0.0, 0, self.act_dtype,
                                                    y_out=sb("n2", H))
-        s_ring = self._s_in_ring(st)  # the backward writes s into its ring slot
-        if c.gu is not None:  # gate/up output kept by the forward (_ac_keep)
-            gu = c.gu
-            s = None if s_ring else ops.swiglu_fwd(gu, out=sb("s", I))
-        elif hasattr(gm, "linear_swiglu"):
-            gu, s = gm.linear_swiglu(n2, w.wgu, ops, s_out=None if s_ring else sb("s", I))
-        else:
-            gu = gm.linear(n2, w.wgu)
-            s = None if s_ring else ops.swiglu_fwd(gu, out=sb("s", I))
-        if s_ring:
-            s = None
+        gu, s = self._gate_up(st, i, w, n2, kept=c.gu, need_s=not self._s_in_ring(st))
         return _LayerCache(x=c.x, rstd1=rstd1, n1=n1, q=q, raw=raw, k=k, v=v, o=c.o, lse=c.lse,
                            x2=c.x2, rstd2=rstd2, n2=n2, gu=gu, s=s)
 
@@ -1143,15 +1117,11 @@ class GPTEngine:
                                       ddelta_out=sb(i, "da", H))
             del dn2
             # attention
-            dkw = self._attn_bounds_kw(st, i)
-            if self.sinks:
-                # gr.sk is shared with the other micro-steps like gr.ln1 / gr.ln2: the
-                # accumulation lies between wait_prev(i) and mark(i)
-                dkw.update(sink=w.sk, dsink=gr.sk)
+            dkw = self._attn_kw(st, i, w, gr)
             do = gm.linear_dgrad(da, w.wo)
             if c.k is None:  # packed: dq/dk/dv land in [M, 3H] with the inverse RoPE applied
                 dqkv = ops.attention_bwd_packed(c.q, c.o, do, c.lse, pa, k_attn, B, S, cfg.num_heads, cos, sin,
-                                                out=sb(i, "dqkv", self.qkv_width), **dkw, **self.gqa_kw)
+                                                out=sb(i, "dqkv", self.qkv_width), **dkw)
                 del do
             else:
                 dq, dk, dv = ops.attention_bwd(c.q, c.k, c.v, c.o, do, c.lse, pa, k_attn, True, **dkw)

@@ -254,14 +254,9 @@ class GPT(nn.Module):
             act_dtype = torch.bfloat16 if dev.type == "cuda" else torch.float32
         if compute_dtype is None:
             compute_dtype = act_dtype
-        if self.config.num_kv_heads != self.config.num_heads and (ops is None or ops.backend == "hip"):
-            ops_mod.check_gqa(dev, self.config.head_dim, act_dtype)  # before anything is re-homed
-        if self.config.qk_norm and (ops is None or ops.backend == "hip"):
-            ops_mod.check_qk_norm(dev, self.config.head_dim, act_dtype)
-        if self.config.attention_sinks and (ops is None or ops.backend == "hip"):
-            ops_mod.check_attention_sinks(dev, self.config.head_dim, act_dtype)
-        if self.config.sliding_window is not None and (ops is None or ops.backend == "hip"):
-            ops_mod.check_sliding_window(dev, self.config.head_dim, act_dtype)
+        if ops is None or ops.backend == "hip":  # before anything is re-homed
+            ops_mod.check_attention_features(dev, self.config.head_dim, act_dtype,
+                                             ops_mod.attn_routes.config_features(self.config))
         if provider is None:
             from ..parallel.flat import FlatParamStore
             provider = FlatParamStore(self, dev, compute_dtype=compute_dtype)

@@ -11,7 +11,8 @@ import types
 
 import torch
 
-from . import reference, rng
+from . import attn_routes, reference, rng
+from .attn_routes import check_attention_features  # noqa: F401  (the public entry of the route table)
 
 _FUNCS = ("rope_tables", "embedding_fwd", "embedding_bwd", "add_dropout_rmsnorm_fwd", "rmsnorm_bwd",
           "rope_qkv_fwd", "rope_qkv_bwd", "attention_fwd", "attention_bwd", "swiglu_fwd", "swiglu_bwd",
@@ -50,95 +51,6 @@ _ATTN_FUNCS = ("rope_qkv_fwd", "rope_qkv_bwd", "attention_fwd", "attention_bwd",
                "attention_fwd_packed", "attention_bwd_packed")
 
 
-def check_doc_mask(device, head_dim: int = 64, act_dtype=torch.bfloat16) -> None:
-    """Raises NotImplementedError when the attention route :func:`for_device` picks for
-    this model has no document mask (``doc=``): on the GPU only the 16-bit flash kernels
-    (head_dim 64 / 128, and smaller heads zero-padded onto them) implement it; the
-    GEMM-formulated route (head_dim above 128) and the fp32 routes do not.  Called where a
-    separator is configured, so the error comes before the first step, not inside it."""
-    if torch.device(device).type != "cuda" or os.environ.get("DLT_ALLOW_REFERENCE_ON_GPU") == "1":
-        return
-    from . import attn_gemm
-    from .hip import ATTN_HEAD_DIMS
-    if head_dim not in ATTN_HEAD_DIMS:  # names the padded / GEMM route it would take
-        attn_gemm.check_doc(act_dtype, head_dim, True)
-    if act_dtype == torch.float32:
-        from . import hip_f32
-        hip_f32._no_doc(True)
-
-
-def check_sliding_window(device, head_dim: int = 64, act_dtype=torch.bfloat16) -> None:
-    """Raises NotImplementedError when the attention route :func:`for_device` picks for this
-    model has no sliding window (``GPTConfig.sliding_window``).  The window runs on the DOC
-    forms of the 16-bit flash kernels, so the routes are :func:`check_doc_mask`'s: head_dim
-    64 / 128 and smaller heads zero-padded onto them pass; the GEMM-formulated route
-    (head_dim above 128) and the fp32 routes raise.  Called when the engine is enabled, so
-    the error comes before the first step, not inside it."""
-    if torch.device(device).type != "cuda" or os.environ.get("DLT_ALLOW_REFERENCE_ON_GPU") == "1":
-        return
-    from . import attn_gemm
-    from .hip import ATTN_HEAD_DIMS
-    if head_dim not in ATTN_HEAD_DIMS:  # names the padded / GEMM route it would take
-        attn_gemm.check_window(act_dtype, head_dim, True)
-    if act_dtype == torch.float32:
-        from . import hip_f32
-        hip_f32._no_window()
-
-
-def check_gqa(device, head_dim: int = 64, act_dtype=torch.bfloat16) -> None:
-    """Raises NotImplementedError when the attention route :func:`for_device` picks for
-    this model has no grouped-query attention (``nkv=``): on the GPU only the 16-bit flash
-    kernels at their native head_dims 64 / 128 implement it; the zero-padded heads, the
-    GEMM-formulated route and the fp32 kernels do not.  Called when the engine is enabled,
-    so the error comes before the first step, not inside it."""
-    if torch.device(device).type != "cuda" or os.environ.get("DLT_ALLOW_REFERENCE_ON_GPU") == "1":
-        return
-    from .hip import ATTN_HEAD_DIMS
-    if act_dtype == torch.float32:
-        raise NotImplementedError("grouped-query attention (num_kv_heads < num_heads) is not implemented for fp32 "
-                                  "activations on the GPU: use bf16 or fp16")
-    if head_dim not in ATTN_HEAD_DIMS:
-        raise NotImplementedError(f"grouped-query attention (num_kv_heads < num_heads) needs head_dim in "
-                                  f"{tuple(ATTN_HEAD_DIMS)} on the GPU; head_dim {head_dim} would run zero-padded "
-                                  f"or as GEMMs, which have no grouped K/V")
-
-
-def check_qk_norm(device, head_dim: int = 64, act_dtype=torch.bfloat16) -> None:
-    """Raises NotImplementedError when the route :func:`for_device` picks for this model has
-    no QK-norm (``GPTConfig.qk_norm``): on the GPU the norm is fused with the in-place RoPE of
-    the 16-bit packed QKV (``qknorm_rope_inplace`` / ``qknorm_bwd``, head_dim 64 / 128); the
-    zero-padded heads, the GEMM-formulated route and the fp32 kernels have no such kernel.
-    Called when the engine is enabled, so the error comes before the first step."""
-    if torch.device(device).type != "cuda" or os.environ.get("DLT_ALLOW_REFERENCE_ON_GPU") == "1":
-        return
-    from .hip import ATTN_HEAD_DIMS
-    if act_dtype == torch.float32:
-        raise NotImplementedError("QK-norm (qk_norm) is not implemented for fp32 activations on the GPU: "
-                                  "use bf16 or fp16")
-    if head_dim not in ATTN_HEAD_DIMS:
-        raise NotImplementedError(f"QK-norm (qk_norm) needs head_dim in {tuple(ATTN_HEAD_DIMS)} on the GPU; "
-                                  f"head_dim {head_dim} would run zero-padded or as GEMMs, which have no "
-                                  f"QK-norm kernel")
-
-
-def check_attention_sinks(device, head_dim: int = 64, act_dtype=torch.bfloat16) -> None:
-    """Raises NotImplementedError when the attention route :func:`for_device` picks for this
-    model has no attention sinks (``GPTConfig.attention_sinks``, ``sink=``).  The sink is a
-    ``SINK`` form of the 16-bit flash forward plus ``k_attn_sink_bwd``, so the routes are
-    :func:`check_doc_mask`'s: head_dim 64 / 128 and smaller heads zero-padded onto them pass;
-    the GEMM-formulated route (head_dim above 128) and the fp32 routes raise.  Called when the
-    engine is enabled, so the error comes before the first step, not inside it."""
-    if torch.device(device).type != "cuda" or os.environ.get("DLT_ALLOW_REFERENCE_ON_GPU") == "1":
-        return
-    from . import attn_gemm
-    from .hip import ATTN_HEAD_DIMS
-    if act_dtype == torch.float32:
-        raise NotImplementedError("attention sinks (attention_sinks) are not implemented for fp32 activations on "
-                                  "the GPU: use bf16 or fp16")
-    if head_dim not in ATTN_HEAD_DIMS:  # names the padded / GEMM route it would take
-        attn_gemm.check_sink(act_dtype, head_dim, True)
-
-
 def for_device(device, head_dim: int = 64, act_dtype=torch.bfloat16) -> types.SimpleNamespace:
     """Op namespace for ``device``.  On the GPU every op is a HIP kernel: bf16 / fp16
     activations on the 16-bit kernels, fp32 (``--mixed_precision fp32``) on the fp32
@@ -157,20 +69,17 @@ def for_device(device, head_dim: int = 64, act_dtype=torch.bfloat16) -> types.Si
             return _namespace(reference, "reference")
         ns = hip_ops()
         ns.attn_backend = "hip"
-        from .hip import ATTN_HEAD_DIMS
-        from .hip_f32 import ATTN_HEAD_DIMS as F32_HEAD_DIMS
-        native_hd = F32_HEAD_DIMS if act_dtype == torch.float32 else ATTN_HEAD_DIMS
-        if head_dim not in native_hd:
+        rt = attn_routes.route(act_dtype, head_dim)
+        if rt.kind != "flash":
             import warnings
 
-            from . import attn_gemm
+            from . import attn_gemm, hip
             if head_dim % 2:
                 raise NotImplementedError(f"head_dim {head_dim}: RoPE (rotate_half) needs an even head_dim")
             rope16 = act_dtype == torch.float32 or head_dim % 16 == 0
-            route = ("zero-padded onto the flash kernels" if attn_gemm.pad_dim(act_dtype, head_dim)
-                     else "batched GEMMs + HIP row kernels")
-            warnings.warn(f"head_dim {head_dim}: the HIP flash attention kernels take head_dim {native_hd}; attention "
-                          f"runs {route} for this model (RoPE: "
+            route = "zero-padded onto the flash kernels" if rt.pad else "batched GEMMs + HIP row kernels"
+            warnings.warn(f"head_dim {head_dim}: the HIP flash attention kernels take head_dim {hip.ATTN_HEAD_DIMS}; "
+                          f"attention runs {route} for this model (RoPE: "
                           f"{'HIP kernel' if rope16 else 'fp32 HIP kernel on widened values'})")
             for f in _ATTN_FUNCS:
                 if not f.startswith("rope") or not rope16:

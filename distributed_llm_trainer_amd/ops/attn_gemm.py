@@ -36,7 +36,7 @@ import os
 
 import torch
 
-from . import hip_f32
+from . import attn_routes, hip_f32
 
 _HK = {torch.bfloat16: 0, torch.float16: 1}
 PAD_FLASH = os.environ.get("DLT_ATTN_PAD", "1") != "0"
@@ -287,60 +287,25 @@ def _rope_bwd(dq, dk, dv, cos, sin, out=None):
 
 
 # ----------------------------------------------------------------------- entry points
-def doc_route(dtype, hd: int) -> str:
-    """Name of the route a (dtype, head_dim) takes here, for messages."""
-    if pad_dim(dtype, hd):
-        return "fp32 zero-padded flash" if dtype == torch.float32 else "zero-padded 16-bit flash"
-    return "GEMM-formulated attention (batched GEMMs + HIP row kernels)"
-
-
-def check_doc(dtype, hd: int, doc) -> None:
-    """The document mask reaches the 16-bit flash kernels only: heads zero-padded onto them
-    pass the bounds through, every other route here raises (no silent fallback)."""
-    if doc is None or (dtype in _HK and pad_dim(dtype, hd)):
-        return
-    raise NotImplementedError(
-        f"document-masked attention (doc_sep_token) is not implemented on the {doc_route(dtype, hd)} route "
-        f"(head_dim {hd}, {dtype}); use bf16 or fp16 activations with head_dim <= 128")
-
-
-def check_window(dtype, hd: int, window) -> None:
-    """Sliding-window attention takes the routes the document mask takes (it runs on the same
-    DOC kernels): zero-padded 16-bit heads pass, every other route here raises."""
-    if window is None or (dtype in _HK and pad_dim(dtype, hd)):
-        return
-    raise NotImplementedError(
-        f"sliding-window attention (sliding_window) is not implemented on the {doc_route(dtype, hd)} route "
-        f"(head_dim {hd}, {dtype}); use bf16 or fp16 activations with head_dim <= 128")
-
-
-def check_sink(dtype, hd: int, sink) -> None:
-    """Attention sinks take the routes the document mask takes: zero-padded 16-bit heads pass
-    ``sink=`` through to the flash kernels (the padding is exact), every other route here raises."""
-    if sink is None or (dtype in _HK and pad_dim(dtype, hd)):
-        return
-    raise NotImplementedError(
-        f"attention sinks (attention_sinks) are not implemented on the {doc_route(dtype, hd)} route "
-        f"(head_dim {hd}, {dtype}); use bf16 or fp16 activations with head_dim <= 128")
-
-
-def _fold_window(window, doc, B, S, dtype, hd, device):
-    """``window=`` of the entry points folded into the bounds the padded flash kernels take
-    (their keep bits stay the full ones: a superset of what the window reads)."""
-    if window is None:
-        return doc
-    check_window(dtype, hd, window)
-    from . import hip
-    return hip._window_doc(window, doc, B, S, device, "attn")[1]
+def _enter(dtype, hd: int, B: int, S: int, device, doc, window, sink):
+    """(padded head_dim or None, bounds) of an entry point: whichever of ``doc`` / ``window``
+    / ``sink`` was passed must exist on the route this head takes here (no silent fallback),
+    and the window is folded into the bounds the padded flash kernels take (their keep bits
+    stay the full ones: a superset of what the window reads)."""
+    rt = attn_routes.route(dtype, hd, flash=False)
+    for feature, arg in (("sinks", sink), ("window", window), ("doc", doc)):
+        if arg is not None:
+            attn_routes.require(rt, feature, "attn_gemm")
+    if window is not None:
+        from . import hip
+        doc = hip._window_doc(window, doc, B, S, device, "attn")[1]
+    return rt.pad, doc
 
 
 def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=True, doc=None, window=None,
                          sink=None):
     hd = qkv.shape[1] // (3 * nh)
-    check_sink(qkv.dtype, hd, sink)
-    doc = _fold_window(window, doc, B, S, qkv.dtype, hd, qkv.device)
-    check_doc(qkv.dtype, hd, doc)
-    Dp = pad_dim(qkv.dtype, hd)
+    Dp, doc = _enter(qkv.dtype, hd, B, S, qkv.device, doc, window, sink)
     H, ld = nh * hd, qkv.stride(0)
     if Dp and qkv.dtype == torch.float32:
         q4p = _pad32(hip_f32._packed_ptrs(qkv, 3, H), (S * ld, ld, hd), B, S, nh, hd, Dp, qkv.device)
@@ -361,10 +326,7 @@ def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=
 def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, doc=None, window=None, sink=None,
                          dsink=None):
     hd = qkv.shape[1] // (3 * nh)
-    check_sink(qkv.dtype, hd, sink)
-    doc = _fold_window(window, doc, B, S, qkv.dtype, hd, qkv.device)
-    check_doc(qkv.dtype, hd, doc)
-    Dp = pad_dim(qkv.dtype, hd)
+    Dp, doc = _enter(qkv.dtype, hd, B, S, qkv.device, doc, window, sink)
     H, ld = nh * hd, qkv.stride(0)
     if Dp and qkv.dtype == torch.float32:
         q4p = _pad32(hip_f32._packed_ptrs(qkv, 3, H), (S * ld, ld, hd), B, S, nh, hd, Dp, qkv.device)
@@ -395,10 +357,7 @@ def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=
     if not causal:
         raise NotImplementedError("only causal attention is implemented (the model is a causal LM)")
     B, nh, S, hd = q.shape
-    check_sink(q.dtype, hd, sink)
-    doc = _fold_window(window, doc, B, S, q.dtype, hd, q.device)
-    check_doc(q.dtype, hd, doc)
-    Dp = pad_dim(q.dtype, hd)
+    Dp, doc = _enter(q.dtype, hd, B, S, q.device, doc, window, sink)
     hm = (nh * S * hd, hd, S * hd)
     if Dp and q.dtype == torch.float32:
         ts = [t.contiguous() for t in (q, k, v)]
@@ -417,10 +376,7 @@ def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=
 
 def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, doc=None, window=None, sink=None, dsink=None):
     B, nh, S, hd = q.shape
-    check_sink(q.dtype, hd, sink)
-    doc = _fold_window(window, doc, B, S, q.dtype, hd, q.device)
-    check_doc(q.dtype, hd, doc)
-    Dp = pad_dim(q.dtype, hd)
+    Dp, doc = _enter(q.dtype, hd, B, S, q.device, doc, window, sink)
     hm = (nh * S * hd, hd, S * hd)
     if Dp and q.dtype == torch.float32:
         ts = [t.contiguous() for t in (q, k, v)]

@@ -619,20 +619,13 @@ def _req_nkv(nh: int, nkv, name: str) -> int:
     return nkv
 
 
-def _no_gqa_f32(name: str):
-    raise NotImplementedError(f"{name}: grouped-query attention (nkv=) is not implemented for fp32 activations")
-
-
 def rope_qk_inplace(qkv, B, S, nh, cos, sin, nkv=None):
     """Rotate the q and k column blocks of the packed [B*S, 3H] QKV in place.  With ``nkv``
     (grouped-query attention) the row is [B*S, H + 2*KV]: nh q heads | nkv k heads | nkv v heads."""
     if nkv is not None:
         nkv = _req_nkv(nh, nkv, "rope_qk_inplace")
     if qkv.dtype == torch.float32:
-        if nkv is not None:
-            _no_gqa_f32("rope_qk_inplace")
-        from . import hip_f32
-        return hip_f32.rope_qk_inplace(qkv, B, S, nh, cos, sin)
+        return _f32("rope_qk_inplace", qkv.shape[1] // (3 * nh), nkv=nkv).rope_qk_inplace(qkv, B, S, nh, cos, sin)
     M, Wd = qkv.shape
     heads = 3 * nh if nkv is None else nh + 2 * nkv
     hd = Wd // heads
@@ -850,8 +843,6 @@ def _head_major_nkv(q, k, v, nkv, name: str):
     if tuple(k.shape) != (q.shape[0], nkv, q.shape[2], q.shape[3]):
         raise ValueError(f"{name}: k / v must be [B, nkv, S, hd] = {[q.shape[0], nkv, q.shape[2], q.shape[3]]}, "
                          f"got {list(k.shape)}")
-    if q.dtype == torch.float32:
-        _no_gqa_f32(name)
     return nkv
 
 
@@ -941,9 +932,17 @@ def _attn_sink(sink, nh: int, device, name: str, grad: bool = False):
     return sink
 
 
-def _no_sink_f32(sink, name: str):
-    if sink is not None:
-        raise NotImplementedError(f"{name}: attention sinks are not implemented for fp32 activations on the GPU")
+def _f32(name: str, hd: int, doc=None, window=None, sink=None, nkv=None, scale=None):
+    """``hip_f32``, for an fp32 call to hand over to: the fp32 routes have no document mask, window,
+    sinks or grouped K/V, and their score scale is 1/sqrt(head_dim)."""
+    from . import attn_routes, hip_f32
+    rt = attn_routes.route(torch.float32, hd)
+    for feature, arg in (("sinks", sink), ("gqa", nkv), ("window", window), ("doc", doc)):
+        if arg is not None:
+            attn_routes.require(rt, feature, name)
+    if scale is not None:
+        raise NotImplementedError("fp32 attention: the score scale is 1/sqrt(head_dim)")
+    return hip_f32
 
 
 def _attn_fwd_launch(name, src, o, lse, keep, key, lo, B, nh, nkv, S, hd, hk, scale, sink=None):
@@ -991,13 +990,8 @@ def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=
     value row; the SINK kernels); the returned lse holds it."""
     nkv = _head_major_nkv(q, k, v, nkv, "attn")
     if q.dtype == torch.float32:
-        _no_sink_f32(sink, "attention_fwd")
-        from . import hip_f32
-        if window is not None:
-            hip_f32._no_window()
-        if scale is not None:
-            raise NotImplementedError("fp32 attention: the score scale is 1/sqrt(head_dim)")
-        return hip_f32.attention_fwd(q, k, v, p, key, causal, store_mask=store_mask, out=out, mask=mask, doc=doc)
+        return _f32("attention_fwd", q.shape[3], doc, window, sink, nkv, scale).attention_fwd(
+            q, k, v, p, key, causal, store_mask=store_mask, out=out, mask=mask)
     if not causal:
         raise NotImplementedError("only causal attention is implemented (the model is a causal LM)")
     B, nh, S, hd = q.shape
@@ -1038,14 +1032,8 @@ def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=
     attention) the packed row is [H + 2*KV]; lse and the keep bits stay per query head.
     ``window``, ``sink``: see :func:`attention_fwd`."""
     if qkv.dtype == torch.float32:
-        _no_sink_f32(sink, "attention_fwd_packed")
-        if nkv is not None:
-            _no_gqa_f32("attention_fwd_packed")
-        from . import hip_f32
-        if window is not None:
-            hip_f32._no_window()
-        return hip_f32.attention_fwd_packed(qkv, B, S, nh, p, key, out=out, mask=mask, store_mask=store_mask,
-                                            doc=doc)
+        return _f32("attention_fwd_packed", qkv.shape[1] // (3 * nh), doc, window, sink, nkv).attention_fwd_packed(
+            qkv, B, S, nh, p, key, out=out, mask=mask, store_mask=store_mask)
     M, H, hd, KV = _packed_dims(qkv, B, S, nh, nkv)
     window, doc = _window_doc(window, doc, B, S, qkv.device, "attn")
     lo, _ = _req_doc(doc, B, S, qkv.device, "attn")
@@ -1070,13 +1058,8 @@ def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, 
     ``dsink[h] += -sum_{b,q} exp(sink[h] - lse) * rowsum(dO * O)`` in a fixed order (no atomics);
     dq / dk / dv need only the forward's lse."""
     if qkv.dtype == torch.float32:
-        _no_sink_f32(sink, "attention_bwd_packed")
-        if nkv is not None:
-            _no_gqa_f32("attention_bwd_packed")
-        from . import hip_f32
-        if window is not None:
-            hip_f32._no_window()
-        return hip_f32.attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=out, doc=doc)
+        return _f32("attention_bwd_packed", qkv.shape[1] // (3 * nh), doc, window, sink, nkv).attention_bwd_packed(
+            qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=out)
     M, H, hd, KV = _packed_dims(qkv, B, S, nh, nkv)
     Wd = H + 2 * KV
     window, doc = _window_doc(window, doc, B, S, qkv.device, "attn_bwd")
@@ -1105,13 +1088,8 @@ def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, scale=None, doc=None
     attention, see :func:`attention_fwd`).  ``sink`` / ``dsink``: see :func:`attention_bwd_packed`."""
     nkv = _head_major_nkv(q, k, v, nkv, "attn_bwd")
     if q.dtype == torch.float32:
-        _no_sink_f32(sink, "attention_bwd")
-        from . import hip_f32
-        if window is not None:
-            hip_f32._no_window()
-        if scale is not None:
-            raise NotImplementedError("fp32 attention: the score scale is 1/sqrt(head_dim)")
-        return hip_f32.attention_bwd(q, k, v, o, do, aux, p, key, causal, doc=doc)
+        return _f32("attention_bwd", q.shape[3], doc, window, sink, nkv, scale).attention_bwd(
+            q, k, v, o, do, aux, p, key, causal)
     B, nh, S, hd = q.shape
     n = B * nh * S * hd
     nk = B * (nkv or nh) * S * hd

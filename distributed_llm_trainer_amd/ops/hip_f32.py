@@ -369,25 +369,7 @@ def _fwd(qp, kp, vp, strides, B, nh, S, hd, p, key, device, out, mask, store_mas
     return o, _h().AttnAux((lse, mask if store_mask else None))
 
 
-def _no_doc(doc) -> None:
-    """The document mask exists in the 16-bit MFMA flash kernels only; the fp32 routes
-    (VALU flash, GEMM formulation) say so instead of attending across documents."""
-    if doc is not None:
-        raise NotImplementedError(
-            "document-masked attention (doc_sep_token) is not implemented on the fp32 attention route "
-            "(fp32 flash / fp32 GEMM formulation); use bf16 or fp16 activations with head_dim <= 128")
-
-
-def _no_window() -> None:
-    """Sliding-window attention runs on the DOC forms of the 16-bit flash kernels; the fp32
-    routes have none."""
-    raise NotImplementedError(
-        "sliding-window attention (sliding_window) is not implemented on the fp32 attention route "
-        "(fp32 flash / fp32 GEMM formulation); use bf16 or fp16 activations with head_dim <= 128")
-
-
-def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=None, doc=None):
-    _no_doc(doc)
+def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=None):
     if not causal:
         raise NotImplementedError("only causal attention is implemented (the model is a causal LM)")
     B, nh, S, hd = q.shape
@@ -399,8 +381,7 @@ def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=
                 store_mask)
 
 
-def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=True, doc=None):
-    _no_doc(doc)
+def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=True):
     M, threeH = qkv.shape
     hd = threeH // (3 * nh)
     if M != B * S or hd * 3 * nh != threeH:
@@ -427,8 +408,7 @@ def _bwd(qp, kp, vp, strides, o, do, aux, B, nh, S, hd, p, key, device, gp, gstr
          "f32_attn_bwd")
 
 
-def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, doc=None):
-    _no_doc(doc)
+def attention_bwd(q, k, v, o, do, aux, p, key, causal=True):
     B, nh, S, hd = q.shape
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
         _req32(t, "attn_bwd_f32." + n, B * nh * S * hd)
@@ -440,10 +420,9 @@ def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, doc=None):
     return dq, dk, dv
 
 
-def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, doc=None):
+def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None):
     """dqkv [B*S, 3H] (pre-RoPE): the attention backward writes raw dq / dk / dv into the
     packed layout, then the inverse rotation runs in place on the q and k blocks."""
-    _no_doc(doc)
     M, threeH = qkv.shape
     hd = threeH // (3 * nh)
     _req32(qkv, "attn_bwd_f32.qkv")

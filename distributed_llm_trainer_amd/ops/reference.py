@@ -281,7 +281,7 @@ def window_bounds(B: int, S: int, W: int, device, doc=None) -> Tuple[torch.Tenso
     hi = (pos + (int(W) - 1)).clamp_(max=S - 1).to(torch.int32)
     lo, hi = lo.expand(B, S), hi.expand(B, S)
     if doc is not None:
-        dlo, dhi = _check_doc(doc, B, S, device, "window_bounds")
+        dlo, dhi = _req_doc(doc, B, S, device, "window_bounds")
         lo, hi = torch.maximum(lo, dlo), torch.minimum(hi, dhi)
     return WindowBounds(lo.contiguous(), hi.contiguous(), W)
 
@@ -297,7 +297,7 @@ def _fold_window(window, doc, B: int, S: int, device):
     return window_bounds(B, S, int(window), device, doc=doc)
 
 
-def _check_doc(doc, B: int, S: int, device, name: str):
+def _req_doc(doc, B: int, S: int, device, name: str):
     """``doc`` = (lo, hi) of :func:`doc_bounds`: int32, contiguous, [B, S], on ``device``."""
     if not isinstance(doc, (tuple, list)) or len(doc) != 2:
         raise TypeError(f"{name}: doc must be None or (lo, hi)")
@@ -321,7 +321,7 @@ def _masked_out(S: int, device, causal: bool, doc, B: int, name: str) -> Optiona
         return mask
     if not causal:
         raise NotImplementedError("the document mask is defined for causal attention")
-    lo, _ = _check_doc(doc, B, S, device, name)
+    lo, _ = _req_doc(doc, B, S, device, name)
     kpos = torch.arange(S, device=device).view(1, 1, 1, S)
     return mask | (kpos < lo.view(B, 1, S, 1))
 
@@ -342,7 +342,7 @@ def _rep_kv(t: torch.Tensor, G: int) -> torch.Tensor:
     return t if G == 1 else t.repeat_interleave(G, dim=1)
 
 
-def _check_sink(sink, nh: int, device, name: str, grad: bool = False) -> torch.Tensor:
+def _req_sink(sink, nh: int, device, name: str, grad: bool = False) -> torch.Tensor:
     """``sink`` of the attention ops: one logit per query head, [nh], on ``device``; fp32 (a
     gathered 16-bit FSDP unit is upcast).  ``grad``: the fp32 gradient accumulator, as it is."""
     if not isinstance(sink, torch.Tensor) or not sink.is_floating_point() or tuple(sink.shape) != (nh,):
@@ -375,7 +375,7 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, p: float, k
         s = s.masked_fill(mask, float("-inf"))
     lse = torch.logsumexp(s, dim=-1)
     if sink is not None:
-        lse = torch.logaddexp(lse, _check_sink(sink, nh, q.device, "attn.sink").view(1, nh, 1).expand_as(lse))
+        lse = torch.logaddexp(lse, _req_sink(sink, nh, q.device, "attn.sink").view(1, nh, 1).expand_as(lse))
     prob = torch.exp(s - lse.unsqueeze(-1))
     if p > 0.0:
         keep = rng.attn_keep_mask(B * nh, S, S, key, p, device=q.device).view(B, nh, S, S)
@@ -419,8 +419,8 @@ def attention_bwd(q, k, v, o, do, lse, p: float, key: int, causal: bool = True, 
     dp = torch.where(keep, dpd / (1.0 - p), torch.zeros((), device=q.device)) if keep is not None else dpd
     delta = (dof * of).sum(dim=-1, keepdim=True)
     if sink is not None:
-        sink = _check_sink(sink, nh, q.device, "attn_bwd.sink")
-        _check_sink(dsink, nh, q.device, "attn_bwd.dsink", grad=True)
+        sink = _req_sink(sink, nh, q.device, "attn_bwd.sink")
+        _req_sink(dsink, nh, q.device, "attn_bwd.dsink", grad=True)
         p_sink = torch.exp(sink.view(1, nh, 1) - lse)
         dsink += -(p_sink * delta.squeeze(-1)).sum(dim=(0, 2))
     ds = prob * (dp - delta)

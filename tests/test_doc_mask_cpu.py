@@ -333,16 +333,16 @@ def test_eval_loss_applies_the_mask():
 def test_routes_without_the_mask_say_so():
     """The choice is made from (device, head_dim, dtype) alone, so it needs no GPU."""
     from distributed_llm_trainer_amd import ops
-    ops.check_doc_mask("cpu", 160, torch.float32)       # reference ops mask densely
-    ops.check_doc_mask("cuda", 64, torch.bfloat16)
-    ops.check_doc_mask("cuda", 128, torch.float16)
-    ops.check_doc_mask("cuda", 96, torch.bfloat16)      # zero-padded onto the flash kernels
+    ops.check_attention_features("cpu", 160, torch.float32, {"doc"})       # reference ops mask densely
+    ops.check_attention_features("cuda", 64, torch.bfloat16, {"doc"})
+    ops.check_attention_features("cuda", 128, torch.float16, {"doc"})
+    ops.check_attention_features("cuda", 96, torch.bfloat16, {"doc"})      # zero-padded onto the flash kernels
     with pytest.raises(NotImplementedError, match="GEMM-formulated"):
-        ops.check_doc_mask("cuda", 160, torch.bfloat16)
+        ops.check_attention_features("cuda", 160, torch.bfloat16, {"doc"})
     with pytest.raises(NotImplementedError, match="fp32"):
-        ops.check_doc_mask("cuda", 64, torch.float32)
+        ops.check_attention_features("cuda", 64, torch.float32, {"doc"})
     with pytest.raises(NotImplementedError, match="fp32"):
-        ops.check_doc_mask("cuda", 96, torch.float32)
+        ops.check_attention_features("cuda", 96, torch.float32, {"doc"})
 
 
 # ------------------------------------------------------------------ 5. configuration

@@ -392,9 +392,9 @@ def test_unsupported_routes_refuse_at_enable_engine():
     with pytest.raises(NotImplementedError, match="head_dim"):
         m96.enable_engine()
     with pytest.raises(NotImplementedError):
-        ops.check_gqa(DEV, 192, torch.bfloat16)  # the GEMM-formulated route
-    ops.check_gqa(DEV, 64, torch.float16)
-    ops.check_gqa(DEV, 128, torch.bfloat16)
+        ops.check_attention_features(DEV, 192, torch.bfloat16, {"gqa"})  # the GEMM-formulated route
+    ops.check_attention_features(DEV, 64, torch.float16, {"gqa"})
+    ops.check_attention_features(DEV, 128, torch.bfloat16, {"gqa"})
     GPT(_cfg(0.0, num_kv_heads=None, hidden_size=384)).to(DEV).enable_engine()  # MHA still takes head_dim 96
 
 

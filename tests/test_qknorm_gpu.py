@@ -310,9 +310,9 @@ def test_unsupported_routes_refuse_at_enable_engine(monkeypatch):
     with pytest.raises(NotImplementedError, match="head_dim"):
         m96.enable_engine()
     with pytest.raises(NotImplementedError):
-        ops.check_qk_norm(DEV, 192, torch.bfloat16)  # the GEMM-formulated route
-    ops.check_qk_norm(DEV, 64, torch.float16)
-    ops.check_qk_norm(DEV, 128, torch.bfloat16)
+        ops.check_attention_features(DEV, 192, torch.bfloat16, {"qk_norm"})  # the GEMM-formulated route
+    ops.check_attention_features(DEV, 64, torch.float16, {"qk_norm"})
+    ops.check_attention_features(DEV, 128, torch.bfloat16, {"qk_norm"})
     monkeypatch.setenv("DLT_PACKED_QKV", "0")
     with pytest.raises(NotImplementedError, match="packed"):
         GPT(_cfg(0.0)).to(DEV).enable_engine()

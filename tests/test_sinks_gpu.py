@@ -326,13 +326,13 @@ def test_unsupported_routes_refuse_at_enable_engine():
         m.enable_engine(act_dtype=torch.float32)
     assert m.engine is None and m.store is None
     with pytest.raises(NotImplementedError, match="attention sinks"):
-        ops.check_attention_sinks(DEV, 192, torch.bfloat16)  # the GEMM-formulated route
+        ops.check_attention_features(DEV, 192, torch.bfloat16, {"sinks"})  # the GEMM-formulated route
     m192 = GPT(_cfg(0.0, hidden_size=768)).to(DEV)  # head_dim 192
     with pytest.raises(NotImplementedError, match="attention sinks"):
         m192.enable_engine()
     for hd, dt in ((64, torch.float16), (128, torch.bfloat16), (96, torch.bfloat16), (32, torch.float16)):
-        ops.check_attention_sinks(DEV, hd, dt)
-    ops.check_attention_sinks("cpu", 192, torch.float32)
+        ops.check_attention_features(DEV, hd, dt, {"sinks"})
+    ops.check_attention_features("cpu", 192, torch.float32, {"sinks"})
 
 
 # ------------------------------------------------------------------ 3. decode

@@ -370,11 +370,11 @@ def test_engine_chain_state_and_cached_bounds():
     w1 = eng._window_bounds(st, ids.device)
     assert w1 is eng._window_bounds(st, ids.device), "without a separator the bounds are built once"
     st.win = w1
-    assert eng._attn_bounds_kw(st, 0) == {"doc": w1, "window": 5} and eng._attn_bounds_kw(st, 1) == {}
+    assert eng._attn_kw(st, 0, None) == {"doc": w1, "window": 5} and eng._attn_kw(st, 1, None) == {}
     st.doc = ref.doc_bounds(ids, SEP)
     st.win = eng._window_bounds(st, ids.device)
     assert torch.equal(st.win[0], torch.maximum(w1[0], st.doc[0])) and torch.equal(st.win[1], torch.minimum(w1[1], st.doc[1]))
-    assert eng._attn_bounds_kw(st, 1) == {"doc": st.doc}
+    assert eng._attn_kw(st, 1, None) == {"doc": st.doc}
     st.S = 5  # the window covers the batch: the plain path
     assert eng._window_bounds(st, ids.device) is None
 
@@ -414,15 +414,15 @@ def test_eval_loss_applies_the_window():
 
 
 def test_routes_that_refuse_the_window():
-    ops.check_sliding_window("cpu", 160, torch.float32)  # the CPU ops mask densely
-    ops.check_sliding_window("cuda", 64, torch.bfloat16)
-    ops.check_sliding_window("cuda", 96, torch.float16)   # zero-padded onto the flash kernels
+    ops.check_attention_features("cpu", 160, torch.float32, {"window"})  # the CPU ops mask densely
+    ops.check_attention_features("cuda", 64, torch.bfloat16, {"window"})
+    ops.check_attention_features("cuda", 96, torch.float16, {"window"})   # zero-padded onto the flash kernels
     with pytest.raises(NotImplementedError, match="GEMM-formulated"):
-        ops.check_sliding_window("cuda", 160, torch.bfloat16)
+        ops.check_attention_features("cuda", 160, torch.bfloat16, {"window"})
     with pytest.raises(NotImplementedError, match="fp32"):
-        ops.check_sliding_window("cuda", 64, torch.float32)
+        ops.check_attention_features("cuda", 64, torch.float32, {"window"})
     with pytest.raises(NotImplementedError, match="sliding"):
-        ops.check_sliding_window("cuda", 96, torch.float32)
+        ops.check_attention_features("cuda", 96, torch.float32, {"window"})
 
 
 # ------------------------------------------------------------------ checkpoints and the CLI
