@@ -46,6 +46,7 @@ other leaves idle.  The reference runs the micro-steps strictly one after the ot
 from __future__ import annotations
 
 import contextlib
+import math
 import os
 from dataclasses import dataclass, field
 from typing import Any, Callable, Dict, List, Optional
@@ -123,6 +124,14 @@ class ParamProvider:
     def post_backward(self, unit) -> None: pass
 
 
+def check_z_loss(coef) -> float:
+    """The z-loss coefficient as a float; ValueError unless it is finite and >= 0."""
+    c = float(coef)
+    if not math.isfinite(c) or c < 0.0:
+        raise ValueError(f"z_loss must be a finite coefficient >= 0, got {coef!r}")
+    return c
+
+
 def shift_targets(labels: torch.Tensor) -> torch.Tensor:
     """labels [B,S] -> per-row targets [B*S]: labels[b, s+1], IGNORE at s = S-1.
 
@@ -177,6 +186,7 @@ class _StepState:
     d_last: Any = None  # bf16 d of last layer (input of final norm)
     doc: Any = None     # document mask bounds (lo, hi) of ids, or None (set_doc_separator)
     win: Any = None     # bounds of the windowed layers: window_bounds merged with doc, or None
+    loss_parts: Any = None  # (cross-entropy, weighted z term) of this forward's loss (set_z_loss)
 
 
 class GPTEngine:
@@ -193,6 +203,13 @@ class GPTEngine:
         # trainer's loss scale) so it does not underflow; the backward divides it out
         # where it applies dloss (the lm_head weight / data gradients)
         self.ce_grad_scale = 1.0
+        # auxiliary z-loss coefficient of the training head (set_z_loss); 0 = off
+        self.z_loss = 0.0
+        # (cross-entropy, weighted z term) of the last training-head forward, and of every
+        # micro-step chain of the last train_window: device scalars, no host sync
+        self.last_loss_parts: Any = None
+        self.window_loss_parts: List[Any] = []
+        self._zeros: Dict[Any, torch.Tensor] = {}
         self.gemm = gemm or _TorchGemm()
         self._rope = {}
         # dropout probabilities (zeroed in eval mode)
@@ -316,6 +333,32 @@ class GPTEngine:
             if getattr(self.ops, "backend", "") == "hip":  # the GPU routes; reference ops mask densely
                 attn_routes.check_attention_features("cuda", self.cfg.head_dim, self.act_dtype, {"doc"})
         self.doc_sep_token = token_id
+
+    def set_z_loss(self, coef: float) -> None:
+        """Auxiliary z-loss of the training head: the loss becomes ``ce + coef * mean(lse^2)``,
+        ``lse`` the log-partition of the output softmax over the real vocabulary and the mean
+        taken over the valid targets exactly as the cross-entropy's (per fused micro-step
+        segment).  The cross-entropy kernel adds the term's gradient to dlogits in place
+        (its Z form), so nothing else in the backward changes.  0 (the default) runs the
+        plain kernels.  Evaluation (``eval_loss``) reports plain cross-entropy whatever the
+        coefficient.  A property of the objective, not of the model: not in GPTConfig or
+        in checkpoints."""
+        self.z_loss = check_z_loss(coef)
+
+    def _zero_scalar(self, dev) -> torch.Tensor:
+        z = self._zeros.get(dev)
+        if z is None:
+            z = self._zeros[dev] = torch.zeros((), dtype=torch.float32, device=dev)
+        return z
+
+    def _head_ce(self, lg, targets, V: int, norm, zparts: list) -> torch.Tensor:
+        """One cross-entropy call of the training head (gradient in place, pre-scaled by
+        ce_grad_scale).  With a z-loss coefficient: the Z form, whose rows' lse^2 join ``zparts``."""
+        if self.z_loss == 0.0:
+            return self.ops.cross_entropy_fwd_bwd(lg, targets, V, norm, self.ce_grad_scale)
+        z_rows = torch.empty(lg.shape[0], dtype=torch.float32, device=lg.device)
+        zparts.append(z_rows)
+        return self.ops.cross_entropy_fwd_bwd(lg, targets, V, norm, self.ce_grad_scale, self.z_loss, z_rows)
 
     def set_loss_segments(self, n: int) -> None:
         """Declare that each training forward carries ``n`` fused micro-steps.
@@ -759,6 +802,7 @@ class GPTEngine:
             else:
                 nvs = [(targets[a:b] != -100).sum() for a, b in segs]
                 norms = [nv * nseg for nv in nvs]
+            zparts: list = []  # the rows' lse^2 of every Z-form call, in row order (set_z_loss)
             chunked = need_bwd and self.head_chunks > 0
             if chunked:
                 st.head_rows = self._head_rows(rows, nseg)
@@ -778,8 +822,7 @@ class GPTEngine:
                 parts = []
                 for ci, (a, b) in enumerate(st.head_rows):
                     lg = self.gemm.linear(nf[a:b], hw.lm_head, out=lg_buf[:b - a])
-                    parts.append(self.ops.cross_entropy_fwd_bwd(lg, targets[a:b], V, norms[a * nseg // rows],
-                                                                self.ce_grad_scale))
+                    parts.append(self._head_ce(lg, targets[a:b], V, norms[a * nseg // rows], zparts))
                     self._head_chunk_bwd(lg, hw.lm_head, dnf[a:b], hacc, nfs[a:b], ci == 0)
                 del nfs
                 if self.head_share and lg_buf.is_cuda:
@@ -793,10 +836,9 @@ class GPTEngine:
                 lg_out = self._sb(st, "head", "lg", rows, Vp, nf.device)
                 lg = self.gemm.linear(nf, hw.lm_head, out=lg_out)
                 if nseg == 1:
-                    row_loss = self.ops.cross_entropy_fwd_bwd(lg, targets, V, norms[0], self.ce_grad_scale)
+                    row_loss = self._head_ce(lg, targets, V, norms[0], zparts)
                 else:
-                    row_loss = torch.cat([self.ops.cross_entropy_fwd_bwd(lg[a:b], targets[a:b], V, norms[k],
-                                                                         self.ce_grad_scale)
+                    row_loss = torch.cat([self._head_ce(lg[a:b], targets[a:b], V, norms[k], zparts)
                                           for k, (a, b) in enumerate(segs)])
                 if need_bwd:
                     st.dlogits = lg  # now holds ce_grad_scale * d(mean loss)/d(logits)
@@ -805,6 +847,19 @@ class GPTEngine:
             else:
                 loss = torch.stack([row_loss[a:b].sum() / nvs[k].clamp(min=1).float()
                                     for k, (a, b) in enumerate(segs)]).mean()
+            if zparts:
+                # the z term, normalised as the cross-entropy is: per segment by its valid count
+                z_rows = zparts[0] if len(zparts) == 1 else torch.cat(zparts)
+                if nseg == 1:
+                    z_mean = z_rows.sum() / nvs[0].clamp(min=1).float()
+                else:
+                    z_mean = torch.stack([z_rows[a:b].sum() / nvs[k].clamp(min=1).float()
+                                          for k, (a, b) in enumerate(segs)]).mean()
+                ce, z_term = loss, self.z_loss * z_mean
+                loss = ce + z_term
+            else:
+                ce, z_term = loss, self._zero_scalar(loss.device)
+            self.last_loss_parts = st.loss_parts = (ce, z_term)
             if need_bwd:
                 st.ce_scale = self.ce_grad_scale
                 st.xf, st.rstdf, st.nf = xf, rstdf, nf
@@ -1353,6 +1408,7 @@ class GPTEngine:
                           main, p0, streams):
         losses: List[Any] = [None, None]
         states: List[Any] = [None, None]
+        self.window_loss_parts = [None, None]
         ready: List[Any] = []
         # forwards: chain 0 first in every round (micro-step numbering = dropout streams)
         gens = [self._forward_gen(micro_ids[k], micro_targets[k], True, recompute, need_backward=True,
@@ -1366,6 +1422,7 @@ class GPTEngine:
                     except StopIteration as stop:
                         live.remove(k)
                         losses[k], _, states[k] = stop.value
+                        self.window_loss_parts[k] = states[k].loss_parts
                         if k == 0:
                             ev = torch.cuda.Event()
                             ev.record()
@@ -1473,8 +1530,10 @@ class GPTEngine:
 
         losses: List[Any] = [None] * GA
         states: List[Any] = [None] * GA
+        self.window_loss_parts = [None] * GA
         with on(0):
             losses[0], _, states[0] = _drain(fwd(0))
+            self.window_loss_parts[0] = states[0].loss_parts
         for k in range(GA):
             if k == GA - 1:
                 if cuda and GA > 1 and not overlap:
@@ -1503,6 +1562,7 @@ class GPTEngine:
                             running.remove(item)
                             if is_fwd:
                                 losses[j], _, states[j] = stop.value
+                                self.window_loss_parts[j] = states[j].loss_parts
         if overlap:  # the optimizer (current stream) must see every backward's gradients
             main.wait_stream(pipe)
         return losses

@@ -207,6 +207,33 @@ class GPT(nn.Module):
         # intra-document attention mask (set_doc_separator); run-time state, not a
         # GPTConfig field: checkpoints and the pickled config are unchanged
         self.doc_sep_token: Optional[int] = None
+        # auxiliary z-loss coefficient (set_z_loss): a property of the objective, likewise
+        # run-time state; and the (cross-entropy, weighted z term) of the last forward with labels
+        self.z_loss: float = 0.0
+        self._loss_parts = None
+
+    def set_z_loss(self, coef: float) -> None:
+        """Auxiliary z-loss (PaLM): a forward with labels returns ``ce + coef * mean(z^2)``,
+        ``z = logsumexp(logits)`` per predicted token, the mean over the tokens whose label
+        is not ``ignore_index`` as for the cross-entropy.  It keeps the output logits from
+        drifting to magnitudes at which a 16-bit lm_head loses its low bits; PaLM uses 1e-4.
+        0 (the default) is plain cross-entropy.  ``last_loss_parts`` has the two parts.
+        ``eval_loss`` / ``eval_loss_sum`` always report plain cross-entropy.  Applies to the
+        eager path and to the engine (now or when it is enabled later).  Raises ValueError
+        for a negative or non-finite coefficient."""
+        from .engine import check_z_loss
+        coef = check_z_loss(coef)
+        if self.engine is not None:
+            self.engine.set_z_loss(coef)
+        self.z_loss = coef
+
+    @property
+    def last_loss_parts(self):
+        """``(ce, z_term)`` of the last forward with labels: device scalars (no host sync) with
+        ``ce + z_term == loss``; ``z_term`` is the weighted term, zero without a coefficient."""
+        if self.engine is not None:
+            return self.engine.last_loss_parts
+        return self._loss_parts
 
     def set_doc_separator(self, token_id: Optional[int]) -> None:
         """Intra-document masking for packed training sequences: ``token_id`` (GPT-2:
@@ -275,6 +302,7 @@ class GPT(nn.Module):
         self.engine = GPTEngine(self.config, provider, ops, act_dtype=act_dtype, seed=seed, gemm=gemm)
         if self.doc_sep_token is not None:
             self.engine.set_doc_separator(self.doc_sep_token)
+        self.engine.set_z_loss(self.z_loss)
         self._anchor = torch.zeros((), device=dev, requires_grad=True)
         return self.engine
 
@@ -303,6 +331,14 @@ class GPT(nn.Module):
             shift_logits = logits[..., :-1, :].contiguous()
             shift_labels = labels[..., 1:].contiguous()
             loss = F.cross_entropy(shift_logits.view(-1, self.config.vocab_size), shift_labels.view(-1))
+            if self.z_loss != 0.0:
+                valid = shift_labels.reshape(-1) != -100
+                z = torch.logsumexp(shift_logits.view(-1, self.config.vocab_size).float(), dim=-1)[valid]
+                ce, z_term = loss, self.z_loss * (z ** 2).sum() / valid.sum().clamp(min=1)
+                loss = ce + z_term.to(ce.dtype)
+                self._loss_parts = (ce.detach(), z_term.detach().to(ce.dtype))
+            else:
+                self._loss_parts = (loss.detach(), torch.zeros_like(loss))
         return logits, loss
 
     def _engine_forward(self, input_ids, labels):

@@ -308,11 +308,14 @@ __global__ __launch_bounds__(256) void k_f32_swiglu_bwd(const float* __restrict_
 // One 256-thread block per row: logsumexp over the first `vocab` columns (online max /
 // sum per thread, then block combine), loss = lse - logit[target], and the row is
 // overwritten by grad_scale * (softmax - onehot) / n_valid (padding columns and ignored
-// rows: zero).
-template <int V>
+// rows: zero).  ZL: the z-loss form of loss.hip -- the softmax factor of
+// the row carries zf = 1 + 2 c lse, the target element is (p * zf - 1), and z_rows gets
+// lse^2 (0 on ignored rows); `loss` stays the cross-entropy part.
+template <int V, bool ZL = false>
 __global__ __launch_bounds__(256) void k_f32_ce_row(float* __restrict__ logits, const long* __restrict__ targets,
                                                     const long* __restrict__ n_valid, float* __restrict__ loss, int Vp,
-                                                    int vocab, float grad_scale) {
+                                                    int vocab, float grad_scale, float zcoef,
+                                                    float* __restrict__ z_rows) {
   __shared__ float sm[4], sl[4];
   const int row = blockIdx.x, tid = threadIdx.x;
   float* lg = logits + (size_t)row * Vp;
@@ -362,14 +365,25 @@ __global__ __launch_bounds__(256) void k_f32_ce_row(float* __restrict__ logits, 
   const bool valid = tg != -100;
   const float nv = (float)(n_valid[0] > 0 ? n_valid[0] : 1);
   if (tid == 0) loss[row] = valid ? lse - lg[tg] : 0.f;
+  float zf = 1.f;
+  if constexpr (ZL) {
+    zf = fmaf(2.f * zcoef, lse, 1.f);
+    if (tid == 0) z_rows[row] = valid ? lse * lse : 0.f;
+  }
   __syncthreads();  // the target logit is read before any thread overwrites it
   const float gs = valid ? grad_scale / nv : 0.f;
+  const float gz = ZL ? gs * zf : gs;
   for (int c0 = tid * V; c0 < Vp; c0 += 256 * V) {
     F32Vec<V> g = f32_ldv<V>(lg + c0);
 #pragma unroll
     for (int i = 0; i < V; ++i) {
       const int c = c0 + i;
-      g.v[i] = (c < vocab && valid) ? (__expf(g.v[i] - lse) - (c == tg ? 1.f : 0.f)) * gs : 0.f;
+      if constexpr (ZL) {
+        const float p = __expf(g.v[i] - lse);
+        g.v[i] = (c < vocab && valid) ? (c == tg ? (p * zf - 1.f) * gs : p * gz) : 0.f;
+      } else {
+        g.v[i] = (c < vocab && valid) ? (__expf(g.v[i] - lse) - (c == tg ? 1.f : 0.f)) * gs : 0.f;
+      }
     }
     f32_stv<V>(lg + c0, g);
   }
@@ -724,8 +738,18 @@ DLT_API int dlt_f32_swiglu_bwd(const float* gu, const float* da, float* dgu, flo
 DLT_API int dlt_f32_cross_entropy(float* logits, const long* targets, const long* n_valid, float* loss, int M, int Vp,
                                   int vocab, float grad_scale, hipStream_t st) {
   if (M <= 0) return 0;
-  if (Vp % 4 == 0 && f32_al16(logits)) k_f32_ce_row<4><<<M, 256, 0, st>>>(logits, targets, n_valid, loss, Vp, vocab, grad_scale);
-  else k_f32_ce_row<1><<<M, 256, 0, st>>>(logits, targets, n_valid, loss, Vp, vocab, grad_scale);
+  if (Vp % 4 == 0 && f32_al16(logits)) k_f32_ce_row<4><<<M, 256, 0, st>>>(logits, targets, n_valid, loss, Vp, vocab, grad_scale, 0.f, nullptr);
+  else k_f32_ce_row<1><<<M, 256, 0, st>>>(logits, targets, n_valid, loss, Vp, vocab, grad_scale, 0.f, nullptr);
+  DLT_CHECK_LAUNCH();
+}
+
+// the z-loss form: zcoef joins the gradient, z_rows [M] receives lse^2 (see k_f32_ce_row)
+DLT_API int dlt_f32_cross_entropy_z(float* logits, const long* targets, const long* n_valid, float* loss, int M, int Vp,
+                                    int vocab, float grad_scale, float zcoef, float* z_rows, hipStream_t st) {
+  if (!z_rows || vocab > Vp) return -1;
+  if (M <= 0) return 0;
+  if (Vp % 4 == 0 && f32_al16(logits)) k_f32_ce_row<4, true><<<M, 256, 0, st>>>(logits, targets, n_valid, loss, Vp, vocab, grad_scale, zcoef, z_rows);
+  else k_f32_ce_row<1, true><<<M, 256, 0, st>>>(logits, targets, n_valid, loss, Vp, vocab, grad_scale, zcoef, z_rows);
   DLT_CHECK_LAUNCH();
 }
 

@@ -15,13 +15,22 @@
 // x 13 chunks (94 VGPRs, five waves per SIMD), bench step -0.1 to -0.2 ms
 // (round-2 harness ab_ce.sh, in git history; DLT_CE_THREADS=512 selects the older shape).  Rows too long for
 // registers fall back to k_ce_fwd_bwd (online max/sum pass + gradient pass).
+//
+// Z forms (ZL = true; launched with a coefficient and z_rows): the auxiliary z-loss
+// c * lse^2 of the row.  Its gradient is 2 c lse * softmax, so the row's softmax factor
+// becomes zf = 1 + 2 c lse (one fma per row; it may be negative, and is used as it is) and
+// the target element (p * zf - 1).  loss_rows keeps the cross-entropy part alone and z_rows
+// receives lse^2 (0 on ignored rows); the caller forms c * sum(z_rows) / n_valid.  ZL is
+// compile-time: the plain forms never read the two extra arguments and keep the vector
+// code, registers, LDS and scratch they had before the Z forms existed (profiles/z_loss.md).
 #include "common.h"
 #include <cstdlib>
 
-template <int HK = 0>
+template <int HK = 0, bool ZL = false>
 __global__ __launch_bounds__(256) void k_ce_fwd_bwd(bf16_t* __restrict__ logits, const int64_t* __restrict__ targets,
                                                     const int64_t* __restrict__ n_valid, float* __restrict__ loss_rows,
-                                                    int M, int Vp, int V, float gscale) {
+                                                    int M, int Vp, int V, float gscale, float zcoef,
+                                                    float* __restrict__ z_rows) {
   __shared__ float sm_m[4], sm_s[4];
   const int row = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -63,9 +72,15 @@ __global__ __launch_bounds__(256) void k_ce_fwd_bwd(bf16_t* __restrict__ logits,
   for (int w = 0; w < 4; ++w) gs += (sm_m[w] == -INFINITY) ? 0.f : sm_s[w] * __expf(sm_m[w] - gm);
   const float lse = gm + __logf(gs);
   if (tid == 0) loss_rows[row] = valid ? (lse - h2f<HK>(lrow[tgt])) : 0.f;
+  float zf = 1.f;
+  if constexpr (ZL) {
+    zf = fmaf(2.f * zcoef, lse, 1.f);
+    if (tid == 0) z_rows[row] = valid ? lse * lse : 0.f;
+  }
   __syncthreads();  // everyone has read lrow[tgt] before it is overwritten
   const int64_t nv = *n_valid;
   const float inv_n = valid ? gscale / (float)(nv > 0 ? nv : 1) : 0.f;
+  const float gmul = ZL ? (valid ? inv_n * zf : 0.f) : inv_n;  // an ignored row stays +0 whatever zf is
   // pass 2: gradient in place
   for (int c = tid; c < nchunk; c += 256) {
     u16x8 x = *reinterpret_cast<const u16x8*>(lrow + c * 8);
@@ -75,8 +90,12 @@ __global__ __launch_bounds__(256) void k_ce_fwd_bwd(bf16_t* __restrict__ logits,
       float g = 0.f;
       if (col < V) {
         g = __expf(h2f<HK>(x.v[e]) - lse);
-        if (col == tgt) g -= 1.f;
-        g *= inv_n;
+        if constexpr (ZL) {
+          g = (col == tgt) ? (g * zf - 1.f) * inv_n : g * gmul;
+        } else {
+          if (col == tgt) g -= 1.f;
+          g *= inv_n;
+        }
       }
       x.v[e] = f2h<HK>(g);
     }
@@ -87,10 +106,11 @@ __global__ __launch_bounds__(256) void k_ce_fwd_bwd(bf16_t* __restrict__ logits,
 // gscale: factor on the gradient only (1 for bf16; the fp16 path stores the gradient
 // pre-multiplied by the loss scale so it does not underflow fp16, and the engine divides
 // the scale back out where it applies dloss)
-template <int CPT, int NTH = 512, bool CE_NT = false, int HK = 0>
+template <int CPT, int NTH = 512, bool CE_NT = false, int HK = 0, bool ZL = false>
 __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(NTH == 1024 ? 8 : 1, 8))) void k_ce_row(bf16_t* __restrict__ logits, const int64_t* __restrict__ targets,
                                                 const int64_t* __restrict__ n_valid, float* __restrict__ loss_rows,
-                                                int M, int Vp, int V, float gscale) {
+                                                int M, int Vp, int V, float gscale, float zcoef,
+                                                float* __restrict__ z_rows) {
   // Per element only: max, one exp2 for the sum, one exp2 + scale for the gradient.
   // Column bounds are tested per 8-wide chunk (only the last chunk straddles V), and
   // the target column is patched by its owning thread per chunk, not per element.
@@ -177,6 +197,10 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(NTH == 1024
   const int64_t nv = *n_valid;
   const float inv_n = valid ? gscale / (float)(nv > 0 ? nv : 1) : 0.f;
   const float nl2 = -lse * L2E;
+  // Z form: the row's softmax factor carries zf = 1 + 2 c lse; the plain form multiplies by inv_n alone
+  float zf = 1.f;
+  if constexpr (ZL) zf = fmaf(2.f * zcoef, lse, 1.f);
+  const float gmul = ZL ? (valid ? inv_n * zf : 0.f) : inv_n;  // an ignored row stays +0 whatever zf is
 #pragma unroll
   for (int t = 0; t < CPT; ++t) {
     const int c = tid + NTH * t;
@@ -184,11 +208,11 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(NTH == 1024
       u16x8 o;
       if (c * 8 + 8 <= V) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) o.v[e] = f2h<HK>(__builtin_amdgcn_exp2f(fmaf(el(t, e), L2E, nl2)) * inv_n);
+        for (int e = 0; e < 8; ++e) o.v[e] = f2h<HK>(__builtin_amdgcn_exp2f(fmaf(el(t, e), L2E, nl2)) * gmul);
       } else {
 #pragma unroll
         for (int e = 0; e < 8; ++e)
-          o.v[e] = f2h<HK>(c * 8 + e < V ? __builtin_amdgcn_exp2f(fmaf(el(t, e), L2E, nl2)) * inv_n : 0.f);
+          o.v[e] = f2h<HK>(c * 8 + e < V ? __builtin_amdgcn_exp2f(fmaf(el(t, e), L2E, nl2)) * gmul : 0.f);
       }
       if (c == tchunk) {
         const int e = (int)(tgt & 7);
@@ -196,7 +220,9 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(NTH == 1024
 #pragma unroll
         for (int j = 0; j < 8; ++j) l = (j == e) ? el(t, j) : l;
         loss_rows[row] = lse - l;
-        const uint16_t gt = f2h<HK>((__builtin_amdgcn_exp2f(fmaf(l, L2E, nl2)) - 1.f) * inv_n);
+        if constexpr (ZL) z_rows[row] = lse * lse;
+        const float pt = __builtin_amdgcn_exp2f(fmaf(l, L2E, nl2));
+        const uint16_t gt = f2h<HK>(((ZL ? pt * zf : pt) - 1.f) * inv_n);
 #pragma unroll
         for (int j = 0; j < 8; ++j) o.v[j] = (j == e) ? gt : o.v[j];
       }
@@ -212,33 +238,38 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(NTH == 1024
       }
     }
   }
-  if (!valid && tid == 0) loss_rows[row] = 0.f;
+  if (!valid && tid == 0) {
+    loss_rows[row] = 0.f;
+    if constexpr (ZL) z_rows[row] = 0.f;
+  }
 }
 
-template <int HK>
+// One launch choice for both forms, so a shape takes the same variant with and without the z-loss.
+template <int HK, bool ZL>
 static void ce_launch(int wide, int nt, int cpt, hipStream_t st, bf16_t* logits, const int64_t* targets,
-                      const int64_t* n_valid, float* loss_rows, int M, int Vp, int V, float gscale) {
-#define CE_ARGS logits, targets, n_valid, loss_rows, M, Vp, V, gscale
+                      const int64_t* n_valid, float* loss_rows, int M, int Vp, int V, float gscale, float zcoef,
+                      float* z_rows) {
+#define CE_ARGS logits, targets, n_valid, loss_rows, M, Vp, V, gscale, zcoef, z_rows
+#define CE_ROW(CPT, NTH, NT) k_ce_row<CPT, NTH, NT, HK, ZL><<<M, NTH, 0, st>>>(CE_ARGS)
   if (wide && (Vp / 8 + 1023) / 1024 <= 7) {  // 1024 threads x 7 chunks (Vp <= 57344)
-    if (nt) k_ce_row<7, 1024, true, HK><<<M, 1024, 0, st>>>(CE_ARGS);
-    else k_ce_row<7, 1024, false, HK><<<M, 1024, 0, st>>>(CE_ARGS);
+    if (nt) CE_ROW(7, 1024, true);
+    else CE_ROW(7, 1024, false);
     return;
   }
-  if (cpt <= 1) k_ce_row<1, 512, false, HK><<<M, 512, 0, st>>>(CE_ARGS);
-  else if (cpt <= 2) k_ce_row<2, 512, false, HK><<<M, 512, 0, st>>>(CE_ARGS);
-  else if (cpt <= 4) k_ce_row<4, 512, false, HK><<<M, 512, 0, st>>>(CE_ARGS);
-  else if (cpt <= 8) k_ce_row<8, 512, false, HK><<<M, 512, 0, st>>>(CE_ARGS);
-  else if (cpt <= 13) k_ce_row<13, 512, false, HK><<<M, 512, 0, st>>>(CE_ARGS);
-  else if (cpt <= 16) k_ce_row<16, 512, false, HK><<<M, 512, 0, st>>>(CE_ARGS);
-  else k_ce_fwd_bwd<HK><<<M, 256, 0, st>>>(CE_ARGS);
+  if (cpt <= 1) CE_ROW(1, 512, false);
+  else if (cpt <= 2) CE_ROW(2, 512, false);
+  else if (cpt <= 4) CE_ROW(4, 512, false);
+  else if (cpt <= 8) CE_ROW(8, 512, false);
+  else if (cpt <= 13) CE_ROW(13, 512, false);
+  else if (cpt <= 16) CE_ROW(16, 512, false);
+  else k_ce_fwd_bwd<HK, ZL><<<M, 256, 0, st>>>(CE_ARGS);
+#undef CE_ROW
 #undef CE_ARGS
 }
 
-// hk: logits format (0 bf16, 1 fp16); gscale multiplies the in-place gradient
-DLT_API int dlt_cross_entropy_fwd_bwd(bf16_t* logits, const int64_t* targets, const int64_t* n_valid,
-                                      float* loss_rows, int M, int Vp, int V, float gscale, int hk, hipStream_t st) {
-  if (Vp % 8 || V > Vp) return -1;
-  const int cpt = (Vp / 8 + 511) / 512;
+// The launch variant of a call: the two statics are read once per process and shared by both entry points.
+static void ce_choice(int Vp, int* wide_out, int* nt_out, int* cpt_out) {
+  *cpt_out = (Vp / 8 + 511) / 512;
   static int wide = -1;
   if (wide < 0) {
     const char* e = getenv("DLT_CE_THREADS");
@@ -252,6 +283,30 @@ DLT_API int dlt_cross_entropy_fwd_bwd(bf16_t* logits, const int64_t* targets, co
     const char* e = getenv("DLT_CE_NT");
     nt = (e && atoi(e) == 0) ? 0 : 1;
   }
-  DLT_HK_DISPATCH(hk, ce_launch<HKC>(wide, nt, cpt, st, logits, targets, n_valid, loss_rows, M, Vp, V, gscale));
+  *wide_out = wide;
+  *nt_out = nt;
+}
+
+// hk: logits format (0 bf16, 1 fp16); gscale multiplies the in-place gradient
+DLT_API int dlt_cross_entropy_fwd_bwd(bf16_t* logits, const int64_t* targets, const int64_t* n_valid,
+                                      float* loss_rows, int M, int Vp, int V, float gscale, int hk, hipStream_t st) {
+  if (Vp % 8 || V > Vp) return -1;
+  int wide, nt, cpt;
+  ce_choice(Vp, &wide, &nt, &cpt);
+  DLT_HK_DISPATCH(hk, (ce_launch<HKC, false>(wide, nt, cpt, st, logits, targets, n_valid, loss_rows, M, Vp, V, gscale,
+                                             0.f, nullptr)));
+  DLT_CHECK_LAUNCH();
+}
+
+// The Z form: as above plus the z-loss coefficient (its gradient joins the in-place gradient)
+// and z_rows [M] fp32, which receives lse^2 per row (0 on ignored rows).
+DLT_API int dlt_cross_entropy_z_fwd_bwd(bf16_t* logits, const int64_t* targets, const int64_t* n_valid,
+                                        float* loss_rows, int M, int Vp, int V, float gscale, int hk, float zcoef,
+                                        float* z_rows, hipStream_t st) {
+  if (Vp % 8 || V > Vp || !z_rows) return -1;
+  int wide, nt, cpt;
+  ce_choice(Vp, &wide, &nt, &cpt);
+  DLT_HK_DISPATCH(hk, (ce_launch<HKC, true>(wide, nt, cpt, st, logits, targets, n_valid, loss_rows, M, Vp, V, gscale,
+                                            zcoef, z_rows)));
   DLT_CHECK_LAUNCH();
 }

@@ -47,6 +47,8 @@ _SIGS = {
     "dlt_swiglu_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "dlt_cross_entropy_fwd_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int,
                                   c_void_p],
+    "dlt_cross_entropy_z_fwd_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int,
+                                    c_float, c_void_p, c_void_p],
     "dlt_sumsq": [c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
     "dlt_clip_coef": [c_void_p, c_void_p, c_float, c_float, c_float, c_void_p],
     "dlt_adamw": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float,
@@ -1144,13 +1146,32 @@ def swiglu_bwd(gu, da, out=None, s_out=None):
 
 
 # ------------------------------------------------------------ cross-entropy
-def cross_entropy_fwd_bwd(logits, targets, vocab, n_valid, grad_scale: float = 1.0):
+def check_z_rows(z_rows, logits, name: str = "ce.z_rows") -> None:
+    """``z_rows`` of the z-loss form: fp32 [M], contiguous, on the logits' device."""
+    if not isinstance(z_rows, torch.Tensor):
+        raise TypeError(f"{name}: the z-loss form needs an fp32 [M] tensor for the rows' lse^2")
+    if z_rows.device != logits.device:
+        raise ValueError(f"{name}: expected a tensor on {logits.device}, got {z_rows.device}")
+    if z_rows.dtype != torch.float32:
+        raise TypeError(f"{name}: expected torch.float32, got {z_rows.dtype}")
+    if tuple(z_rows.shape) != (logits.shape[0],) or not z_rows.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous [{logits.shape[0]}] tensor, got {tuple(z_rows.shape)}")
+
+
+def cross_entropy_fwd_bwd(logits, targets, vocab, n_valid, grad_scale: float = 1.0, z_loss: float = 0.0,
+                          z_rows=None):
     """Per-row loss; the logits buffer (bf16 or fp16) is overwritten by
     grad_scale * (softmax - onehot) / n_valid (fp16: grad_scale = the loss scale, so the
-    gradient does not underflow)."""
+    gradient does not underflow).
+
+    The z-loss form (``z_loss`` != 0 or ``z_rows`` given; ``z_rows`` fp32 [M] is then required):
+    the gradient is that of ``(lse - logit[target]) + z_loss * lse^2``, i.e.
+    grad_scale * (softmax * (1 + 2 z_loss lse) - onehot) / n_valid; the returned rows stay the
+    cross-entropy part and ``z_rows`` receives lse^2 (0 on ignored rows).  Without either
+    argument the plain kernels run, as before the form existed."""
     if logits.dtype == torch.float32:
         from . import hip_f32
-        return hip_f32.cross_entropy_fwd_bwd(logits, targets, vocab, n_valid, grad_scale)
+        return hip_f32.cross_entropy_fwd_bwd(logits, targets, vocab, n_valid, grad_scale, z_loss, z_rows)
     M, Vp = logits.shape
     hk = _req_act(logits, logits.dtype, "ce.logits")
     targets = targets.contiguous()
@@ -1158,8 +1179,16 @@ def cross_entropy_fwd_bwd(logits, targets, vocab, n_valid, grad_scale: float = 1
         raise ValueError("ce.targets must be int64 [M]")
     nv = n_valid.reshape(1).to(torch.int64).contiguous()
     loss = torch.empty(M, dtype=torch.float32, device=logits.device)
-    _chk(lib().dlt_cross_entropy_fwd_bwd(_p(logits), _p(targets), _p(nv), _p(loss), M, Vp, vocab,
-                                         float(grad_scale), hk, _stream()), "cross_entropy")
+    if float(z_loss) == 0.0 and z_rows is None:
+        _chk(lib().dlt_cross_entropy_fwd_bwd(_p(logits), _p(targets), _p(nv), _p(loss), M, Vp, vocab,
+                                             float(grad_scale), hk, _stream()), "cross_entropy")
+        return loss
+    check_z_rows(z_rows, logits)
+    if Vp % 8 or vocab > Vp:
+        raise ValueError(f"ce.logits: the padded width {Vp} must be a multiple of 8 and hold the vocabulary {vocab}")
+    _chk(lib().dlt_cross_entropy_z_fwd_bwd(_p(logits), _p(targets), _p(nv), _p(loss), M, Vp, vocab,
+                                           float(grad_scale), hk, float(z_loss), _p(z_rows), _stream()),
+         "cross_entropy_z")
     return loss
 
 

@@ -28,6 +28,8 @@ SIGS = {
     "dlt_f32_swiglu_fwd": [c_void_p, c_void_p, c_int, c_int, c_void_p],
     "dlt_f32_swiglu_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
     "dlt_f32_cross_entropy": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p],
+    "dlt_f32_cross_entropy_z": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p,
+                                c_void_p],
     "dlt_f32_scale": [c_void_p, c_void_p, c_long, c_void_p, c_float, c_void_p],
     "dlt_f32_attn_fwd": [c_void_p, c_void_p, c_void_p, c_long, c_long, c_long, c_void_p, c_void_p, c_void_p, c_int,
                          c_int, c_int, c_int, c_float, c_float, c_void_p],
@@ -465,7 +467,9 @@ def swiglu_bwd(gu, da, out=None, s_out=None):
 
 
 # ------------------------------------------------------------ cross-entropy
-def cross_entropy_fwd_bwd(logits, targets, vocab, n_valid, grad_scale: float = 1.0):
+def cross_entropy_fwd_bwd(logits, targets, vocab, n_valid, grad_scale: float = 1.0, z_loss: float = 0.0,
+                          z_rows=None):
+    """fp32 logits; ``z_loss`` / ``z_rows``: the z-loss form, as ``hip.cross_entropy_fwd_bwd``."""
     M, Vp = logits.shape
     _req32(logits, "ce_f32.logits")
     targets = targets.contiguous()
@@ -473,8 +477,16 @@ def cross_entropy_fwd_bwd(logits, targets, vocab, n_valid, grad_scale: float = 1
         raise ValueError("ce.targets must be int64 [M]")
     nv = n_valid.reshape(1).to(torch.int64).contiguous()
     loss = torch.empty(M, dtype=torch.float32, device=logits.device)
-    _chk(_lib().dlt_f32_cross_entropy(_p(logits), _p(targets), _p(nv), _p(loss), M, Vp, vocab, float(grad_scale),
-                                      _st()), "f32_cross_entropy")
+    if float(z_loss) == 0.0 and z_rows is None:
+        _chk(_lib().dlt_f32_cross_entropy(_p(logits), _p(targets), _p(nv), _p(loss), M, Vp, vocab, float(grad_scale),
+                                          _st()), "f32_cross_entropy")
+        return loss
+    from .hip import check_z_rows
+    check_z_rows(z_rows, logits, "ce_f32.z_rows")
+    if vocab > Vp:
+        raise ValueError(f"ce_f32.logits: {Vp} columns cannot hold the vocabulary {vocab}")
+    _chk(_lib().dlt_f32_cross_entropy_z(_p(logits), _p(targets), _p(nv), _p(loss), M, Vp, vocab, float(grad_scale),
+                                        float(z_loss), _p(z_rows), _st()), "f32_cross_entropy_z")
     return loss
 
 

@@ -465,13 +465,29 @@ def swiglu_bwd(gu: torch.Tensor, da: torch.Tensor, out=None, s_out=None) -> torc
 
 # ------------------------------------------------------ cross-entropy (fused with grad)
 def cross_entropy_fwd_bwd(logits: torch.Tensor, targets: torch.Tensor, vocab: int,
-                          n_valid: torch.Tensor, grad_scale: float = 1.0) -> torch.Tensor:
+                          n_valid: torch.Tensor, grad_scale: float = 1.0, z_loss: float = 0.0,
+                          z_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Per-row loss [M] fp32; ``logits`` [M, Vp] is overwritten with
     grad_scale * dloss_mean/dlogits.
 
     Columns >= vocab are padding and get zero gradient.  Rows whose target is
     IGNORE_INDEX get zero loss and zero gradient.  ``n_valid`` is a 0-dim tensor.
+
+    The z-loss form (``z_loss`` != 0 or ``z_rows`` given, fp32 [M]): the row's objective is
+    ``(lse - logit[target]) + z_loss * lse^2``, so the softmax part of the gradient carries
+    the factor ``1 + 2 z_loss lse`` (possibly negative; used as it is).  The returned rows stay
+    the cross-entropy part and ``z_rows`` receives lse^2 (0 on ignored rows).
     """
+    zform = float(z_loss) != 0.0 or z_rows is not None
+    if zform:
+        if not isinstance(z_rows, torch.Tensor):
+            raise TypeError("ce.z_rows: the z-loss form needs an fp32 [M] tensor for the rows' lse^2")
+        if z_rows.device != logits.device:
+            raise ValueError(f"ce.z_rows: expected a tensor on {logits.device}, got {z_rows.device}")
+        if z_rows.dtype != torch.float32:
+            raise TypeError(f"ce.z_rows: expected torch.float32, got {z_rows.dtype}")
+        if tuple(z_rows.shape) != (logits.shape[0],):
+            raise ValueError(f"ce.z_rows: expected [{logits.shape[0]}], got {tuple(z_rows.shape)}")
     lf = logits[:, :vocab].float()
     lse = torch.logsumexp(lf, dim=-1)
     valid = targets != IGNORE_INDEX
@@ -479,6 +495,9 @@ def cross_entropy_fwd_bwd(logits: torch.Tensor, targets: torch.Tensor, vocab: in
     picked = lf.gather(1, tgt.unsqueeze(1)).squeeze(1)
     loss = torch.where(valid, lse - picked, torch.zeros_like(lse))
     grad = torch.exp(lf - lse.unsqueeze(1))
+    if zform:
+        grad = grad * (1.0 + 2.0 * float(z_loss) * lse).unsqueeze(1)
+        z_rows.copy_(torch.where(valid, lse * lse, torch.zeros_like(lse)))
     grad.scatter_add_(1, tgt.unsqueeze(1), -torch.ones_like(picked).unsqueeze(1))
     grad = grad * (valid.float() * grad_scale / n_valid.float().clamp(min=1)).unsqueeze(1)
     logits.zero_()

@@ -214,6 +214,41 @@ def add_doc_mask_args(p) -> None:
                         "--eval_batches evaluation both use it (default: plain causal attention)")
 
 
+class LossParts:
+    """The (cross-entropy, weighted z term) parts of an optimizer step's loss, summed on the
+    device as the trainers' ``total`` is (no host sync per micro-step).  Inactive without a
+    z-loss coefficient: the metrics and the log line are then what they always were."""
+
+    def __init__(self, coef: float, device):
+        self.sum = torch.zeros(2, dtype=torch.float32, device=device) if coef > 0.0 else None
+
+    def add(self, pair, chains: int) -> None:
+        """``pair``: ``last_loss_parts`` of one micro-step chain; ``chains`` per optimizer step."""
+        if self.sum is not None:
+            self.sum += torch.stack([pair[0].detach().float(), pair[1].detach().float()]) / chains
+
+    def into(self, out: dict, sync: bool) -> None:
+        """``ce_loss`` / ``z_loss`` next to ``loss``: floats when ``sync`` (one copy), else tensors."""
+        if self.sum is not None:
+            out["ce_loss"], out["z_loss"] = self.sum.tolist() if sync else (self.sum[0], self.sum[1])
+
+
+def z_loss_suffix(metrics: dict) -> str:
+    """`` | Z loss: ...`` for the step line of a run with a z-loss coefficient, else nothing."""
+    return f" | Z loss: {float(metrics['z_loss']):.6f}" if "z_loss" in metrics else ""
+
+
+def z_loss_record(metrics: dict) -> dict:
+    """The JSONL record's ``ce_loss`` / ``z_loss`` of a run with a z-loss coefficient, else nothing."""
+    return {k: float(metrics[k]) for k in ("ce_loss", "z_loss") if k in metrics}
+
+
+def add_z_loss_args(p) -> None:
+    p.add_argument("--z_loss", type=float, default=None, metavar="COEF",
+                   help="auxiliary z-loss: the training loss is ce + COEF * mean(logsumexp(logits)^2) (PaLM: 1e-4); "
+                        "validation loss stays plain cross-entropy (default 0: off)")
+
+
 def add_model_args(p) -> None:
     p.add_argument("--num_kv_heads", type=int, default=None, metavar="N",
                    help="grouped-query attention: N key/value heads shared by groups of num_heads / N query "

@@ -73,6 +73,13 @@ class TrainingConfig:
     # (GPT-2: 50256) and a token attends only within its own document; None = plain causal
     # (--doc_sep_token; GPT.set_doc_separator).  Training and evaluation use the same value.
     doc_sep_token: Optional[int] = None
+    # auxiliary z-loss coefficient: the training loss is ce + z_loss * mean(logsumexp(logits)^2)
+    # (PaLM: 1e-4); 0 = off.  Evaluation reports plain cross-entropy.  (--z_loss; GPT.set_z_loss)
+    z_loss: float = 0.0
+
+    def __post_init__(self):
+        from ..models.engine import check_z_loss
+        check_z_loss(self.z_loss)
 
 
 @dataclass
@@ -102,6 +109,11 @@ class FSDPTrainingConfig:
     micro_step_fusion: int = 0
     eval_batches: int = 0              # held-out batches per rank and evaluation, 0 = off (as TrainingConfig)
     doc_sep_token: Optional[int] = None  # document separator id for intra-document masking (as TrainingConfig)
+    z_loss: float = 0.0                # auxiliary z-loss coefficient, 0 = off (as TrainingConfig)
+
+    def __post_init__(self):
+        from ..models.engine import check_z_loss
+        check_z_loss(self.z_loss)
 
 
 @dataclass

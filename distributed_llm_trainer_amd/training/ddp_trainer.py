@@ -40,7 +40,7 @@ from ..parallel.flat import FlatParamStore
 from ..utils import checkpoint as ckpt
 from ..utils import debug as dbg
 from ..utils.profiling import Profiler, range_push, range_pop
-from .common import EVAL_SEED_OFFSET, HeldOutBatches, add_doc_mask_args, add_eval_args, add_model_args, apply_model_args, cosine_lr, evaluate_held_out, gemm_plan_hook, global_mean_loss, held_out_of, log_evaluation, memory_stats, micro_step_fusion, seed_all, select_device, setup_distributed, unwrap_batch
+from .common import EVAL_SEED_OFFSET, HeldOutBatches, LossParts, add_doc_mask_args, add_eval_args, add_z_loss_args, z_loss_record, z_loss_suffix, add_model_args, apply_model_args, cosine_lr, evaluate_held_out, gemm_plan_hook, global_mean_loss, held_out_of, log_evaluation, memory_stats, micro_step_fusion, seed_all, select_device, setup_distributed, unwrap_batch
 from .configs import TrainingConfig
 from .optim import flat_store_optimizer
 
@@ -113,6 +113,7 @@ class DistributedTrainer:
             print(f"Model parameters: {count_parameters(self.model):,}")
         # before the engine exists, so a route without the mask is refused when it is enabled
         self.model.set_doc_separator(getattr(self.training_config, "doc_sep_token", None))
+        self.model.set_z_loss(getattr(self.training_config, "z_loss", 0.0))
         if self.use_engine:
             act = self.dtype if self.device.type == "cuda" else None
             eng = self.model.enable_engine(seed=self.training_config.seed + 1000003 * self.rank, act_dtype=act)
@@ -182,6 +183,7 @@ class DistributedTrainer:
             # fp16 underflow); the engine divides it out where dloss is applied
             self.model.engine.ce_grad_scale = float(self.loss_scale or 1.0)
         total = torch.zeros((), dtype=torch.float32, device=self.device)
+        parts = LossParts(self.model.z_loss, self.device)
         # micro-step pipelining (engine.train_window): from the second step on, so the
         # first one runs the GEMM autotuning on a quiet GPU
         window_ok = (self.use_engine and chains > 1 and cfg.pipeline_micro_steps
@@ -213,6 +215,8 @@ class DistributedTrainer:
             range_pop()
             for loss in losses:
                 total += (loss / chains).detach().float()
+            for pair in self.model.engine.window_loss_parts:
+                parts.add(pair, chains)
         for micro in range(0 if not pipelined else chains, chains):
             ids = input_ids[micro * chain_bs:(micro + 1) * chain_bs]
             if self.ddp is not None:
@@ -229,6 +233,7 @@ class DistributedTrainer:
                 loss.backward()
             range_pop()
             total += loss.detach().float()
+            parts.add(self.model.last_loss_parts, chains)
         if self.use_engine:
             self.model.engine.set_loss_segments(1)
         self._engine_warm = self.use_engine
@@ -276,6 +281,7 @@ class DistributedTrainer:
         if self.use_engine and self.global_step >= 2:
             gemm_plan_hook()
         out = {"loss": total.item() if sync_loss else total, "lr": lr, "tokens": self.tokens_seen}
+        parts.into(out, sync_loss)
         if sync_loss and self.distributed and self.world_size > 1:
             out["loss_global"] = global_mean_loss(total, self.world_size)
         return out
@@ -402,6 +408,7 @@ def build_parser() -> argparse.ArgumentParser:
                         "chunks): ~56 %% of the default peak memory at -3 %% tok/s")
     add_eval_args(p)
     add_doc_mask_args(p)
+    add_z_loss_args(p)
     add_model_args(p)
     return p
 
@@ -456,7 +463,7 @@ def main(argv=None):
         tc.defer_roles = LEAN_DEFER_ROLES
     if args.memory_first:
         tc.memory_first = True
-    for k in ("eval_interval", "eval_batches", "doc_sep_token"):
+    for k in ("eval_interval", "eval_batches", "doc_sep_token", "z_loss"):
         if getattr(args, k) is not None:
             setattr(tc, k, getattr(args, k))
     if tc.eval_batches > 0:
@@ -515,11 +522,11 @@ def main(argv=None):
         if do_log and trainer.is_main_process:
             elapsed = time.time() - start_time
             tps = (metrics["tokens"] - tokens0) / max(elapsed, 1e-9)
-            print(f"Step {step:6d} | Loss: {metrics['loss']:.4f} | LR: {metrics['lr']:.2e} | Tokens/sec: {tps:,.0f}",
-                  flush=True)
+            print(f"Step {step:6d} | Loss: {metrics['loss']:.4f} | LR: {metrics['lr']:.2e} | Tokens/sec: {tps:,.0f}"
+                  f"{z_loss_suffix(metrics)}", flush=True)
             if metrics_f:
                 rec = {"step": step, "loss": metrics["loss"], "lr": metrics["lr"], "tokens": metrics["tokens"],
-                       "elapsed_s": elapsed,
+                       **z_loss_record(metrics), "elapsed_s": elapsed,
                        **({"loss_global": metrics["loss_global"]} if "loss_global" in metrics else {}),
                        "tokens_per_sec": tps, **trainer.get_memory_stats()}
                 if trainer._last_norm is not None:

@@ -33,7 +33,7 @@ from ..parallel.fsdp import FSDPRuntime
 from ..utils import checkpoint as ckpt
 from ..utils import debug as dbg
 from ..utils.profiling import Profiler
-from .common import (EVAL_SEED_OFFSET, HeldOutBatches, add_doc_mask_args, add_eval_args, add_model_args, apply_model_args, cosine_lr, evaluate_held_out, gemm_plan_hook,
+from .common import (EVAL_SEED_OFFSET, HeldOutBatches, LossParts, add_doc_mask_args, add_eval_args, add_z_loss_args, z_loss_record, z_loss_suffix, add_model_args, apply_model_args, cosine_lr, evaluate_held_out, gemm_plan_hook,
                      global_mean_loss, held_out_of, log_evaluation, memory_stats, micro_step_fusion, seed_all, select_device, setup_distributed, unwrap_batch)
 from .configs import FSDPConfig, FSDPTrainingConfig
 from .optim import FlatAdamW
@@ -94,6 +94,7 @@ class FSDPTrainer:
         self.model.gradient_checkpointing = bool(fc.activation_checkpointing)
         # before the engine exists, so a route without the mask is refused when it is enabled
         self.model.set_doc_separator(getattr(tc, "doc_sep_token", None))
+        self.model.set_z_loss(getattr(tc, "z_loss", 0.0))
         self.model.enable_engine(provider=self.runtime, act_dtype=self.compute_dtype,
                                  seed=tc.seed + 1000003 * self.rank)
         if self.is_main_process:
@@ -142,6 +143,7 @@ class FSDPTrainer:
         F = self.fusion_factor(GA, micro_bs, input_ids.shape[1])
         chains, chain_bs = GA // F, micro_bs * F
         total = torch.zeros((), dtype=torch.float32, device=self.device)
+        parts = LossParts(self.model.z_loss, self.device)
         rt.zero_grad()
         defer = not self.fsdp_config.sync_every_micro_step
         eng = self.model.engine
@@ -167,6 +169,8 @@ class FSDPTrainer:
                                       sync_hook=rt.require_sync)
             for loss in losses:
                 total += (loss / chains).detach().float()
+            for pair in eng.window_loss_parts:
+                parts.add(pair, chains)
         for micro in range(chains if pipelined else 0, chains):
             ids = input_ids[micro * chain_bs:(micro + 1) * chain_bs]
             rt.require_sync(micro == chains - 1)
@@ -175,6 +179,7 @@ class FSDPTrainer:
             loss = loss / chains
             (loss * ls).backward() if self.loss_scale else loss.backward()
             total += loss.detach().float()
+            parts.add(self.model.last_loss_parts, chains)
         eng.set_loss_segments(1)
         self._engine_warm = True
         rt.finish()
@@ -212,6 +217,7 @@ class FSDPTrainer:
         if self.global_step >= 2:
             gemm_plan_hook()
         out = {"loss": total.item() if sync_loss else total, "lr": lr, "tokens": self.tokens_seen}
+        parts.into(out, sync_loss)
         if sync_loss and self.distributed and self.world_size > 1:
             out["loss_global"] = global_mean_loss(total, self.world_size)
         return out
@@ -425,6 +431,7 @@ def build_parser():
                         "directory, no gather (resume with --resume_from DIR)")
     add_eval_args(p)  # (--eval_data_path: this trainer reads the dummy stream only)
     add_doc_mask_args(p)
+    add_z_loss_args(p)
     add_model_args(p)
     return p
 
@@ -462,7 +469,7 @@ def main(argv=None):
     if args.seq_len:
         model_config.max_seq_len = args.seq_len
     apply_model_args(args, model_config)
-    for k in ("eval_interval", "eval_batches", "doc_sep_token"):
+    for k in ("eval_interval", "eval_batches", "doc_sep_token", "z_loss"):
         if getattr(args, k) is not None:
             setattr(tc, k, getattr(args, k))
     if tc.eval_batches > 0 and tc.eval_interval <= 0:
@@ -522,10 +529,10 @@ def main(argv=None):
             tps = (metrics["tokens"] - tokens0) / max(elapsed, 1e-9)
             mem = trainer.get_memory_stats()
             print(f"Step {step:6d} | Loss: {metrics['loss']:.4f} | LR: {metrics['lr']:.2e} | "
-                  f"Tokens/s: {tps:,.0f} | Mem: {mem['allocated_gb']:.1f}GB", flush=True)
+                  f"Tokens/s: {tps:,.0f} | Mem: {mem['allocated_gb']:.1f}GB{z_loss_suffix(metrics)}", flush=True)
             if metrics_f:
                 rec = {"step": step, "loss": metrics["loss"], "lr": metrics["lr"], "tokens": metrics["tokens"],
-                       "elapsed_s": elapsed,
+                       **z_loss_record(metrics), "elapsed_s": elapsed,
                        **({"loss_global": metrics["loss_global"]} if "loss_global" in metrics else {}),
                        "tokens_per_sec": tps, **mem}
                 if trainer._last_norm is not None:

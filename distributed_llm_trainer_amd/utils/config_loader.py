@@ -18,7 +18,7 @@ _TRAIN_MAP = {"batch_size": "batch_size", "gradient_accumulation_steps": "gradie
               "learning_rate": "learning_rate", "weight_decay": "weight_decay", "beta1": "beta1", "beta2": "beta2",
               "grad_clip": "grad_clip", "max_steps": "max_steps", "warmup_steps": "warmup_steps",
               "log_interval": "log_interval", "eval_interval": "eval_interval", "save_interval": "save_interval",
-              "eval_batches": "eval_batches"}
+              "eval_batches": "eval_batches", "z_loss": "z_loss"}
 
 
 def explicit_args(parser: argparse.ArgumentParser, argv: Optional[Sequence[str]]) -> set:
