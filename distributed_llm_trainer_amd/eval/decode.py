@@ -5,7 +5,8 @@ whole context for every new token (O(T^2) work).  Here the pro
 prefilled once, per-layer K/V (already RoPE-rotated) are cached in preallocated
 ``[B, nh, max_seq_len, hd]`` buffers, and each new token costs one token's worth of
 GEMV + attention.  Sampling semantics are the reference's: temperature, top-k
-filtering (``logits < kth`` -> -inf), softmax, ``torch.multinomial``; contexts longer
+filtering (``logits < kth`` -> -inf), softmax, ``torch.multinomial`` -- and, off by default,
+nucleus (top-p) and min-p filtering on top of top-k (:func:`filter_logits`); contexts longer
 than ``max_seq_len`` are cropped to the last ``max_seq_len`` tokens (the cache is then
 re-prefilled on the cropped window so RoPE positions match the reference exactly).
 
@@ -29,6 +30,8 @@ from typing import Optional
 
 import torch
 import torch.nn.functional as F
+
+from ..ops.hip import check_top_p_min_p
 
 
 class KVCache:
@@ -175,7 +178,8 @@ class DecodeGraph:
     """
 
     def __init__(self, model, cache: KVCache, pos: int, sample: Optional[dict] = None):
-        """``sample`` (fused step only): dict(temperature, top_k, seed, hist, hist_base) --
+        """``sample`` (fused step only): dict(temperature, top_k, seed, hist, hist_base and
+        optionally top_p, min_p) --
         the graph then also draws the next token (ops ``dec_sample``) into ``self.ids`` and
         ``hist`` and advances the device position, so generation is one replay per token
         with no host round trip."""
@@ -251,7 +255,7 @@ class DecodeGraph:
         if self.sample is not None:
             sm = self.sample
             ops.dec_sample(self.lg, sm["temperature"], sm["top_k"], sm["seed"], self.pos, self.ids, sm["hist"],
-                           sm["hist_base"], ws=self.sample_ws)
+                           sm["hist_base"], ws=self.sample_ws, top_p=sm.get("top_p", 1.0), min_p=sm.get("min_p", 0.0))
             ops.dec_advance(self.pos)
         return self.lg
 
@@ -385,12 +389,44 @@ def _reset(cache: KVCache) -> KVCache:
     return cache
 
 
+def filter_logits(lg: torch.Tensor, top_k: int, top_p: float = 1.0, min_p: float = 0.0) -> torch.Tensor:
+    """The sampling filters on ``lg`` = logits / temperature [B, V]: what is not kept is -inf.
+    Each filter keeps the values >= a threshold of its own, so equal values stand or fall
+    together, and the kept set is the intersection (the device sampler, ``dec_sample``, applies
+    the same definition):
+
+    * top-k (``top_k`` > 0): the values >= the k-th largest;
+    * top-p (``top_p`` < 1), on q = softmax over what top-k left: a value is kept iff the
+      q-mass of the values strictly above it is < top_p (the value that crosses top_p is kept,
+      the largest always is; the sums are taken in fp64);
+    * min-p (``min_p`` > 0): exp(v - max) >= min_p, i.e. p >= min_p * p_max.
+
+    With the defaults this is the top-k code ``generate`` always ran."""
+    top_p, min_p = check_top_p_min_p(top_p, min_p)
+    x = lg
+    if top_k > 0:
+        v, _ = torch.topk(lg, min(top_k, lg.size(-1)))
+        lg = lg.masked_fill(lg < v[:, [-1]], float("-inf"))
+    if top_p < 1.0:
+        s, _ = torch.sort(lg, dim=-1, descending=True)
+        q = F.softmax(s.double(), dim=-1)
+        above = q.cumsum(dim=-1) - q  # exclusive: of equal values the first has the mass strictly above
+        thr = s.masked_fill(above >= top_p, float("inf")).amin(dim=-1, keepdim=True)
+        lg = lg.masked_fill(lg < thr, float("-inf"))
+    if min_p > 0.0:
+        thr = x.amax(dim=-1, keepdim=True) + math.log(min_p)
+        lg = lg.masked_fill(x < thr, float("-inf"))
+    return lg
+
+
 @torch.no_grad()
 def kv_cached_generate(model, input_ids: torch.Tensor, max_new_tokens: int = 100, temperature: float = 1.0,
-                       top_k: int = 50) -> torch.Tensor:
-    """KV-cached top-k sampling (``GPT.generate`` on the engine path).  The document mask
+                       top_k: int = 50, top_p: float = 1.0, min_p: float = 0.0) -> torch.Tensor:
+    """KV-cached sampling (``GPT.generate`` on the engine path): temperature, then the top-k,
+    top-p and min-p filters of :func:`filter_logits`.  The document mask
     of ``GPT.set_doc_separator`` is not applied here: generation continues one document,
     so the prompt and every cached key are taken to belong to it."""
+    top_p, min_p = check_top_p_min_p(top_p, min_p)
     cfg = model.config
     eng = model.engine
     B = input_ids.shape[0]
@@ -403,16 +439,13 @@ def kv_cached_generate(model, input_ids: torch.Tensor, max_new_tokens: int = 100
             and _fused_kind(model, B) is not None and os.environ.get("DLT_DECODE_DEVICE_LOOP", "1") != "0"):
         # first token from the prefill logits (ATen sampling), then one graph replay per
         # token: the fused step samples on the device and feeds itself (no host round trip)
-        lg = logits / temperature
-        if top_k > 0:
-            v, _ = torch.topk(lg, min(top_k, lg.size(-1)))
-            lg = lg.masked_fill(lg < v[:, [-1]], float("-inf"))
+        lg = filter_logits(logits / temperature, top_k, top_p, min_p)
         nxt = torch.multinomial(F.softmax(lg, dim=-1), num_samples=1)
         hist = torch.empty(B, n_dev, dtype=torch.long, device=input_ids.device)
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())  # torch's generator: manual_seed reproducible
         graph = DecodeGraph(model, cache, cache.len,
                             sample=dict(temperature=float(temperature), top_k=int(top_k), seed=seed, hist=hist,
-                                        hist_base=cache.len + 1))
+                                        hist_base=cache.len + 1, top_p=top_p, min_p=min_p))
         graph.ids.copy_(nxt)
         for _ in range(n_dev):
             graph.graph.replay()
@@ -426,10 +459,7 @@ def kv_cached_generate(model, input_ids: torch.Tensor, max_new_tokens: int = 100
     graph = DecodeGraph(model, cache, cache.len) if (_graph_ok(model, input_ids.device)
                                                     and cache.len < cfg.max_seq_len and max_new_tokens > 1) else None
     for step in range(max_new_tokens):
-        lg = logits / temperature
-        if top_k > 0:
-            v, _ = torch.topk(lg, min(top_k, lg.size(-1)))
-            lg = lg.masked_fill(lg < v[:, [-1]], float("-inf"))
+        lg = filter_logits(logits / temperature, top_k, top_p, min_p)
         probs = F.softmax(lg, dim=-1)
         nxt = torch.multinomial(probs, num_samples=1)
         out = torch.cat([out, nxt], dim=1)

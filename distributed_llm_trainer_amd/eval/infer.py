@@ -63,6 +63,10 @@ def main(argv=None):
     p.add_argument("--device", default="auto")
     p.add_argument("--temperature", type=float, default=1.0)
     p.add_argument("--top_k", type=int, default=50)
+    p.add_argument("--top_p", type=float, default=1.0,
+                   help="nucleus sampling: keep the smallest set of top tokens whose probability reaches top_p (1: off)")
+    p.add_argument("--min_p", type=float, default=0.0,
+                   help="keep the tokens with probability >= min_p * the top token's (0: off)")
     p.add_argument("--tokenizer", default="gpt2")
     p.add_argument("--seed", type=int, default=None)
     p.add_argument("--num_kv_heads", type=int, default=None, metavar="N",
@@ -83,7 +87,8 @@ def main(argv=None):
                        args.sliding_window_pattern, args.attention_sinks)
     tok = get_tokenizer(args.tokenizer)
     ids = torch.tensor([tok.encode(args.prompt)], dtype=torch.long, device=dev)
-    out = model.generate(ids, max_new_tokens=args.max_new_tokens, temperature=args.temperature, top_k=args.top_k)
+    out = model.generate(ids, max_new_tokens=args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
+                         top_p=args.top_p, min_p=args.min_p)
     text = tok.decode(out[0].tolist())
     print(text)
     return text

@@ -386,8 +386,11 @@ class GPT(nn.Module):
     # ------------------------------------------------------------ generation
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, max_new_tokens: int = 100,
-                 temperature: float = 1.0, top_k: int = 50) -> torch.Tensor:
-        """Top-k sampling with the reference's semantics (``gpt.py:457-484``).
+                 temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0,
+                 min_p: float = 0.0) -> torch.Tensor:
+        """Top-k sampling with the reference's semantics (``gpt.py:457-484``), and on top of
+        it nucleus (``top_p`` < 1) and min-p (``min_p`` > 0) filtering as
+        ``eval.decode.filter_logits`` defines them; both are off by default.
 
         With the engine enabled this uses the KV-cached decoder in
         ``eval/decode.py`` (one token per step instead of a full re-forward).  The
@@ -397,16 +400,13 @@ class GPT(nn.Module):
         flush = getattr(getattr(self.engine, "provider", None), "flush_pending", None)
         if flush is not None:  # a recorded (lazy) optimizer step: the decoder reads every unit
             flush()
+        from ..eval.decode import filter_logits, kv_cached_generate
         if self.engine is not None:
-            from ..eval.decode import kv_cached_generate
-            return kv_cached_generate(self, input_ids, max_new_tokens, temperature, top_k)
+            return kv_cached_generate(self, input_ids, max_new_tokens, temperature, top_k, top_p, min_p)
         for _ in range(max_new_tokens):
             idx = input_ids if input_ids.size(1) <= self.config.max_seq_len else input_ids[:, -self.config.max_seq_len:]
             logits, _ = self(idx)
-            logits = logits[:, -1, :] / temperature
-            if top_k > 0:
-                v, _ = torch.topk(logits, min(top_k, logits.size(-1)))
-                logits[logits < v[:, [-1]]] = float("-inf")
+            logits = filter_logits(logits[:, -1, :] / temperature, top_k, top_p, min_p)
             probs = F.softmax(logits, dim=-1)
             nxt = torch.multinomial(probs, num_samples=1)
             input_ids = torch.cat([input_ids, nxt], dim=1)

@@ -754,9 +754,125 @@ __device__ uint32_t kth_key(KeyAt key_at, int C, int k, uint32_t* hist, float* s
   return prefix;
 }
 
+// ---- nucleus (top-p): the mass-select next to kth_key.
+// A value's mass is floor(__expf(x - max) * 2^40) as a 64-bit integer (exp <= 1, so a row of
+// V < 2^24 values sums below 2^64).  Integer sums are associative: Z, T and every histogram
+// bin are exact functions of the row, whatever order the LDS atomics arrive in -- float
+// masses would make the threshold (and the sampled id) vary from run to run.
+constexpr float SMP_MASS_ONE = 1099511627776.f;  // 2^40
+
+__device__ __forceinline__ unsigned long long mass_of(uint32_t key, float mx) {
+  const float e = __expf(key2f(key) - mx);
+  return e > 0.f ? (unsigned long long)(e * SMP_MASS_ONE) : 0ull;  // NaN (a row without a finite value): 0
+}
+
+// exclusive prefix sum over the block of a 64-bit integer; ms: 16 words of LDS
+__device__ __forceinline__ unsigned long long block_excl_scan_u64(unsigned long long v, unsigned long long* ms,
+                                                                  unsigned long long* tot) {
+  constexpr int NW = SMP_NT / 64;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  unsigned long long incl = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t lo = __shfl_up((uint32_t)incl, o, 64), hi = __shfl_up((uint32_t)(incl >> 32), o, 64);
+    if (lane >= o) incl += ((unsigned long long)hi << 32) | lo;
+  }
+  if (lane == 63) ms[wid] = incl;
+  __syncthreads();
+  if (tid == 0) {
+    unsigned long long a = 0;
+    for (int w = 0; w < NW; ++w) {
+      a += ms[w];
+      ms[8 + w] = a;
+    }
+  }
+  __syncthreads();
+  const unsigned long long base = wid ? ms[8 + wid - 1] : 0ull;
+  *tot = ms[8 + NW - 1];
+  __syncthreads();
+  return base + incl - v;
+}
+
+// The key of the smallest value the nucleus keeps among the keys >= lo (the top-k threshold):
+// with Z the mass of those keys and T = top_p * Z, a value is kept iff the mass of the keys
+// strictly above it is < T -- the value that crosses T is kept, the largest always is, equal
+// values stand or fall together.  Radix descent over kth_key's bit fields with bins walked in
+// descending order: the bin with mass_above < T <= mass_above + mass(bin) holds the answer,
+// and the next pass looks inside it for T - mass_above.  T is the integer ceil(top_p * Z)
+// (A < t <=> A < ceil(t) for an integer A), formed once in fp64.
+// hist: 4096 64-bit bins, ms: 17 64-bit words, sel: 1 int.
+template <typename KeyAt>
+__device__ uint32_t mass_key(KeyAt key_at, int C, uint32_t lo, float top_p, float mx, unsigned long long* hist,
+                             unsigned long long* ms, int* sel) {
+  const int tid = threadIdx.x;
+  uint32_t prefix = 0, pmask = 0;
+  unsigned long long T = 0;
+  const int shifts[3] = {20, 8, 0}, widths[3] = {12, 12, 8};
+#pragma unroll
+  for (int ps = 0; ps < 3; ++ps) {
+    const int sh = shifts[ps], nb = 1 << widths[ps];
+    for (int i = tid; i < nb; i += SMP_NT) hist[i] = 0;
+    if (tid == 0) {
+      sel[0] = 0;
+      ms[16] = 0;
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int j = 0; j < C; ++j) {
+      const uint32_t kj = key_at(j);
+      if (kj >= lo && (kj & pmask) == prefix) {
+        const unsigned long long m = mass_of(kj, mx);
+        if (m) atomicAdd(&hist[(kj >> sh) & (nb - 1)], m);
+      }
+    }
+    __syncthreads();
+    // masses in descending-bin order: thread t owns reversed bins [8t, 8t + 8)
+    unsigned long long c[8], own = 0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int r = 8 * tid + q;
+      c[q] = r < nb ? hist[nb - 1 - r] : 0ull;
+      own += c[q];
+    }
+    unsigned long long total;
+    unsigned long long before = block_excl_scan_u64(own, ms, &total);  // mass in higher bins than this thread's
+    if (ps == 0) {
+      T = (unsigned long long)ceil((double)top_p * (double)total);
+      T = T < 1 ? 1 : (T > total ? total : T);
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int r = 8 * tid + q;
+      if (r < nb && before < T && T <= before + c[q]) {
+        sel[0] = nb - 1 - r;
+        ms[16] = T - before;
+      }
+      before += c[q];
+    }
+    __syncthreads();
+    prefix |= (uint32_t)sel[0] << sh;
+    pmask |= (uint32_t)(nb - 1) << sh;
+    T = ms[16];
+    __syncthreads();
+  }
+  return prefix;
+}
+
+// The filters beyond top-k (NUC instantiations only), each "value >= a threshold" like top-k:
+// they only raise thr.  min-p keeps exp(v - max) >= min_p, i.e. v >= max + log(min_p).
+template <typename KeyAt>
+__device__ __forceinline__ uint32_t nucleus_thr(KeyAt key_at, int C, uint32_t thr, float top_p, float min_p, float mx,
+                                                unsigned long long* mbins, unsigned long long* ms, int* sel) {
+  if (top_p < 1.f) thr = max(thr, mass_key(key_at, C, thr, top_p, mx, mbins, ms, sel));
+  if (min_p > 0.f) thr = max(thr, f2key(mx + logf(min_p)));
+  return thr;
+}
+
+template <bool NUC>
 __device__ void sample_row(const float* __restrict__ logits, int V, float temperature, int top_k, uint32_t seed,
                            const long* __restrict__ posp, long* __restrict__ ids, long* __restrict__ hist,
-                           int hist_len, int hist_base, int b, uint32_t* bins, float* scr, int* sel) {
+                           int hist_len, int hist_base, int b, uint32_t* bins, float* scr, int* sel,
+                           float top_p = 1.f, float min_p = 0.f, unsigned long long* ms = nullptr) {
   const int tid = threadIdx.x;
   // Thread t owns the elements i = t + SMP_NT * j (coalesced loads).  The draw inverts the
   // cumulative sum in (thread, j) order -- any fixed order of the elements samples the
@@ -826,6 +942,9 @@ __device__ void sample_row(const float* __restrict__ logits, int V, float temper
       thr = max(thr, kth_key(key_at, C, top_k, bins, scr, sel));
     }
   }
+  // NUC: bins is the 64-bit histogram's LDS (the top-k select is done with it)
+  if constexpr (NUC)
+    thr = nucleus_thr(key_at, C, thr, top_p, min_p, mx, reinterpret_cast<unsigned long long*>(bins), ms, sel);
   float own = 0.f;
 #pragma unroll 4
   for (int j = 0; j < C; ++j) {
@@ -867,14 +986,24 @@ __device__ void sample_row(const float* __restrict__ logits, int V, float temper
   }
 }
 
+// NUC: the top-p / min-p forms; the plain sampler (NUC = false) is the code it always was.
+template <bool NUC>
 __global__ __launch_bounds__(SMP_NT) void k_dec_sample(const float* __restrict__ logits, int V, float temperature,
                                                        int top_k, uint32_t seed, const long* __restrict__ posp,
                                                        long* __restrict__ ids, long* __restrict__ hist, int hist_len,
-                                                       int hist_base) {
-  __shared__ uint32_t bins[4096];
+                                                       int hist_base, float top_p, float min_p) {
   __shared__ float scr[40];
   __shared__ int sel[2];
-  sample_row(logits, V, temperature, top_k, seed, posp, ids, hist, hist_len, hist_base, blockIdx.x, bins, scr, sel);
+  if constexpr (NUC) {
+    __shared__ unsigned long long mbins[4096];  // top-k's 32-bit bins, then the 64-bit mass bins
+    __shared__ unsigned long long ms[17];
+    sample_row<true>(logits, V, temperature, top_k, seed, posp, ids, hist, hist_len, hist_base, blockIdx.x,
+                     reinterpret_cast<uint32_t*>(mbins), scr, sel, top_p, min_p, ms);
+  } else {
+    __shared__ uint32_t bins[4096];
+    sample_row<false>(logits, V, temperature, top_k, seed, posp, ids, hist, hist_len, hist_base, blockIdx.x, bins, scr,
+                      sel);
+  }
 }
 
 // Split sampler for 1 <= top_k <= 64: SMP_NS workgroups per row each take a slice of the
@@ -948,13 +1077,17 @@ __global__ __launch_bounds__(SMP_NT) void k_dec_topk_slices(const float* __restr
   if (tid == 0) cnt[sl] = (int)tot <= SMP_MAXC ? (int)tot : -1;  // -1: overflow
 }
 
+template <bool NUC>
 __global__ __launch_bounds__(SMP_NT) void k_dec_topk_draw(const int* __restrict__ ws, const float* __restrict__ logits,
                                                           int V, float temperature, int top_k, uint32_t seed,
                                                           const long* __restrict__ posp, long* __restrict__ ids,
-                                                          long* __restrict__ hist, int hist_len, int hist_base) {
+                                                          long* __restrict__ hist, int hist_len, int hist_base,
+                                                          float top_p, float min_p) {
   __shared__ uint32_t ckey[SMP_NS * SMP_MAXC];
   __shared__ int cidx[SMP_NS * SMP_MAXC];
-  __shared__ uint32_t bins[4096];
+  // NUC: 64-bit mass bins, used as top-k's 32-bit bins first (as in k_dec_sample)
+  __shared__ __attribute__((aligned(8))) uint32_t bins[NUC ? 8192 : 4096];
+  __shared__ unsigned long long ms[NUC ? 17 : 1];
   __shared__ float scr[40];
   __shared__ int sel[2];
   const int tid = threadIdx.x, b = blockIdx.x;
@@ -969,7 +1102,8 @@ __global__ __launch_bounds__(SMP_NT) void k_dec_topk_draw(const int* __restrict_
     kmax = max(kmax, (uint32_t)maxk[sl]);
   }
   if (overflow) {  // (uniform) a slice had more than SMP_MAXC elements tied at its threshold
-    sample_row(logits, V, temperature, top_k, seed, posp, ids, hist, hist_len, hist_base, b, bins, scr, sel);
+    sample_row<NUC>(logits, V, temperature, top_k, seed, posp, ids, hist, hist_len, hist_base, b, bins, scr, sel,
+                    top_p, min_p, ms);
     return;
   }
   for (int i = tid; i < SMP_NS * SMP_MAXC; i += SMP_NT) {
@@ -982,8 +1116,11 @@ __global__ __launch_bounds__(SMP_NT) void k_dec_topk_draw(const int* __restrict_
   constexpr int PT = SMP_NS * SMP_MAXC / SMP_NT;  // candidates per thread: tid + SMP_NT * j
   auto key_at = [&](int j) { return ckey[tid + SMP_NT * j]; };
   // as in sample_row: never keep -inf (fewer than top_k finite logits) or the 0 padding
-  const uint32_t thr = max(f2key(-INFINITY) + 1, kth_key(key_at, PT, top_k, bins, scr, sel));
+  uint32_t thr = max(f2key(-INFINITY) + 1, kth_key(key_at, PT, top_k, bins, scr, sel));
   const float mx = key2f(kmax);
+  // the candidates hold every value >= the top-k threshold: the nucleus over them is the row's
+  if constexpr (NUC)
+    thr = nucleus_thr(key_at, PT, thr, top_p, min_p, mx, reinterpret_cast<unsigned long long*>(bins), ms, sel);
   float own = 0.f;
 #pragma unroll
   for (int j = 0; j < PT; ++j) {
@@ -1187,17 +1324,38 @@ DLT_API int dlt_dec_norm_head(const float* h, const void* lnw, int wbf16, float 
 // ids [B] (int64, the next step's input), hist [B, hist_len]: hist[b][pos + 1 - hist_base] = sampled id
 // ws: int32 workspace of B * 16 * 258 (dlt_dec_sample_ws_ints); nullptr -> one workgroup per row
 DLT_API int dlt_dec_sample_ws_ints(int B) { return B * SMP_NS * (2 + 2 * SMP_MAXC); }
+template <bool NUC>
+static void dec_sample_launch(const float* logits, int B, int V, float temperature, int top_k, uint32_t seed,
+                              const long* pos, long* ids, long* hist, int hist_len, int hist_base, int* ws,
+                              float top_p, float min_p, hipStream_t st) {
+  if (ws && top_k >= 1 && top_k <= 64 && V <= SMP_NS * SMP_SLICE && top_k < V) {
+    k_dec_topk_slices<<<dim3(SMP_NS, B), SMP_NT, 0, st>>>(logits, V, temperature, top_k, ws);
+    k_dec_topk_draw<NUC><<<B, SMP_NT, 0, st>>>(ws, logits, V, temperature, top_k, seed, pos, ids, hist, hist_len,
+                                               hist_base, top_p, min_p);
+  } else {
+    k_dec_sample<NUC><<<B, SMP_NT, 0, st>>>(logits, V, temperature, top_k, seed, pos, ids, hist, hist_len, hist_base,
+                                            top_p, min_p);
+  }
+}
+
 DLT_API int dlt_dec_sample(const float* logits, int B, int V, float temperature, int top_k, uint32_t seed,
                            const long* pos, long* ids, long* hist, int hist_len, int hist_base, int* ws,
                            hipStream_t st) {
   if (V <= 0 || temperature <= 0.f) return -1;
-  if (ws && top_k >= 1 && top_k <= 64 && V <= SMP_NS * SMP_SLICE && top_k < V) {
-    k_dec_topk_slices<<<dim3(SMP_NS, B), SMP_NT, 0, st>>>(logits, V, temperature, top_k, ws);
-    k_dec_topk_draw<<<B, SMP_NT, 0, st>>>(ws, logits, V, temperature, top_k, seed, pos, ids, hist, hist_len,
-                                          hist_base);
-  } else {
-    k_dec_sample<<<B, SMP_NT, 0, st>>>(logits, V, temperature, top_k, seed, pos, ids, hist, hist_len, hist_base);
-  }
+  dec_sample_launch<false>(logits, B, V, temperature, top_k, seed, pos, ids, hist, hist_len, hist_base, ws, 1.f, 0.f,
+                           st);
+  DLT_CHECK_LAUNCH();
+}
+
+// dlt_dec_sample with nucleus (0 < top_p <= 1; 1: off) and min-p (0 <= min_p < 1; 0: off) filters
+// on top of top-k; the same workspace.  The mass sums are 40-bit fixed point: V < 2^24.
+DLT_API int dlt_dec_sample_p(const float* logits, int B, int V, float temperature, int top_k, float top_p, float min_p,
+                             uint32_t seed, const long* pos, long* ids, long* hist, int hist_len, int hist_base,
+                             int* ws, hipStream_t st) {
+  if (V <= 0 || V >= (1 << 24) || temperature <= 0.f) return -1;
+  if (!(top_p > 0.f && top_p <= 1.f) || !(min_p >= 0.f && min_p < 1.f)) return -1;
+  dec_sample_launch<true>(logits, B, V, temperature, top_k, seed, pos, ids, hist, hist_len, hist_base, ws, top_p,
+                          min_p, st);
   DLT_CHECK_LAUNCH();
 }
 

@@ -110,6 +110,8 @@ _SIGS = {
     "dlt_dec_norm_head": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "dlt_dec_sample": [c_void_p, c_int, c_int, c_float, c_int, c_uint32, c_void_p, c_void_p, c_void_p, c_int, c_int,
                        c_void_p, c_void_p],
+    "dlt_dec_sample_p": [c_void_p, c_int, c_int, c_float, c_int, c_float, c_float, c_uint32, c_void_p, c_void_p, c_void_p,
+                         c_int, c_int, c_void_p, c_void_p],
     "dlt_dec_sample_ws_ints": [c_int],
     "dlt_dec_advance": [c_void_p, c_void_p],
 }
@@ -355,12 +357,26 @@ def dec_sample_workspace(B: int, device) -> torch.Tensor:
     return torch.empty(int(lib().dlt_dec_sample_ws_ints(B)), dtype=torch.int32, device=device)
 
 
-def dec_sample(logits, temperature, top_k, seed, pos, ids, hist, hist_base, ws=None):
+def check_top_p_min_p(top_p, min_p):
+    """(top_p, min_p) as floats; ValueError unless 0 < top_p <= 1 and 0 <= min_p < 1 (a NaN
+    or an infinity fails either comparison)."""
+    top_p, min_p = float(top_p), float(min_p)
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"top_p={top_p}: expected 0 < top_p <= 1 (1: no nucleus filter)")
+    if not 0.0 <= min_p < 1.0:
+        raise ValueError(f"min_p={min_p}: expected 0 <= min_p < 1 (0: no min-p filter)")
+    return top_p, min_p
+
+
+def dec_sample(logits, temperature, top_k, seed, pos, ids, hist, hist_base, ws=None, top_p=1.0, min_p=0.0):
     """One top-k multinomial draw per row of ``logits`` [B, V] (fp32) on the device: the
     id goes to ``ids`` (B int64, the next decode step's input) and to
     ``hist[b, pos + 1 - hist_base]`` (int64 [B, L]) when inside the history.  With ``ws``
     (:func:`dec_sample_workspace`) and 1 <= top_k <= 64 the row is split over 16
-    workgroups."""
+    workgroups.  ``top_p`` < 1 (nucleus over what top-k leaves) and ``min_p`` > 0 (keep
+    p >= min_p * p_max) raise the threshold further in the kernels' ``NUC`` forms; with both
+    off this launches the plain kernels."""
+    top_p, min_p = check_top_p_min_p(top_p, min_p)
     B, V = logits.shape
     if ws is not None:
         _req(ws, torch.int32, "dec.sample_ws", int(lib().dlt_dec_sample_ws_ints(B)))
@@ -370,8 +386,18 @@ def dec_sample(logits, temperature, top_k, seed, pos, ids, hist, hist_base, ws=N
     _req(hist, torch.int64, "dec.hist")
     if hist.dim() != 2 or hist.shape[0] != B:
         raise ValueError("dec_sample: hist must be [B, L]")
-    _chk(lib().dlt_dec_sample(_p(logits), B, V, float(temperature), int(top_k), int(seed) & 0xFFFFFFFF, _p(pos),
-                              _p(ids), _p(hist), hist.shape[1], int(hist_base), _p(ws), _stream()), "dec_sample")
+    # the kernels take fp32: decide on the rounded values (a top_p that rounds to 1 is off; a
+    # min_p that rounds to 1 is the largest fp32 below it)
+    top_p, min_p = max(c_float(top_p).value, 2.0 ** -126), min(c_float(min_p).value, 1.0 - 2.0 ** -24)
+    if top_p == 1.0 and min_p == 0.0:
+        _chk(lib().dlt_dec_sample(_p(logits), B, V, float(temperature), int(top_k), int(seed) & 0xFFFFFFFF, _p(pos),
+                                  _p(ids), _p(hist), hist.shape[1], int(hist_base), _p(ws), _stream()), "dec_sample")
+        return
+    if V >= 1 << 24:
+        raise ValueError("dec_sample: top_p / min_p need V < 2^24 (40-bit fixed-point mass sums)")
+    _chk(lib().dlt_dec_sample_p(_p(logits), B, V, float(temperature), int(top_k), top_p, min_p,
+                                int(seed) & 0xFFFFFFFF, _p(pos), _p(ids), _p(hist), hist.shape[1], int(hist_base),
+                                _p(ws), _stream()), "dec_sample")
 
 
 def dec_advance(pos):
