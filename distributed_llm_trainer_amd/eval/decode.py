@@ -110,6 +110,12 @@ def _rep_kv(t: torch.Tensor, cfg) -> torch.Tensor:
     return t if G == 1 else t.repeat_interleave(G, dim=1)
 
 
+def _softcap(logits: torch.Tensor, cfg) -> torch.Tensor:
+    """The model's final-logit soft cap (cfg.logit_softcap) on fp32 logits; unset: the logits themselves."""
+    cap = getattr(cfg, "logit_softcap", None)
+    return logits if cap is None else cap * torch.tanh(logits / cap)
+
+
 @torch.no_grad()
 def forward_cached(model, ids: torch.Tensor, cache: KVCache) -> torch.Tensor:
     """Append ``ids`` [B, T] at positions cache.len.. ; returns last-position logits [B, V]."""
@@ -159,7 +165,7 @@ def forward_cached(model, ids: torch.Tensor, cache: KVCache) -> torch.Tensor:
         prov.post_forward(i)
     hw = prov.head()
     nf = _rms(h[:, -1], hw.norm, eng.eps).to(dt)
-    logits = torch.matmul(nf, hw.lm_head.t())[:, :cfg.vocab_size].float()
+    logits = _softcap(torch.matmul(nf, hw.lm_head.t())[:, :cfg.vocab_size].float(), cfg)
     prov.post_forward("head")
     cache.len = p0 + T
     return logits
@@ -251,7 +257,11 @@ class DecodeGraph:
             ops.dec_gemv_res(self.ob, w.wo, self.h)
             ops.dec_norm_gu(self.h, w.ln2, eng.eps, w.wgu, self.sb)
             ops.dec_gemv_res(self.sb, w.wdown, self.h)
-        ops.dec_norm_head(self.h, hw.norm, eng.eps, hw.lm_head, self.lg, cfg.vocab_size)
+        cap = getattr(cfg, "logit_softcap", None)
+        if cap is None:
+            ops.dec_norm_head(self.h, hw.norm, eng.eps, hw.lm_head, self.lg, cfg.vocab_size)
+        else:  # the CAP kernel: the sampler below reads capped logits
+            ops.dec_norm_head(self.h, hw.norm, eng.eps, hw.lm_head, self.lg, cfg.vocab_size, softcap=cap)
         if self.sample is not None:
             sm = self.sample
             ops.dec_sample(self.lg, sm["temperature"], sm["top_k"], sm["seed"], self.pos, self.ids, sm["hist"],
@@ -297,7 +307,7 @@ class DecodeGraph:
             I = cfg.intermediate_size
             h = h + torch.matmul((F.silu(gu[..., :I]) * gu[..., I:]).to(dt), w.wdown.t()).float()
         nf = _rms(h[:, -1], hw.norm, eng.eps).to(dt)
-        return torch.matmul(nf, hw.lm_head.t())[:, :cfg.vocab_size].float()
+        return _softcap(torch.matmul(nf, hw.lm_head.t())[:, :cfg.vocab_size].float(), cfg)
 
     def __call__(self, ids: torch.Tensor) -> torch.Tensor:
         """Append ``ids`` [B, 1] at position cache.len; returns logits [B, V] (graph-owned:

@@ -18,6 +18,7 @@ Intentional divergences (documented in SURVEY.md §7.1 / Appendix A):
 """
 from __future__ import annotations
 
+import math
 from dataclasses import asdict, dataclass, fields
 from typing import Any, Dict, Optional
 
@@ -60,6 +61,10 @@ class GPTConfig:
     # the softmax denominator and has no value row: p_j = exp(s_j) / (sum_j exp(s_j) + exp(sink)).
     attention_sinks: bool = False
 
+    # Final-logit soft-capping (Gemma-2's rule, cap 30 there): the model's logits are
+    # cap * tanh(lm_head(norm(h)) / cap), in training, evaluation and generation alike.  None = off.
+    logit_softcap: Optional[float] = None
+
     # Sliding-window (local) attention: query q sees key k iff q - W < k <= q, W keys with its
     # own (the Mistral / Gemma rule).  With sliding_window_pattern = N, layer i (0-based) is
     # global (plain causal) iff (i + 1) % N == 0 (Gemma-3's rule); unset, every layer is windowed.
@@ -93,6 +98,11 @@ class GPTConfig:
             if isinstance(n, bool) or int(n) != n or n < 2:
                 raise ValueError(f"sliding_window_pattern ({n!r}) must be an integer >= 2")
             self.sliding_window_pattern = int(n)
+        if self.logit_softcap is not None:
+            c = self.logit_softcap
+            if isinstance(c, bool) or not isinstance(c, (int, float)) or not math.isfinite(c) or c <= 0:
+                raise ValueError(f"logit_softcap ({c!r}) must be a finite float > 0")
+            self.logit_softcap = float(c)
 
     # ------------------------------------------------------------------ presets
     @classmethod
@@ -200,7 +210,7 @@ class GPTConfig:
             del d["qk_norm"]
         if not self.attention_sinks:  # ... and configs without attention sinks
             del d["attention_sinks"]
-        for k in ("sliding_window", "sliding_window_pattern"):  # ... and unwindowed ones
+        for k in ("sliding_window", "sliding_window_pattern", "logit_softcap"):  # ... and unwindowed / uncapped ones
             if d[k] is None:
                 del d[k]
         return d
@@ -216,7 +226,7 @@ class GPTConfig:
             state.pop("qk_norm", None)
         if not state.get("attention_sinks"):
             state.pop("attention_sinks", None)
-        for k in ("sliding_window", "sliding_window_pattern"):
+        for k in ("sliding_window", "sliding_window_pattern", "logit_softcap"):
             if state.get(k) is None:
                 state.pop(k, None)
         return state
@@ -229,6 +239,7 @@ class GPTConfig:
         self.attention_sinks = bool(self.__dict__.get("attention_sinks", False))
         self.__dict__.setdefault("sliding_window", None)
         self.__dict__.setdefault("sliding_window_pattern", None)
+        self.__dict__.setdefault("logit_softcap", None)
 
     @classmethod
     def from_dict(cls, d: Dict[str, Any]) -> "GPTConfig":

@@ -285,9 +285,17 @@ class GPTEngine:
         # (k_attn_sink_bwd, from lse and the delta workspace); o and lse are kept anyway, so
         # activation checkpointing keeps nothing new
         self.sinks = bool(getattr(cfg, "attention_sinks", False))
+        # final-logit soft cap (cfg.logit_softcap; 0 = off): every cross-entropy call of the head takes
+        # softcap= (the CAP kernels), evaluation runs lm_head GEMM + CAP cross-entropy in row chunks, and
+        # returned logits are capped
+        self.softcap = float(getattr(cfg, "logit_softcap", None) or 0.0)
         if getattr(ops, "backend", "") == "hip":  # the GPU routes; the reference ops have every feature
             attn_routes.check_attention_features("cuda", cfg.head_dim, act_dtype, attn_routes.config_features(cfg),
                                                  self.packed_qkv)
+            from ..ops import hip_f32
+            if self.softcap and act_dtype == torch.float32 and "logit_softcap" in hip_f32.REFUSED_FEATURES:
+                raise NotImplementedError("this model on the GPU: fp32 activations have no final-logit soft-capping "
+                                          "(logit_softcap); use bf16 or fp16 activations")
         # last layers of the deferred-wgrad backward whose weight gradients run on the
         # current stream instead of the side stream (see _backward_gen)
         self.main_wgrad_layers = int(os.environ.get("DLT_MAIN_WGRAD_LAYERS", "1"))
@@ -353,12 +361,18 @@ class GPTEngine:
 
     def _head_ce(self, lg, targets, V: int, norm, zparts: list) -> torch.Tensor:
         """One cross-entropy call of the training head (gradient in place, pre-scaled by
-        ce_grad_scale).  With a z-loss coefficient: the Z form, whose rows' lse^2 join ``zparts``."""
-        if self.z_loss == 0.0:
+        ce_grad_scale).  With a z-loss coefficient: the Z form, whose rows' lse^2 join ``zparts``.
+        With the model's soft cap: the CAP form (of either), so every head schedule caps here."""
+        if self.z_loss == 0.0 and self.softcap == 0.0:
             return self.ops.cross_entropy_fwd_bwd(lg, targets, V, norm, self.ce_grad_scale)
-        z_rows = torch.empty(lg.shape[0], dtype=torch.float32, device=lg.device)
-        zparts.append(z_rows)
-        return self.ops.cross_entropy_fwd_bwd(lg, targets, V, norm, self.ce_grad_scale, self.z_loss, z_rows)
+        z_rows = None
+        if self.z_loss != 0.0:
+            z_rows = torch.empty(lg.shape[0], dtype=torch.float32, device=lg.device)
+            zparts.append(z_rows)
+        if self.softcap == 0.0:
+            return self.ops.cross_entropy_fwd_bwd(lg, targets, V, norm, self.ce_grad_scale, self.z_loss, z_rows)
+        return self.ops.cross_entropy_fwd_bwd(lg, targets, V, norm, self.ce_grad_scale, self.z_loss, z_rows,
+                                              softcap=self.softcap)
 
     def set_loss_segments(self, n: int) -> None:
         """Declare that each training forward carries ``n`` fused micro-steps.
@@ -723,13 +737,27 @@ class GPTEngine:
         and does not advance ``micro_counter``.  The head is the logits-free
         ``lmhead_loss`` when it takes the shape and the activations are 16-bit, else the
         lm_head GEMM + ``cross_entropy_fwd_bwd`` (fp32, padded vocabularies that are no
-        multiple of 128); ``DLT_EVAL_HEAD=unfused`` forces the latter (A/B knob)."""
+        multiple of 128); ``DLT_EVAL_HEAD=unfused`` forces the latter (A/B knob).  A model with
+        ``logit_softcap`` runs lm_head GEMM + CAP cross-entropy through one buffer of a quarter
+        of the rows (``lmhead_loss`` has no CAP epilogue); the value is the plain cross-entropy
+        of the capped logits whatever ``z_loss`` is."""
         loss_sum, n_valid, _ = _drain(self._forward_gen(ids, targets, False, need_backward=False, loss_only=True))
         return loss_sum, n_valid
 
     def _eval_row_loss(self, nf, w, targets, V: int) -> torch.Tensor:
         """Per-row loss of the evaluation head (see :meth:`eval_loss`)."""
         ops = self.ops
+        if self.softcap != 0.0:
+            rows = nf.shape[0]
+            rc = max(1, min(-(-rows // 4), 2048))
+            lg_buf = torch.empty(min(rc, rows), w.shape[0], dtype=nf.dtype, device=nf.device)
+            parts = []
+            for a in range(0, rows, rc):
+                b = min(a + rc, rows)
+                lg = self.gemm.linear(nf[a:b], w, out=lg_buf[:b - a])
+                parts.append(ops.cross_entropy_fwd_bwd(lg, targets[a:b], V, (targets[a:b] != -100).sum(), 1.0,
+                                                       softcap=self.softcap))
+            return parts[0] if len(parts) == 1 else torch.cat(parts)
         takes = nf.dtype in (torch.bfloat16, torch.float16) or getattr(ops, "backend", "") == "reference"
         if (os.environ.get("DLT_EVAL_HEAD", "fused") != "unfused" and takes and hasattr(ops, "lmhead_loss")
                 and ops.lmhead_loss_fits(nf.shape[0], w.shape[0], nf.shape[1])):
@@ -866,6 +894,8 @@ class GPTEngine:
         if return_logits or targets is None:
             lg2 = self.gemm.linear(nf, hw.lm_head)
             logits = lg2[:, :V].reshape(B, S, V)
+            if self.softcap != 0.0:  # fp32 from the rounded logits, as the CAP kernels form it
+                logits = self.softcap * torch.tanh(logits.float() / self.softcap)
         prov.post_forward("head")
         return loss, logits, (st if need_bwd else None)
 

@@ -326,6 +326,9 @@ class GPT(nn.Module):
                 h = layer(h, attention_mask, doc_hidden)
         h = self.norm(h)
         logits = self.lm_head(h)
+        cap = getattr(self.config, "logit_softcap", None)
+        if cap is not None:  # the model's logits: fp32 from the rounded lm_head output
+            logits = cap * torch.tanh(logits.float() / cap)
         loss = None
         if labels is not None:
             shift_logits = logits[..., :-1, :].contiguous()

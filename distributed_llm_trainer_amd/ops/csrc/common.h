@@ -78,6 +78,14 @@ __device__ __forceinline__ uint32_t drop_bits(uint32_t key, uint64_t idx) {
 // emits for `1.f / x` is a ~10-instruction sequence, which dominated the SwiGLU GEMM
 // epilogue.  Every SwiGLU kernel uses this one so the fused and unfused paths agree.
 __device__ __forceinline__ float dlt_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
+// tanh(x / cap) of the final-logit soft cap, k2 = 2 log2(e) / cap: with a = exp2(-|x| k2) in [0, 1]
+// and r = rcp(1 + a) it is copysign((1 - a) r, x), and 1 - tanh^2 = 4 a r^2 (a and r are returned for
+// it).  Nothing overflows; an underflowing a gives exactly +-1 and a derivative of exactly 0.
+__device__ __forceinline__ float dlt_cap_tanh(float x, float k2, float& a, float& r) {
+  a = __builtin_amdgcn_exp2f(-fabsf(x) * k2);
+  r = __builtin_amdgcn_rcpf(1.f + a);
+  return copysignf((1.f - a) * r, x);
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

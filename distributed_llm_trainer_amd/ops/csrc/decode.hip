@@ -625,10 +625,13 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_norm_gu(const float* __restrict_
 }
 
 // logits[b][r] = float(bf16(RMSNorm(h[b]) . E[r])) for r < V; 16 rows per workgroup.
-template <int B>
+// CAP: the model's final-logit soft cap, cap * tanh(x / cap) of that rounded value in fp32
+// (dlt_cap_tanh, the cross-entropy CAP forms' formulation), applied before the store.  CAP is
+// compile-time: the plain form never reads `cap`.
+template <int B, bool CAP = false>
 __global__ __launch_bounds__(DEC_NT) void k_dec_norm_head(const float* __restrict__ h, const void* __restrict__ lnw,
                                                           int wbf16, float eps, const bf16_t* __restrict__ emb,
-                                                          float* __restrict__ logits, int H, int V) {
+                                                          float* __restrict__ logits, int H, int V, float cap) {
   extern __shared__ __attribute__((aligned(16))) char dsm[];
   bf16_t* xs = reinterpret_cast<bf16_t*>(dsm);
   float* red = reinterpret_cast<float*>(dsm + (size_t)B * H * 2);
@@ -647,7 +650,14 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_norm_head(const float* __restric
     for (int r = 0; r < 4; ++r)
       if (r0 + r < V) {
 #pragma unroll
-        for (int b = 0; b < B; ++b) logits[(size_t)b * V + r0 + r] = bf_round(acc[r][b]);
+        for (int b = 0; b < B; ++b) {
+          if constexpr (CAP) {
+            float a, rc;
+            logits[(size_t)b * V + r0 + r] = cap * dlt_cap_tanh(bf_round(acc[r][b]), 2.88539008177792681472f / cap, a, rc);
+          } else {
+            logits[(size_t)b * V + r0 + r] = bf_round(acc[r][b]);
+          }
+        }
       }
   }
 }
@@ -1315,7 +1325,19 @@ DLT_API int dlt_dec_norm_gu(const float* h, const void* lnw, int wbf16, float ep
 DLT_API int dlt_dec_norm_head(const float* h, const void* lnw, int wbf16, float eps, const bf16_t* emb,
                               float* logits, int B, int H, int V, hipStream_t st) {
   if (H % 8 || dec_lds(B, H) > 160 * 1024) return -1;
-#define L(BB) k_dec_norm_head<BB><<<(V + 15) / 16, DEC_NT, dec_lds(BB, H), st>>>(h, lnw, wbf16, eps, emb, logits, H, V)
+#define L(BB) \
+  k_dec_norm_head<BB><<<(V + 15) / 16, DEC_NT, dec_lds(BB, H), st>>>(h, lnw, wbf16, eps, emb, logits, H, V, 0.f)
+  DEC_DISPATCH(B, L)
+#undef L
+  DLT_CHECK_LAUNCH();
+}
+
+// The CAP form of dlt_dec_norm_head: logits = cap * tanh(logits / cap), cap finite and > 0.
+DLT_API int dlt_dec_norm_head_cap(const float* h, const void* lnw, int wbf16, float eps, const bf16_t* emb,
+                                  float* logits, int B, int H, int V, float cap, hipStream_t st) {
+  if (H % 8 || dec_lds(B, H) > 160 * 1024 || !(cap > 0.f) || cap > 3.0e38f) return -1;
+#define L(BB) \
+  k_dec_norm_head<BB, true><<<(V + 15) / 16, DEC_NT, dec_lds(BB, H), st>>>(h, lnw, wbf16, eps, emb, logits, H, V, cap)
   DEC_DISPATCH(B, L)
 #undef L
   DLT_CHECK_LAUNCH();

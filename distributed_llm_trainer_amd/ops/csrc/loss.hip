@@ -23,14 +23,26 @@
 // receives lse^2 (0 on ignored rows); the caller forms c * sum(z_rows) / n_valid.  ZL is
 // compile-time: the plain forms never read the two extra arguments and keep the vector
 // code, registers, LDS and scratch they had before the Z forms existed (profiles/z_loss.md).
+//
+// CAP forms (CAP = true; launched with a final-logit soft cap): the row's logits are
+// c = cap * tanh(x / cap) of the stored 16-bit x, formed in fp32 per element and never stored.
+// With a = exp2(-|x| * k2), k2 = 2 log2(e) / cap, and r = rcp(1 + a):
+//   tanh(x / cap) = copysign((1 - a) * r, x)      1 - tanh^2 = 4 a r^2
+// a lies in [0, 1], so nothing overflows: a huge |x| / cap underflows a to 0, which gives tanh = +-1
+// and a derivative of exactly 0; the derivative is a product, never 1 - t * t.  tanh is monotone,
+// so the max pass runs on the raw values and the maximum is capped once.  The sum pass costs an
+// exp2 and a rcp more per element, the gradient pass the same plus the derivative's products.
+// loss_rows is lse(c) - c_t, z_rows lse(c)^2, and the in-place gradient
+// grad_scale * (p zf - [j == t]) * (1 - tanh^2) / n_valid with p = softmax(c).  CAP is compile-time
+// like ZL: the other forms never read the cap (profiles/logit_softcap.md).
 #include "common.h"
 #include <cstdlib>
 
-template <int HK = 0, bool ZL = false>
+template <int HK = 0, bool ZL = false, bool CAP = false>
 __global__ __launch_bounds__(256) void k_ce_fwd_bwd(bf16_t* __restrict__ logits, const int64_t* __restrict__ targets,
                                                     const int64_t* __restrict__ n_valid, float* __restrict__ loss_rows,
                                                     int M, int Vp, int V, float gscale, float zcoef,
-                                                    float* __restrict__ z_rows) {
+                                                    float* __restrict__ z_rows, float cap) {
   __shared__ float sm_m[4], sm_s[4];
   const int row = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -39,6 +51,17 @@ __global__ __launch_bounds__(256) void k_ce_fwd_bwd(bf16_t* __restrict__ logits,
   DLT_DASSERT(tgt == -100 || (tgt >= 0 && tgt < V));  // ignore_index or a real token
   const bool valid = tgt >= 0 && tgt < V;
   const int nchunk = Vp >> 3;
+  const float k2 = CAP ? 2.88539008177792681472f / cap : 0.f;  // 2 log2(e) / cap
+  // the logit of the softmax: the stored value, or its capped form
+  auto lg = [&](uint16_t h) -> float {
+    const float x = h2f<HK>(h);
+    if constexpr (CAP) {
+      float a, r;
+      return cap * dlt_cap_tanh(x, k2, a, r);
+    } else {
+      return x;
+    }
+  };
   // pass 1: online max / sum-exp
   float mx = -INFINITY, sm = 0.f;
   for (int c = tid; c < nchunk; c += 256) {
@@ -47,7 +70,7 @@ __global__ __launch_bounds__(256) void k_ce_fwd_bwd(bf16_t* __restrict__ logits,
     float lm = -INFINITY;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      v[e] = (c * 8 + e < V) ? h2f<HK>(x.v[e]) : -INFINITY;
+      v[e] = (c * 8 + e < V) ? lg(x.v[e]) : -INFINITY;
       lm = fmaxf(lm, v[e]);
     }
     if (lm > mx) { sm *= __expf(mx - lm); mx = lm; }
@@ -71,7 +94,7 @@ __global__ __launch_bounds__(256) void k_ce_fwd_bwd(bf16_t* __restrict__ logits,
 #pragma unroll
   for (int w = 0; w < 4; ++w) gs += (sm_m[w] == -INFINITY) ? 0.f : sm_s[w] * __expf(sm_m[w] - gm);
   const float lse = gm + __logf(gs);
-  if (tid == 0) loss_rows[row] = valid ? (lse - h2f<HK>(lrow[tgt])) : 0.f;
+  if (tid == 0) loss_rows[row] = valid ? (lse - lg(lrow[tgt])) : 0.f;
   float zf = 1.f;
   if constexpr (ZL) {
     zf = fmaf(2.f * zcoef, lse, 1.f);
@@ -89,13 +112,22 @@ __global__ __launch_bounds__(256) void k_ce_fwd_bwd(bf16_t* __restrict__ logits,
       const int col = c * 8 + e;
       float g = 0.f;
       if (col < V) {
-        g = __expf(h2f<HK>(x.v[e]) - lse);
+        float dq = 1.f;  // CAP: a r^2, a quarter of 1 - tanh^2
+        if constexpr (CAP) {
+          float a, r;
+          const float ts = dlt_cap_tanh(h2f<HK>(x.v[e]), k2, a, r);
+          g = __expf(cap * ts - lse);
+          dq = a * r * r;
+        } else {
+          g = __expf(h2f<HK>(x.v[e]) - lse);
+        }
         if constexpr (ZL) {
           g = (col == tgt) ? (g * zf - 1.f) * inv_n : g * gmul;
         } else {
           if (col == tgt) g -= 1.f;
           g *= inv_n;
         }
+        if constexpr (CAP) g *= 4.f * dq;
       }
       x.v[e] = f2h<HK>(g);
     }
@@ -106,11 +138,11 @@ __global__ __launch_bounds__(256) void k_ce_fwd_bwd(bf16_t* __restrict__ logits,
 // gscale: factor on the gradient only (1 for bf16; the fp16 path stores the gradient
 // pre-multiplied by the loss scale so it does not underflow fp16, and the engine divides
 // the scale back out where it applies dloss)
-template <int CPT, int NTH = 512, bool CE_NT = false, int HK = 0, bool ZL = false>
+template <int CPT, int NTH = 512, bool CE_NT = false, int HK = 0, bool ZL = false, bool CAP = false>
 __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(NTH == 1024 ? 8 : 1, 8))) void k_ce_row(bf16_t* __restrict__ logits, const int64_t* __restrict__ targets,
                                                 const int64_t* __restrict__ n_valid, float* __restrict__ loss_rows,
                                                 int M, int Vp, int V, float gscale, float zcoef,
-                                                float* __restrict__ z_rows) {
+                                                float* __restrict__ z_rows, float cap) {
   // Per element only: max, one exp2 for the sum, one exp2 + scale for the gradient.
   // Column bounds are tested per 8-wide chunk (only the last chunk straddles V), and
   // the target column is patched by its owning thread per chunk, not per element.
@@ -172,6 +204,22 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(NTH == 1024
 #pragma unroll
   for (int w = 1; w < NTH / 64; ++w) gm = fmaxf(gm, red[w]);
   __syncthreads();
+  // CAP: the exponent of an element is tanh * (cap log2(e)) through the same fma, and the
+  // maximum is the capped raw maximum (tanh is monotone)
+  const float k2 = CAP ? (2.f * L2E) / cap : 0.f;
+  const float cl = CAP ? cap * L2E : L2E;
+  auto ex = [&](int t, int e) -> float {
+    if constexpr (CAP) {
+      float a, r;
+      return dlt_cap_tanh(el(t, e), k2, a, r);
+    } else {
+      return el(t, e);
+    }
+  };
+  if constexpr (CAP) {
+    float a, r;
+    gm = cap * dlt_cap_tanh(gm, k2, a, r);
+  }
   const float nm2 = -gm * L2E;
   float sm = 0.f;
 #pragma unroll
@@ -179,11 +227,11 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(NTH == 1024
     const int c = tid + NTH * t;
     if (c * 8 + 8 <= V) {
 #pragma unroll
-      for (int e = 0; e < 8; ++e) sm += __builtin_amdgcn_exp2f(fmaf(el(t, e), L2E, nm2));
+      for (int e = 0; e < 8; ++e) sm += __builtin_amdgcn_exp2f(fmaf(ex(t, e), cl, nm2));
     } else if (c < nchunk) {
 #pragma unroll
       for (int e = 0; e < 8; ++e)
-        if (c * 8 + e < V) sm += __builtin_amdgcn_exp2f(fmaf(el(t, e), L2E, nm2));
+        if (c * 8 + e < V) sm += __builtin_amdgcn_exp2f(fmaf(ex(t, e), cl, nm2));
     }
   }
   pin();
@@ -201,6 +249,16 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(NTH == 1024
   float zf = 1.f;
   if constexpr (ZL) zf = fmaf(2.f * zcoef, lse, 1.f);
   const float gmul = ZL ? (valid ? inv_n * zf : 0.f) : inv_n;  // an ignored row stays +0 whatever zf is
+  // one element of the gradient off the target: p * gmul, times 4 a r^2 = 1 - tanh^2 in the CAP form
+  auto ge = [&](int t, int e) -> float {
+    if constexpr (CAP) {
+      float a, r;
+      const float ts = dlt_cap_tanh(el(t, e), k2, a, r);
+      return __builtin_amdgcn_exp2f(fmaf(ts, cl, nl2)) * (gmul * 4.f) * (a * r * r);
+    } else {
+      return __builtin_amdgcn_exp2f(fmaf(el(t, e), L2E, nl2)) * gmul;
+    }
+  };
 #pragma unroll
   for (int t = 0; t < CPT; ++t) {
     const int c = tid + NTH * t;
@@ -208,21 +266,31 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(NTH == 1024
       u16x8 o;
       if (c * 8 + 8 <= V) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) o.v[e] = f2h<HK>(__builtin_amdgcn_exp2f(fmaf(el(t, e), L2E, nl2)) * gmul);
+        for (int e = 0; e < 8; ++e) o.v[e] = f2h<HK>(ge(t, e));
       } else {
 #pragma unroll
         for (int e = 0; e < 8; ++e)
-          o.v[e] = f2h<HK>(c * 8 + e < V ? __builtin_amdgcn_exp2f(fmaf(el(t, e), L2E, nl2)) * gmul : 0.f);
+          o.v[e] = f2h<HK>(c * 8 + e < V ? ge(t, e) : 0.f);
       }
       if (c == tchunk) {
         const int e = (int)(tgt & 7);
         float l = 0.f;
 #pragma unroll
         for (int j = 0; j < 8; ++j) l = (j == e) ? el(t, j) : l;
-        loss_rows[row] = lse - l;
+        float dt = 1.f;  // CAP: 1 - tanh^2 at the target
+        if constexpr (CAP) {
+          float a, r;
+          l = dlt_cap_tanh(l, k2, a, r);
+          dt = 4.f * (a * r * r);
+          loss_rows[row] = lse - cap * l;
+        } else {
+          loss_rows[row] = lse - l;
+        }
         if constexpr (ZL) z_rows[row] = lse * lse;
-        const float pt = __builtin_amdgcn_exp2f(fmaf(l, L2E, nl2));
-        const uint16_t gt = f2h<HK>(((ZL ? pt * zf : pt) - 1.f) * inv_n);
+        const float pt = __builtin_amdgcn_exp2f(fmaf(l, cl, nl2));
+        float gtf = ((ZL ? pt * zf : pt) - 1.f) * inv_n;
+        if constexpr (CAP) gtf *= dt;
+        const uint16_t gt = f2h<HK>(gtf);
 #pragma unroll
         for (int j = 0; j < 8; ++j) o.v[j] = (j == e) ? gt : o.v[j];
       }
@@ -244,13 +312,13 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(NTH == 1024
   }
 }
 
-// One launch choice for both forms, so a shape takes the same variant with and without the z-loss.
-template <int HK, bool ZL>
+// One launch choice for every form, so a shape takes the same variant with and without the z-loss or the cap.
+template <int HK, bool ZL, bool CAP = false>
 static void ce_launch(int wide, int nt, int cpt, hipStream_t st, bf16_t* logits, const int64_t* targets,
                       const int64_t* n_valid, float* loss_rows, int M, int Vp, int V, float gscale, float zcoef,
-                      float* z_rows) {
-#define CE_ARGS logits, targets, n_valid, loss_rows, M, Vp, V, gscale, zcoef, z_rows
-#define CE_ROW(CPT, NTH, NT) k_ce_row<CPT, NTH, NT, HK, ZL><<<M, NTH, 0, st>>>(CE_ARGS)
+                      float* z_rows, float cap = 0.f) {
+#define CE_ARGS logits, targets, n_valid, loss_rows, M, Vp, V, gscale, zcoef, z_rows, cap
+#define CE_ROW(CPT, NTH, NT) k_ce_row<CPT, NTH, NT, HK, ZL, CAP><<<M, NTH, 0, st>>>(CE_ARGS)
   if (wide && (Vp / 8 + 1023) / 1024 <= 7) {  // 1024 threads x 7 chunks (Vp <= 57344)
     if (nt) CE_ROW(7, 1024, true);
     else CE_ROW(7, 1024, false);
@@ -262,7 +330,7 @@ static void ce_launch(int wide, int nt, int cpt, hipStream_t st, bf16_t* logits,
   else if (cpt <= 8) CE_ROW(8, 512, false);
   else if (cpt <= 13) CE_ROW(13, 512, false);
   else if (cpt <= 16) CE_ROW(16, 512, false);
-  else k_ce_fwd_bwd<HK, ZL><<<M, 256, 0, st>>>(CE_ARGS);
+  else k_ce_fwd_bwd<HK, ZL, CAP><<<M, 256, 0, st>>>(CE_ARGS);
 #undef CE_ROW
 #undef CE_ARGS
 }
@@ -308,5 +376,23 @@ DLT_API int dlt_cross_entropy_z_fwd_bwd(bf16_t* logits, const int64_t* targets, 
   ce_choice(Vp, &wide, &nt, &cpt);
   DLT_HK_DISPATCH(hk, (ce_launch<HKC, true>(wide, nt, cpt, st, logits, targets, n_valid, loss_rows, M, Vp, V, gscale,
                                             zcoef, z_rows)));
+  DLT_CHECK_LAUNCH();
+}
+
+// The CAP form: the softmax runs over cap * tanh(logits / cap) (cap finite and > 0), with the z-loss
+// when zcoef != 0 (z_rows is then required; it may be null without a coefficient).
+DLT_API int dlt_cross_entropy_cap_fwd_bwd(bf16_t* logits, const int64_t* targets, const int64_t* n_valid,
+                                          float* loss_rows, int M, int Vp, int V, float gscale, int hk, float zcoef,
+                                          float* z_rows, float cap, hipStream_t st) {
+  if (Vp % 8 || V > Vp || !(cap > 0.f) || cap > 3.0e38f || (zcoef != 0.f && !z_rows)) return -1;
+  int wide, nt, cpt;
+  ce_choice(Vp, &wide, &nt, &cpt);
+  if (z_rows) {
+    DLT_HK_DISPATCH(hk, (ce_launch<HKC, true, true>(wide, nt, cpt, st, logits, targets, n_valid, loss_rows, M, Vp, V,
+                                                    gscale, zcoef, z_rows, cap)));
+  } else {
+    DLT_HK_DISPATCH(hk, (ce_launch<HKC, false, true>(wide, nt, cpt, st, logits, targets, n_valid, loss_rows, M, Vp, V,
+                                                     gscale, 0.f, nullptr, cap)));
+  }
   DLT_CHECK_LAUNCH();
 }

@@ -18,6 +18,7 @@ from typing import Optional
 import torch
 
 from . import rng
+from .reference import check_softcap  # noqa: F401  (one validation for both backends)
 
 _LIB = None
 # DLT_KERNEL_DEBUG=1 loads the bounds-checked build (ops/build.py --debug);
@@ -49,6 +50,8 @@ _SIGS = {
                                   c_void_p],
     "dlt_cross_entropy_z_fwd_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int,
                                     c_float, c_void_p, c_void_p],
+    "dlt_cross_entropy_cap_fwd_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int,
+                                      c_float, c_void_p, c_float, c_void_p],
     "dlt_sumsq": [c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
     "dlt_clip_coef": [c_void_p, c_void_p, c_float, c_float, c_float, c_void_p],
     "dlt_adamw": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float,
@@ -108,6 +111,8 @@ _SIGS = {
     "dlt_dec_gemv_res": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "dlt_dec_norm_gu": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "dlt_dec_norm_head": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
+    "dlt_dec_norm_head_cap": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
+                              c_void_p],
     "dlt_dec_sample": [c_void_p, c_int, c_int, c_float, c_int, c_uint32, c_void_p, c_void_p, c_void_p, c_int, c_int,
                        c_void_p, c_void_p],
     "dlt_dec_sample_p": [c_void_p, c_int, c_int, c_float, c_int, c_float, c_float, c_uint32, c_void_p, c_void_p, c_void_p,
@@ -340,7 +345,9 @@ def dec_norm_gu(h, ln, eps, wgu, s_out):
          "dec_norm_gu")
 
 
-def dec_norm_head(h, ln, eps, emb, logits, V):
+def dec_norm_head(h, ln, eps, emb, logits, V, softcap: float = 0.0):
+    """``softcap`` (0 = off): the model's final-logit cap, logits = cap * tanh(logits / cap) (the CAP kernel)."""
+    cap = _cap32(softcap, "dec_norm_head.softcap")
     B, H = h.shape
     _req(h, torch.float32, "dec.h", B * H)
     w, wbf16 = _norm_weight(ln, H, "dec.norm")
@@ -348,6 +355,10 @@ def dec_norm_head(h, ln, eps, emb, logits, V):
     _req(logits, torch.float32, "dec.logits", B * V)
     if emb.shape[0] < V or emb.shape[1] != H:
         raise ValueError("dec_norm_head: shape mismatch")
+    if cap != 0.0:
+        _chk(lib().dlt_dec_norm_head_cap(_p(h), _p(w), wbf16, float(eps), _p(emb), _p(logits), B, H, V, cap,
+                                         _stream()), "dec_norm_head_cap")
+        return
     _chk(lib().dlt_dec_norm_head(_p(h), _p(w), wbf16, float(eps), _p(emb), _p(logits), B, H, V, _stream()),
          "dec_norm_head")
 
@@ -1172,6 +1183,14 @@ def swiglu_bwd(gu, da, out=None, s_out=None):
 
 
 # ------------------------------------------------------------ cross-entropy
+def _cap32(softcap, name: str = "ce.softcap") -> float:
+    """check_softcap, and the cap must still be finite and > 0 as the fp32 the kernels receive."""
+    cap = check_softcap(softcap, name)
+    if cap != 0.0 and not 0.0 < ctypes.c_float(cap).value < math.inf:
+        raise ValueError(f"{name}: the cap must be finite and > 0 in fp32, got {softcap!r}")
+    return cap
+
+
 def check_z_rows(z_rows, logits, name: str = "ce.z_rows") -> None:
     """``z_rows`` of the z-loss form: fp32 [M], contiguous, on the logits' device."""
     if not isinstance(z_rows, torch.Tensor):
@@ -1185,7 +1204,7 @@ def check_z_rows(z_rows, logits, name: str = "ce.z_rows") -> None:
 
 
 def cross_entropy_fwd_bwd(logits, targets, vocab, n_valid, grad_scale: float = 1.0, z_loss: float = 0.0,
-                          z_rows=None):
+                          z_rows=None, softcap: float = 0.0):
     """Per-row loss; the logits buffer (bf16 or fp16) is overwritten by
     grad_scale * (softmax - onehot) / n_valid (fp16: grad_scale = the loss scale, so the
     gradient does not underflow).
@@ -1194,8 +1213,15 @@ def cross_entropy_fwd_bwd(logits, targets, vocab, n_valid, grad_scale: float = 1
     the gradient is that of ``(lse - logit[target]) + z_loss * lse^2``, i.e.
     grad_scale * (softmax * (1 + 2 z_loss lse) - onehot) / n_valid; the returned rows stay the
     cross-entropy part and ``z_rows`` receives lse^2 (0 on ignored rows).  Without either
-    argument the plain kernels run, as before the form existed."""
+    argument the plain kernels run, as before the form existed.
+
+    The CAP form (``softcap`` != 0, finite and > 0; 16-bit logits only): the softmax, the rows and
+    ``z_rows`` are those of ``c = softcap * tanh(logits / softcap)``, and every element of the
+    gradient carries ``1 - tanh^2(logits / softcap)``.  With ``softcap`` 0 the call is what it was."""
+    cap = _cap32(softcap)
     if logits.dtype == torch.float32:
+        if cap != 0.0:
+            raise NotImplementedError("ce.softcap: fp32 logits have no CAP kernel on the GPU (logit_softcap)")
         from . import hip_f32
         return hip_f32.cross_entropy_fwd_bwd(logits, targets, vocab, n_valid, grad_scale, z_loss, z_rows)
     M, Vp = logits.shape
@@ -1205,6 +1231,15 @@ def cross_entropy_fwd_bwd(logits, targets, vocab, n_valid, grad_scale: float = 1
         raise ValueError("ce.targets must be int64 [M]")
     nv = n_valid.reshape(1).to(torch.int64).contiguous()
     loss = torch.empty(M, dtype=torch.float32, device=logits.device)
+    if cap != 0.0:
+        if float(z_loss) != 0.0 or z_rows is not None:
+            check_z_rows(z_rows, logits)
+        if Vp % 8 or vocab > Vp:
+            raise ValueError(f"ce.logits: the padded width {Vp} must be a multiple of 8 and hold the vocabulary {vocab}")
+        _chk(lib().dlt_cross_entropy_cap_fwd_bwd(_p(logits), _p(targets), _p(nv), _p(loss), M, Vp, vocab,
+                                                 float(grad_scale), hk, float(z_loss), _p(z_rows), cap, _stream()),
+             "cross_entropy_cap")
+        return loss
     if float(z_loss) == 0.0 and z_rows is None:
         _chk(lib().dlt_cross_entropy_fwd_bwd(_p(logits), _p(targets), _p(nv), _p(loss), M, Vp, vocab,
                                              float(grad_scale), hk, _stream()), "cross_entropy")

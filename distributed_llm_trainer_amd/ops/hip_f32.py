@@ -467,9 +467,18 @@ def swiglu_bwd(gu, da, out=None, s_out=None):
 
 
 # ------------------------------------------------------------ cross-entropy
+# Model features the fp32 route has no kernels for, beside the attention features of ops/attn_routes.py:
+# the engine refuses them where it is configured, before any step.
+REFUSED_FEATURES = frozenset(("logit_softcap",))
+
+
 def cross_entropy_fwd_bwd(logits, targets, vocab, n_valid, grad_scale: float = 1.0, z_loss: float = 0.0,
-                          z_rows=None):
-    """fp32 logits; ``z_loss`` / ``z_rows``: the z-loss form, as ``hip.cross_entropy_fwd_bwd``."""
+                          z_rows=None, softcap: float = 0.0):
+    """fp32 logits; ``z_loss`` / ``z_rows``: the z-loss form, as ``hip.cross_entropy_fwd_bwd``.
+    ``softcap`` != 0 is refused: the CAP forms are 16-bit only."""
+    if softcap:
+        raise NotImplementedError("ce.softcap: fp32 logits have no CAP kernel on the GPU (logit_softcap); "
+                                  "use bf16 or fp16 activations")
     M, Vp = logits.shape
     _req32(logits, "ce_f32.logits")
     targets = targets.contiguous()

@@ -464,9 +464,29 @@ def swiglu_bwd(gu: torch.Tensor, da: torch.Tensor, out=None, s_out=None) -> torc
 
 
 # ------------------------------------------------------ cross-entropy (fused with grad)
+def check_softcap(softcap, name: str = "ce.softcap") -> float:
+    """The final-logit soft cap of an op as a float: 0 (or None) is off; otherwise a real number
+    (no bool), finite and > 0."""
+    if softcap is None:
+        return 0.0
+    if isinstance(softcap, bool) or not isinstance(softcap, (int, float)):
+        raise TypeError(f"{name}: expected a float, got {softcap!r}")
+    cap = float(softcap)
+    if cap == 0.0:
+        return 0.0
+    if not math.isfinite(cap) or cap < 0.0:
+        raise ValueError(f"{name}: the cap must be finite and > 0 (0 turns it off), got {softcap!r}")
+    return cap
+
+
+def softcap_logits(logits: torch.Tensor, cap: float) -> torch.Tensor:
+    """``cap * tanh(logits / cap)`` in fp32 (the model's final-logit soft cap; logits as stored)."""
+    return float(cap) * torch.tanh(logits.float() / float(cap))
+
+
 def cross_entropy_fwd_bwd(logits: torch.Tensor, targets: torch.Tensor, vocab: int,
                           n_valid: torch.Tensor, grad_scale: float = 1.0, z_loss: float = 0.0,
-                          z_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+                          z_rows: Optional[torch.Tensor] = None, softcap: float = 0.0) -> torch.Tensor:
     """Per-row loss [M] fp32; ``logits`` [M, Vp] is overwritten with
     grad_scale * dloss_mean/dlogits.
 
@@ -477,7 +497,12 @@ def cross_entropy_fwd_bwd(logits: torch.Tensor, targets: torch.Tensor, vocab: in
     ``(lse - logit[target]) + z_loss * lse^2``, so the softmax part of the gradient carries
     the factor ``1 + 2 z_loss lse`` (possibly negative; used as it is).  The returned rows stay
     the cross-entropy part and ``z_rows`` receives lse^2 (0 on ignored rows).
+
+    The CAP form (``softcap`` != 0, finite and > 0): everything above is taken of
+    ``c = softcap * tanh(logits / softcap)``, formed in fp32 from the stored logits, and the
+    gradient with respect to the stored logits carries ``1 - tanh^2(logits / softcap)``.
     """
+    cap = check_softcap(softcap)
     zform = float(z_loss) != 0.0 or z_rows is not None
     if zform:
         if not isinstance(z_rows, torch.Tensor):
@@ -489,6 +514,9 @@ def cross_entropy_fwd_bwd(logits: torch.Tensor, targets: torch.Tensor, vocab: in
         if tuple(z_rows.shape) != (logits.shape[0],):
             raise ValueError(f"ce.z_rows: expected [{logits.shape[0]}], got {tuple(z_rows.shape)}")
     lf = logits[:, :vocab].float()
+    if cap != 0.0:
+        th = torch.tanh(lf / cap)
+        lf = cap * th
     lse = torch.logsumexp(lf, dim=-1)
     valid = targets != IGNORE_INDEX
     tgt = torch.where(valid, targets, torch.zeros_like(targets))
@@ -500,6 +528,8 @@ def cross_entropy_fwd_bwd(logits: torch.Tensor, targets: torch.Tensor, vocab: in
         z_rows.copy_(torch.where(valid, lse * lse, torch.zeros_like(lse)))
     grad.scatter_add_(1, tgt.unsqueeze(1), -torch.ones_like(picked).unsqueeze(1))
     grad = grad * (valid.float() * grad_scale / n_valid.float().clamp(min=1)).unsqueeze(1)
+    if cap != 0.0:
+        grad = grad * (1.0 - th * th)
     logits.zero_()
     logits[:, :vocab] = grad.to(logits.dtype)
     return loss

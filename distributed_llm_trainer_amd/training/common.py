@@ -270,6 +270,11 @@ def add_model_args(p) -> None:
                    help="attention sinks: one learned fp32 logit per query head and layer that takes part in the "
                         "softmax denominator and has no value row (the gpt-oss form).  Overrides the YAML's "
                         "model.attention_sinks and the preset (default: off)")
+    p.add_argument("--logit_softcap", type=float, default=None, metavar="CAP",
+                   help="final-logit soft-capping: the model's logits are CAP * tanh(logits / CAP) (a finite "
+                        "CAP > 0; Gemma-2 and the GPT-2 speed-run recipes use 30), in training, evaluation and "
+                        "generation, and saved in checkpoints.  Overrides the YAML's model.logit_softcap and the "
+                        "preset (default: off)")
 
 
 def apply_model_args(args, model_config) -> None:
@@ -284,11 +289,14 @@ def apply_model_args(args, model_config) -> None:
     if getattr(args, "attention_sinks", None) is not None:
         model_config.attention_sinks = bool(args.attention_sinks)
     sw, swp = getattr(args, "sliding_window", None), getattr(args, "sliding_window_pattern", None)
-    if sw is not None or swp is not None:
+    cap = getattr(args, "logit_softcap", None)
+    if sw is not None or swp is not None or cap is not None:
         if sw is not None:
             model_config.sliding_window = sw
         if swp is not None:
             model_config.sliding_window_pattern = swp
+        if cap is not None:
+            model_config.logit_softcap = cap
         model_config.__post_init__()  # the config's own validation (ValueError)
 
 
