@@ -116,6 +116,13 @@ def _softcap(logits: torch.Tensor, cfg) -> torch.Tensor:
     return logits if cap is None else cap * torch.tanh(logits / cap)
 
 
+def _cap_scores(s: torch.Tensor, cfg) -> torch.Tensor:
+    """The model's attention-score soft cap (cfg.attn_softcap) on fp32 scaled scores, before any
+    mask; unset: the scores themselves."""
+    cap = getattr(cfg, "attn_softcap", None)
+    return s if cap is None else float(cap) * torch.tanh(s / float(cap))
+
+
 @torch.no_grad()
 def forward_cached(model, ids: torch.Tensor, cache: KVCache) -> torch.Tensor:
     """Append ``ids`` [B, T] at positions cache.len.. ; returns last-position logits [B, V]."""
@@ -145,7 +152,7 @@ def forward_cached(model, ids: torch.Tensor, cache: KVCache) -> torch.Tensor:
         K = _rep_kv(cache.k[i][:, :, :p0 + T].float(), cfg)
         Vv = _rep_kv(cache.v[i][:, :, :p0 + T].float(), cfg)
         qh = q.to(dt).float().transpose(1, 2)  # [B, nh, T, hd]
-        s = torch.matmul(qh, K.transpose(-2, -1)) * scale
+        s = _cap_scores(torch.matmul(qh, K.transpose(-2, -1)) * scale, cfg)
         W = _layer_window(cfg, i)
         if T > 1 or (W is not None and W < p0 + T):
             qpos = torch.arange(p0, p0 + T, device=ids.device)[:, None]
@@ -245,6 +252,8 @@ class DecodeGraph:
             wkw = {"window": W} if W else {}  # a global layer calls the kernels it always did
             if getattr(w, "sk", None) is not None:  # attention sinks: the kernels' sink= forms
                 wkw["sink"] = w.sk
+            if getattr(cfg, "attn_softcap", None) is not None:  # a capped model: the CAP kernels
+                wkw["softcap"] = cfg.attn_softcap
             if self.kind == "gqa":
                 ops.dec_norm_qkv_gqa(self.h, w.ln1, eng.eps, w.wqkv, cos_t, sin_t, self.pos, self.qb, cache.k[i],
                                      cache.v[i], cfg.num_heads, cfg.num_kv_heads)
@@ -298,7 +307,7 @@ class DecodeGraph:
             cache.k[i].index_copy_(2, self.pos, k.transpose(1, 2).to(dt))
             cache.v[i].index_copy_(2, self.pos, v.transpose(1, 2).to(dt))
             qh = q.to(dt).transpose(1, 2)  # [B, nh, 1, hd]; bf16 GEMVs straight on the bf16 cache
-            s_ = torch.matmul(qh, _rep_kv(cache.k[i], cfg).transpose(-2, -1)).float() * scale
+            s_ = _cap_scores(torch.matmul(qh, _rep_kv(cache.k[i], cfg).transpose(-2, -1)).float() * scale, cfg)
             pr = _sink_softmax(s_.masked_fill(masked, float("-inf")), w)
             o = torch.matmul(pr.to(dt), _rep_kv(cache.v[i], cfg)).transpose(1, 2).reshape(B, 1, nh * hd)
             h = h + torch.matmul(o, w.wo.t()).float()

@@ -65,6 +65,11 @@ class GPTConfig:
     # cap * tanh(lm_head(norm(h)) / cap), in training, evaluation and generation alike.  None = off.
     logit_softcap: Optional[float] = None
 
+    # Attention-score soft-capping (the other half of Gemma-2's rule, cap 50 there; Grok-1 too):
+    # every layer's scaled scores are cap * tanh(scale * q.k / cap) before the masks and the
+    # softmax; masked keys stay at -inf and a sink is not capped.  None = off.
+    attn_softcap: Optional[float] = None
+
     # Sliding-window (local) attention: query q sees key k iff q - W < k <= q, W keys with its
     # own (the Mistral / Gemma rule).  With sliding_window_pattern = N, layer i (0-based) is
     # global (plain causal) iff (i + 1) % N == 0 (Gemma-3's rule); unset, every layer is windowed.
@@ -103,6 +108,11 @@ class GPTConfig:
             if isinstance(c, bool) or not isinstance(c, (int, float)) or not math.isfinite(c) or c <= 0:
                 raise ValueError(f"logit_softcap ({c!r}) must be a finite float > 0")
             self.logit_softcap = float(c)
+        if self.attn_softcap is not None:
+            c = self.attn_softcap
+            if isinstance(c, bool) or not isinstance(c, (int, float)) or not math.isfinite(c) or c <= 0:
+                raise ValueError(f"attn_softcap ({c!r}) must be a finite float > 0")
+            self.attn_softcap = float(c)
 
     # ------------------------------------------------------------------ presets
     @classmethod
@@ -210,7 +220,7 @@ class GPTConfig:
             del d["qk_norm"]
         if not self.attention_sinks:  # ... and configs without attention sinks
             del d["attention_sinks"]
-        for k in ("sliding_window", "sliding_window_pattern", "logit_softcap"):  # ... and unwindowed / uncapped ones
+        for k in ("sliding_window", "sliding_window_pattern", "logit_softcap", "attn_softcap"):  # ... and unwindowed / uncapped ones
             if d[k] is None:
                 del d[k]
         return d
@@ -226,7 +236,7 @@ class GPTConfig:
             state.pop("qk_norm", None)
         if not state.get("attention_sinks"):
             state.pop("attention_sinks", None)
-        for k in ("sliding_window", "sliding_window_pattern", "logit_softcap"):
+        for k in ("sliding_window", "sliding_window_pattern", "logit_softcap", "attn_softcap"):
             if state.get(k) is None:
                 state.pop(k, None)
         return state
@@ -240,6 +250,7 @@ class GPTConfig:
         self.__dict__.setdefault("sliding_window", None)
         self.__dict__.setdefault("sliding_window_pattern", None)
         self.__dict__.setdefault("logit_softcap", None)
+        self.__dict__.setdefault("attn_softcap", None)
 
     @classmethod
     def from_dict(cls, d: Dict[str, Any]) -> "GPTConfig":

@@ -289,9 +289,15 @@ class GPTEngine:
         # softcap= (the CAP kernels), evaluation runs lm_head GEMM + CAP cross-entropy in row chunks, and
         # returned logits are capped
         self.softcap = float(getattr(cfg, "logit_softcap", None) or 0.0)
+        # attention-score soft cap (cfg.attn_softcap): every attention forward and backward takes
+        # softcap= (the CAP kernels rebuild tanh from q and k, so nothing new is kept); an uncapped
+        # model passes no keyword
+        self.attn_softcap = getattr(cfg, "attn_softcap", None)
         if getattr(ops, "backend", "") == "hip":  # the GPU routes; the reference ops have every feature
             attn_routes.check_attention_features("cuda", cfg.head_dim, act_dtype, attn_routes.config_features(cfg),
                                                  self.packed_qkv)
+            if self.attn_softcap is not None:
+                attn_routes.check_score_softcap("cuda", cfg.head_dim, act_dtype, cap=self.attn_softcap)
             from ..ops import hip_f32
             if self.softcap and act_dtype == torch.float32 and "logit_softcap" in hip_f32.REFUSED_FEATURES:
                 raise NotImplementedError("this model on the GPU: fp32 activations have no final-logit soft-capping "
@@ -528,7 +534,8 @@ class GPTEngine:
         ``nkv=``: grouped-query attention on the packed layout (the split one shows it in k's
         shape; MHA passes no keyword, so its calls are what they were).  ``sink=``, and
         ``dsink=`` in the backward: gr.sk is shared with the other micro-steps like gr.ln1 /
-        gr.ln2, so the accumulation lies between wait_prev(i) and mark(i)."""
+        gr.ln2, so the accumulation lies between wait_prev(i) and mark(i).  ``softcap=``: a capped
+        model's attention-score cap, in both directions."""
         W = self.cfg.layer_window(i) if st.win is not None else None
         kw = {"doc": st.win, "window": W} if W is not None else {"doc": st.doc} if st.doc is not None else {}
         if self.packed_qkv:
@@ -537,6 +544,8 @@ class GPTEngine:
             kw["sink"] = w.sk
             if grads is not None:
                 kw["dsink"] = grads.sk
+        if self.attn_softcap is not None:
+            kw["softcap"] = self.attn_softcap
         return kw
 
     def _attn_mask_async(self, B, S, p, key, dev, window=None):

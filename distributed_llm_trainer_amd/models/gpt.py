@@ -111,6 +111,9 @@ class CausalSelfAttention(nn.Module):
         self.resid_dropout = nn.Dropout(config.dropout)
         self.rotary_emb = RotaryPositionEmbedding(self.head_dim, config.max_seq_len)
         self.use_flash = config.use_flash_attention
+        # Attention-score soft-capping (config.attn_softcap): fp32 scaled scores -> cap * tanh(s / cap)
+        # before the masks; SDPA cannot express it, so a capped model takes the explicit formula
+        self.attn_softcap = getattr(config, "attn_softcap", None)
 
     def forward(self, hidden_states: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 doc_hidden: Optional[torch.Tensor] = None):
@@ -133,14 +136,25 @@ class CausalSelfAttention(nn.Module):
             pos = torch.arange(S, device=hidden_states.device)
             out_of_window = (pos[None, :] <= pos[:, None] - self.window)[None, None]
             doc_hidden = out_of_window if doc_hidden is None else doc_hidden | out_of_window
+        cap = self.attn_softcap
         if self.attention_sinks:  # SDPA cannot express the sink: the explicit formula in either setting
             scores = torch.matmul(q, k.transpose(-2, -1)) / math.sqrt(self.head_dim)
+            if cap is not None:  # real scores only: the masks below still write -inf, the sink is not capped
+                scores = (cap * torch.tanh(scores.float() / cap)).to(scores.dtype)
             mask = torch.triu(torch.ones(S, S, device=hidden_states.device, dtype=torch.bool), diagonal=1)
             mask = mask[None, None] if doc_hidden is None else mask[None, None] | doc_hidden
             scores = scores.masked_fill(mask, float("-inf"))
             # the sink is one more score column (not scaled, per query head, no value row)
             sink = self.sinks.float().view(1, self.num_heads, 1, 1).expand(B, -1, S, 1)
             probs = F.softmax(torch.cat([scores.float(), sink], dim=-1), dim=-1)[..., :S].to(scores.dtype)
+            out = self.attn_dropout(probs) @ v
+        elif cap is not None:  # SDPA cannot express the cap either
+            scores = torch.matmul(q, k.transpose(-2, -1)) / math.sqrt(self.head_dim)
+            scores = cap * torch.tanh(scores.float() / cap)
+            mask = torch.triu(torch.ones(S, S, device=hidden_states.device, dtype=torch.bool), diagonal=1)
+            mask = mask[None, None] if doc_hidden is None else mask[None, None] | doc_hidden
+            scores = scores.masked_fill(mask, float("-inf"))
+            probs = F.softmax(scores, dim=-1, dtype=torch.float32).to(q.dtype)
             out = self.attn_dropout(probs) @ v
         elif self.use_flash and doc_hidden is not None:
             causal = torch.tril(torch.ones(S, S, device=hidden_states.device, dtype=torch.bool))

@@ -101,10 +101,10 @@ def _rows_padded(t, B, S, nh, hd, Dp):
     return out
 
 
-def _fwd_pad(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask, dt, doc=None, sink=None):
+def _fwd_pad(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask, dt, doc=None, sink=None, softcap=None):
     from . import hip
     o_p, aux = hip.attention_fwd(q4p[0], q4p[1], q4p[2], p, key, True, store_mask=store_mask, mask=mask,
-                                 scale=1.0 / math.sqrt(hd), doc=doc, sink=sink)
+                                 scale=1.0 / math.sqrt(hd), doc=doc, sink=sink, softcap=softcap)
     H = nh * hd
     o = torch.empty(B * S, H, dtype=dt, device=q4p.device) if out is None else out
     if o.dtype != dt or not o.is_contiguous() or o.numel() != B * S * H:
@@ -113,12 +113,12 @@ def _fwd_pad(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask, dt, doc=None,
     return o, aux
 
 
-def _bwd_pad(q4p, o, do, aux, B, S, nh, hd, Dp, p, key, doc=None, sink=None, dsink=None):
+def _bwd_pad(q4p, o, do, aux, B, S, nh, hd, Dp, p, key, doc=None, sink=None, dsink=None, softcap=None):
     """(dq, dk, dv) [3, B, nh, S, hd] from the padded flash backward."""
     from . import hip
     dq, dk, dv = hip.attention_bwd(q4p[0], q4p[1], q4p[2], _rows_padded(o, B, S, nh, hd, Dp),
                                    _rows_padded(do, B, S, nh, hd, Dp), aux, p, key, scale=1.0 / math.sqrt(hd),
-                                   doc=doc, sink=sink, dsink=dsink)
+                                   doc=doc, sink=sink, dsink=dsink, softcap=softcap)
     g = torch.empty(3, B, nh, S, hd, dtype=dq.dtype, device=dq.device)
     for j, t in enumerate((dq, dk, dv)):
         _relayout16(t, (nh * S * Dp, Dp, S * Dp), g[j], (nh * S * hd, hd, S * hd), B, S, nh, hd, 1)
@@ -287,15 +287,19 @@ def _rope_bwd(dq, dk, dv, cos, sin, out=None):
 
 
 # ----------------------------------------------------------------------- entry points
-def _enter(dtype, hd: int, B: int, S: int, device, doc, window, sink):
+def _enter(dtype, hd: int, B: int, S: int, device, doc, window, sink, softcap=None):
     """(padded head_dim or None, bounds) of an entry point: whichever of ``doc`` / ``window``
-    / ``sink`` was passed must exist on the route this head takes here (no silent fallback),
+    / ``sink`` / ``softcap`` was passed must exist on the route this head takes here (no silent
+    fallback: the GEMM-formulated and fp32 routes have none of them, the zero-padded 16-bit route
+    hands them to the flash kernels),
     and the window is folded into the bounds the padded flash kernels take (their keep bits
     stay the full ones: a superset of what the window reads)."""
     rt = attn_routes.route(dtype, hd, flash=False)
     for feature, arg in (("sinks", sink), ("window", window), ("doc", doc)):
         if arg is not None:
             attn_routes.require(rt, feature, "attn_gemm")
+    if softcap is not None:
+        attn_routes.require_score_softcap(rt, "attn_gemm")
     if window is not None:
         from . import hip
         doc = hip._window_doc(window, doc, B, S, device, "attn")[1]
@@ -303,16 +307,16 @@ def _enter(dtype, hd: int, B: int, S: int, device, doc, window, sink):
 
 
 def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=True, doc=None, window=None,
-                         sink=None):
+                         sink=None, softcap=None):
     hd = qkv.shape[1] // (3 * nh)
-    Dp, doc = _enter(qkv.dtype, hd, B, S, qkv.device, doc, window, sink)
+    Dp, doc = _enter(qkv.dtype, hd, B, S, qkv.device, doc, window, sink, softcap)
     H, ld = nh * hd, qkv.stride(0)
     if Dp and qkv.dtype == torch.float32:
         q4p = _pad32(hip_f32._packed_ptrs(qkv, 3, H), (S * ld, ld, hd), B, S, nh, hd, Dp, qkv.device)
         return _fwd_pad32(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask)
     if Dp:
         q4p = _pad16(qkv, (S * ld, ld, hd), B, S, nh, hd, Dp, 3, nh * hd)
-        return _fwd_pad(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask, qkv.dtype, doc, sink)
+        return _fwd_pad(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask, qkv.dtype, doc, sink, softcap)
     _need_fit(B, nh, S, hd)
     if use16(qkv.dtype, B, nh, S, hd):
         q4, k4, v4 = _heads16(qkv, B, S, nh, hd, 3)
@@ -324,9 +328,9 @@ def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=
 
 
 def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, doc=None, window=None, sink=None,
-                         dsink=None):
+                         dsink=None, softcap=None):
     hd = qkv.shape[1] // (3 * nh)
-    Dp, doc = _enter(qkv.dtype, hd, B, S, qkv.device, doc, window, sink)
+    Dp, doc = _enter(qkv.dtype, hd, B, S, qkv.device, doc, window, sink, softcap)
     H, ld = nh * hd, qkv.stride(0)
     if Dp and qkv.dtype == torch.float32:
         q4p = _pad32(hip_f32._packed_ptrs(qkv, 3, H), (S * ld, ld, hd), B, S, nh, hd, Dp, qkv.device)
@@ -335,7 +339,7 @@ def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, 
         return _rope_bwd(g[0], g[1], g[2], cos, sin, out=out)
     if Dp:
         q4p = _pad16(qkv, (S * ld, ld, hd), B, S, nh, hd, Dp, 3, nh * hd)
-        g = _bwd_pad(q4p, o, do, aux, B, S, nh, hd, Dp, p, key, doc, sink, dsink)
+        g = _bwd_pad(q4p, o, do, aux, B, S, nh, hd, Dp, p, key, doc, sink, dsink, softcap)
         del q4p
         return _rope_bwd(g[0], g[1], g[2], cos, sin, out=out)
     _need_fit(B, nh, S, hd)
@@ -353,11 +357,11 @@ def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, 
 
 
 def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=None, doc=None, window=None,
-                  sink=None):
+                  sink=None, softcap=None):
     if not causal:
         raise NotImplementedError("only causal attention is implemented (the model is a causal LM)")
     B, nh, S, hd = q.shape
-    Dp, doc = _enter(q.dtype, hd, B, S, q.device, doc, window, sink)
+    Dp, doc = _enter(q.dtype, hd, B, S, q.device, doc, window, sink, softcap)
     hm = (nh * S * hd, hd, S * hd)
     if Dp and q.dtype == torch.float32:
         ts = [t.contiguous() for t in (q, k, v)]
@@ -365,7 +369,7 @@ def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=
         return _fwd_pad32(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask)
     if Dp:
         q4p = torch.stack([_pad16(t.contiguous(), hm, B, S, nh, hd, Dp, 1, 0)[0] for t in (q, k, v)])
-        return _fwd_pad(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask, q.dtype, doc, sink)
+        return _fwd_pad(q4p, B, S, nh, hd, Dp, p, key, out, mask, store_mask, q.dtype, doc, sink, softcap)
     _need_fit(B, nh, S, hd)
     if use16(q.dtype, B, nh, S, hd):
         return _fwd16(q.contiguous(), k.contiguous(), v.contiguous(), B, nh, S, hd, p, key, out, mask, store_mask)
@@ -374,9 +378,10 @@ def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=
     return _narrow(o32, q.dtype, out), aux
 
 
-def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, doc=None, window=None, sink=None, dsink=None):
+def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, doc=None, window=None, sink=None, dsink=None,
+                  softcap=None):
     B, nh, S, hd = q.shape
-    Dp, doc = _enter(q.dtype, hd, B, S, q.device, doc, window, sink)
+    Dp, doc = _enter(q.dtype, hd, B, S, q.device, doc, window, sink, softcap)
     hm = (nh * S * hd, hd, S * hd)
     if Dp and q.dtype == torch.float32:
         ts = [t.contiguous() for t in (q, k, v)]
@@ -384,7 +389,7 @@ def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, doc=None, window=Non
         return tuple(_bwd_pad32(q4p, o, do, aux, B, S, nh, hd, Dp, p, key).unbind(0))
     if Dp:
         q4p = torch.stack([_pad16(t.contiguous(), hm, B, S, nh, hd, Dp, 1, 0)[0] for t in (q, k, v)])
-        return tuple(_bwd_pad(q4p, o, do, aux, B, S, nh, hd, Dp, p, key, doc, sink, dsink).unbind(0))
+        return tuple(_bwd_pad(q4p, o, do, aux, B, S, nh, hd, Dp, p, key, doc, sink, dsink, softcap).unbind(0))
     _need_fit(B, nh, S, hd)
     if use16(q.dtype, B, nh, S, hd):
         return _bwd16(q.contiguous(), k.contiguous(), v.contiguous(), o, do, aux, B, nh, S, hd, p, key)

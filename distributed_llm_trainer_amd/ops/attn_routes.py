@@ -2,19 +2,21 @@
 
 One table for every place that asks "does this model's attention have feature X":
 
-===========================  ======================================  ===  ======  =====  ===  =======
-route                        taken when                              doc  window  sinks  gqa  qk_norm
-===========================  ======================================  ===  ======  =====  ===  =======
-16-bit flash                 bf16 / fp16, head_dim 64 or 128         yes  yes     yes    yes  yes
-zero-padded 16-bit flash     bf16 / fp16, other head_dim < 128,      yes  yes     yes    no   no
+===========================  ======================================  ===  ======  =====  ===  =======  ===
+route                        taken when                              doc  window  sinks  gqa  qk_norm  cap
+===========================  ======================================  ===  ======  =====  ===  =======  ===
+16-bit flash                 bf16 / fp16, head_dim 64 or 128         yes  yes     yes    yes  yes      yes
+zero-padded 16-bit flash     bf16 / fp16, other head_dim < 128,      yes  yes     yes    no   no       yes
                              ``DLT_ATTN_PAD`` on
-GEMM-formulated              bf16 / fp16, everything else            no   no      no     no   no
-fp32 (flash, zero-padded     fp32, any head_dim                      no   no      no     no   no
+GEMM-formulated              bf16 / fp16, everything else            no   no      no     no   no       no
+fp32 (flash, zero-padded     fp32, any head_dim                      no   no      no     no   no       no
 flash, GEMM-formulated)
-===========================  ======================================  ===  ======  =====  ===  =======
+===========================  ======================================  ===  ======  =====  ===  =======  ===
 
-gqa and qk_norm also need the packed QKV layout on the GPU.  The CPU and the reference ops
-have every feature.  Pure Python: nothing here loads the HIP library.
+gqa and qk_norm also need the packed QKV layout on the GPU.  cap = attention-score
+soft-capping (``attn_softcap``): not one of :data:`FEATURES` (it is a number, not a switch, and
+has no config key of the on/off kind); :func:`check_score_softcap` is its check.  The CPU and
+the reference ops have every feature.  Pure Python: nothing here loads the HIP library.
 """
 from __future__ import annotations
 
@@ -91,3 +93,44 @@ def config_features(cfg) -> frozenset:
     on = {"gqa": cfg.num_kv_heads != cfg.num_heads, "qk_norm": getattr(cfg, "qk_norm", False),
           "sinks": getattr(cfg, "attention_sinks", False), "window": getattr(cfg, "sliding_window", None) is not None}
     return frozenset(f for f, v in on.items() if v)
+
+
+# Largest cap the CAP kernels take.  Their exponent constant is cap * log2(e), and the DOC /
+# window forward multiplies it with M_DEAD = -1e30 (the running max of a row that has seen no live
+# key yet): the product must stay finite in fp32.  2^16 leaves three orders of magnitude, and a
+# cap of that size no longer caps anything (Gemma-2 uses 50).
+SCORE_SOFTCAP_MAX = 65536.0
+
+
+def check_score_softcap_range(cap: float, where: str) -> None:
+    """Raises ValueError for a cap the CAP kernels of the GPU routes do not take (> SCORE_SOFTCAP_MAX)."""
+    if cap > SCORE_SOFTCAP_MAX:
+        raise ValueError(f"{where}: the GPU attention kernels take a cap of at most {SCORE_SOFTCAP_MAX:g}, got {cap!r}")
+
+
+def has_score_softcap(rt: Route) -> bool:
+    """Route ``rt`` has the CAP kernels (attention-score soft-capping, ``attn_softcap``): the
+    16-bit flash route and its zero-padded form."""
+    return rt.kind != "gemm" and rt.dtype != torch.float32
+
+
+def require_score_softcap(rt: Route, where: str) -> None:
+    """Raises NotImplementedError unless route ``rt`` has the CAP kernels (no silent fallback, and
+    no silently ignored ``softcap=``)."""
+    if not has_score_softcap(rt):
+        raise NotImplementedError(
+            f"{where}: the {rt.name} attention route (head_dim {rt.head_dim}, {rt.dtype}) has no attention-score "
+            f"soft-capping (attn_softcap); use bf16 or fp16 activations with head_dim <= 128")
+
+
+def check_score_softcap(device, head_dim: int, act_dtype, where: str = "this model on the GPU", cap=None) -> None:
+    """Raises NotImplementedError when the attention route of (``act_dtype``, ``head_dim``) on
+    ``device`` cannot cap the scores, and ValueError when ``cap`` is given and beyond what its CAP
+    kernels take (:data:`SCORE_SOFTCAP_MAX`).  Called where a capped model is configured
+    (``enable_engine``), so the error comes before the first step.  The CPU and the reference
+    ops cap on every route."""
+    if torch.device(device).type != "cuda" or os.environ.get("DLT_ALLOW_REFERENCE_ON_GPU") == "1":
+        return
+    require_score_softcap(route(act_dtype, head_dim), where)
+    if cap is not None:
+        check_score_softcap_range(float(cap), where + ": attn_softcap")

@@ -1,7 +1,9 @@
 // Device code and launch arguments shared by the flash-attention translation units:
-// attention.hip (forward, backward, keep bits, the C entry points) and attention_sink.hip (the
-// SINK forms of the forward, a translation unit of their own so that attention.hip's kernels
-// compile exactly as they did without them).  See attention.hip for the design.
+// attention.hip (forward, backward, keep bits, the C entry points), attention_sink.hip (the
+// SINK forms of the forward) and attention_cap.hip (the CAP forms of the forward and the
+// backward: attention-score soft-capping), translation units of their own so that
+// attention.hip's kernels compile exactly as they did without them.  The kernel bodies are
+// the fragments attention_fwd_body.h and attention_bwd_body.h.  See attention.hip for the design.
 #pragma once
 #include "common.h"
 
@@ -173,6 +175,23 @@ __device__ __forceinline__ floatx16_t mfma(const bf16x8_t& a, const bf16x8_t& b,
 
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
+// Attention-score soft-capping (the CAP kernels, attention_cap.hip): the raw product s = q.k
+// becomes t = tanh(scale s / cap), in loss.hip's formulation for the final cap:
+//   a = exp2(-|s| cap_k), cap_k = 2 log2(e) scale / cap  (= e^(-2|x|/cap), in (0, 1])
+//   r = 1 / (1 + a),  t = copysign((1 - a) r, s),  1 - t^2 = 4 a r^2.
+// Nothing overflows: |s| -> inf gives a = 0, t = +-1 and a derivative of exactly 0, and the
+// derivative is a product, never 1 - t*t (which cancels where the cap bites).
+__device__ __forceinline__ float cap_tanh(float s, float cap_k, float& dt2) {
+  const float a = fast_exp2(-fabsf(s) * cap_k);
+  const float r = __builtin_amdgcn_rcpf(1.f + a);
+  dt2 = 4.f * a * r * r;
+  return copysignf((1.f - a) * r, s);
+}
+__device__ __forceinline__ float cap_tanh(float s, float cap_k) {
+  const float a = fast_exp2(-fabsf(s) * cap_k);
+  return copysignf((1.f - a) * __builtin_amdgcn_rcpf(1.f + a), s);
+}
+
 // row (within a 32x32 tile) of accumulator register i for lane-half h
 __device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
 
@@ -315,10 +334,10 @@ struct FwdState {
   float m, l;  // running max (raw score units) and per-lane partial row sum
 };
 
-template <bool MASK, bool DROP, int HK, int D, bool DOC = false>
+template <bool MASK, bool DROP, int HK, int D, bool DOC = false, bool CAP = false>
 __device__ __forceinline__ void fwd_tile(FwdState<D>& fs, const bf16_t* Kt, const bf16_t* Vt,
                                          const bf16x8_t (&qf)[D / 16], int k0, int qa, int S, int lane, float c_log2,
-                                         uint2 mw, int lo = 0) {
+                                         uint2 mw, int lo = 0, float cap_k = 0.f) {
   // One 64-key tile as ONE online-softmax step: S = K.Q^T of both 32-key halves first
   // (two independent MFMA chains), one row max / rescale decision for the tile, then
   // per half exp -> dropout -> P.V; the second half's softmax VALU runs while the
@@ -366,6 +385,13 @@ __device__ __forceinline__ void fwd_tile(FwdState<D>& fs, const bf16_t* Kt, cons
       sacc[1] = mfma<HK>(kf[1][s], qf[s], sacc[1]);
     }
 #endif
+  }
+  if constexpr (CAP) {  // s -> t = tanh(scale s / cap) in place; c_log2 is cap * log2(e), so m, l and lse
+                        // below are those of the capped scores; masked keys go to -inf after, never -cap
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) sacc[t][i] = cap_tanh(sacc[t][i], cap_k);
   }
   if (MASK) {
 #pragma unroll
@@ -538,6 +564,9 @@ struct dlt_attn_args {
   float scale, dscale;
   uint32_t key, thr;  // thr != 0: dropout on
   int gen_mask;       // forward; 0: the keep bits are already in `mask` (dlt_attn_dropout_mask)
+  // attention-score soft-capping: scores = softcap * tanh(scale q.k / softcap) before the masks
+  // (the CAP kernels, attention_cap.hip); 0 = off.  It fills the alignment hole before `stride`
+  float softcap;
   struct {
     dlt_attn_stride q, kv, dq, dkv;
   } stride;
@@ -551,6 +580,11 @@ struct dlt_attn_args {
 static_assert(sizeof(dlt_attn_args) == 248, "dlt_attn_args changed: update _AttnArgs in ops/hip.py");
 static inline bool attn_stride_ok(const dlt_attn_stride& s, int m) { return !(s.r % m || s.h % m || s.b % m); }
 
+// attention_cap.hip: launch the CAP forms (a->softcap > 0) after dlt_attn_fwd's / dlt_attn_bwd's
+// argument checks and keep-bit generation.  The forward covers a->sink too; the backward leaves
+// the sink gradient (k_attn_sink_bwd, unchanged by the cap) to dlt_attn_bwd.
+int attn_fwd_cap_launch(const dlt_attn_args* a, hipStream_t st);
+int attn_bwd_cap_launch(const dlt_attn_args* a, hipStream_t st);
 // attention_sink.hip: launches the SINK form of the forward (a->sink set) after dlt_attn_fwd's
 // argument checks and keep-bit generation
 int attn_fwd_sink_launch(const dlt_attn_args* a, hipStream_t st);

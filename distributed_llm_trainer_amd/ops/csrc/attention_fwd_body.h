@@ -6,12 +6,15 @@
 // dscale, in_bs, in_hs, in_rs, xcd_map, dlo, G, kv_bs, kv_hs, kv_rs, the template parameters
 // DROP, HK, D, DOC, GQA, and in scope
 //   constexpr bool SINK;  const float* sink;   // fp32 [nh], read only when SINK
+//   constexpr bool CAP;   float cap_k;         // 2 log2(e) scale / cap, read only when CAP
+// CAP (attention_cap.hip): scores cap * tanh(scale q.k / cap); fwd_tile turns the accumulator into
+// the tanh in place and c_log2 is cap * log2(e), so everything here runs unchanged in those units.
 // SINK: one more logit per query head in the softmax denominator (natural-log units, not
 // scaled, no value row: p_j = exp(s_j) / (sum_j exp(s_j) + exp(sink))); it enters in the
 // epilogue only, see there.
-  static_assert(std::is_same<decltype(SINK), const bool>::value && (D == 64 || D == 128) && (HK == 0 || HK == 1),
+  static_assert(std::is_same<std::remove_const_t<decltype(SINK)>, bool>::value && (D == 64 || D == 128) && (HK == 0 || HK == 1),
                 "attention_fwd_body.h: include it inside a kernel template <bool DROP, int HK, int D, bool DOC, bool GQA> "
-                "with `constexpr bool SINK` and `const float* sink` in scope");
+                "with a compile-time `bool SINK` and `const float* sink` in scope");
   __shared__ __attribute__((aligned(16))) bf16_t lds[2 * 2 * KVB * D];  // [buf][K|V][64][D]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -92,9 +95,9 @@
       const bf16_t* Vt = Kt + KVB * D;
       const int k0 = kb * KVB;
       if (!MASKED)
-        fwd_tile<false, DROP, HK, D>(fs, Kt, Vt, qf, k0, qa, S, lane, c_log2, mw_cur);
+        fwd_tile<false, DROP, HK, D, false, CAP>(fs, Kt, Vt, qf, k0, qa, S, lane, c_log2, mw_cur, 0, cap_k);
       else if (k0 <= q0 + 31 && (!DOC || k0 + KVB > lo_w))  // DOC: not wholly below this wave's documents
-        fwd_tile<true, DROP, HK, D, DOC>(fs, Kt, Vt, qf, k0, qa, S, lane, c_log2, mw_cur, lo_q);
+        fwd_tile<true, DROP, HK, D, DOC, CAP>(fs, Kt, Vt, qf, k0, qa, S, lane, c_log2, mw_cur, lo_q, cap_k);
       mw_cur = mw_next;
       FWD_T(tb);
       tile_barrier();

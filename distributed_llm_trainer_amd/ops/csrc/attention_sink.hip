@@ -19,6 +19,8 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_attn_fwd_sink(
   // the fragment reads this kernel's parameters and template arguments by name (its header
   // lists them): they are k_attn_fwd's, in its order, plus `sink`
   constexpr bool SINK = true;
+  constexpr bool CAP = false;
+  constexpr float cap_k = 0.f;
 #include "attention_fwd_body.h"
 }
 

@@ -232,6 +232,14 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_norm_qkv(const float* __restrict
   }
 }
 
+// Attention-score soft-capping of the decode attention kernels (their CAP forms): the fp32 score
+// s = scale q.k becomes cap * tanh(s / cap), cap_k = 2 log2(e) / cap.
+__device__ __forceinline__ float dec_cap_score(float s, float cap, float cap_k) {
+  // loss.hip's formulation: a = e^(-2|s|/cap) in (0, 1], tanh = copysign((1 - a) / (1 + a), s)
+  const float a = __builtin_amdgcn_exp2f(-fabsf(s) * cap_k);
+  return copysignf(cap * ((1.f - a) * __builtin_amdgcn_rcpf(1.f + a)), s);
+}
+
 // grid (B * nh): one (b, head).  q [B, H] bf16 (head-major 64-blocks), caches [B, nh, maxS, 64].
 // Scores in fp32 (lane = key), softmax over keys 0..pos, then o (lane = dim) summed across
 // the 4 waves in LDS.
@@ -241,11 +249,14 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_norm_qkv(const float* __restrict
 // sink (nullable, fp32 [nh]): the head's attention-sink logit, one more term of the softmax
 // denominator with no value row.  It joins the max after the reduction and the sum before the
 // reciprocal; a null pointer leaves every instruction's inputs as they were.
-template <bool WIN = false>
+// CAP (attention-score soft-capping): the fp32 score becomes cap * tanh(scale q.k / cap) before
+// it enters the max and the softmax (dec_cap_score); the sink is not capped.
+template <bool WIN = false, bool CAP = false>
 __global__ __launch_bounds__(DEC_NT) void k_dec_attn(const bf16_t* __restrict__ q, const bf16_t* __restrict__ kc,
                                                      const bf16_t* __restrict__ vc, const long* __restrict__ posp,
                                                      bf16_t* __restrict__ o, int H, int nh, int maxS, float scale,
-                                                     int win = 0, const float* __restrict__ sink = nullptr) {
+                                                     int win = 0, const float* __restrict__ sink = nullptr,
+                                                     float cap = 0.f, float cap_k = 0.f) {
   extern __shared__ __attribute__((aligned(16))) char dsm[];
   float* sc = reinterpret_cast<float*>(dsm);       // [maxS] scores -> probabilities (WIN: [min(win, maxS)])
   float* red = sc + (WIN ? min(win, maxS) : maxS); // [8]
@@ -275,6 +286,7 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_attn(const bf16_t* __restrict__ 
       for (int e = 0; e < 8; ++e) s = fmaf(qv[c * 8 + e], bf2f(t.v[e]), s);
     }
     s *= scale;
+    if constexpr (CAP) s = dec_cap_score(s, cap, cap_k);
     sc[j] = s;
     mx = fmaxf(mx, s);
   }
@@ -349,12 +361,15 @@ constexpr int GQA_GMAX = 16;  // query heads per workgroup (128 accumulator regi
 // sink (nullable, fp32 [nh], per QUERY head): with NS == 1 it joins each head's max after the
 // reduction and its sum before the reciprocal, as in k_dec_attn; with NS > 1 the chunk
 // workgroups leave it out and k_dec_attn_combine adds it once.  Null: nothing changes.
-template <int GT, bool WIN = false>
+// CAP: as in k_dec_attn; the partials of NS > 1 are those of the capped scores, so
+// k_dec_attn_combine is unchanged.
+template <int GT, bool WIN = false, bool CAP = false>
 __global__ __launch_bounds__(DEC_NT) void k_dec_attn_gqa(const bf16_t* __restrict__ q, const bf16_t* __restrict__ kc,
                                                          const bf16_t* __restrict__ vc, const long* __restrict__ posp,
                                                          bf16_t* __restrict__ o, float* __restrict__ ws, int H, int nh,
                                                          int nkv, int maxS, int NS, int C, float scale, int win = 0,
-                                                         const float* __restrict__ sink = nullptr) {
+                                                         const float* __restrict__ sink = nullptr, float cap = 0.f,
+                                                         float cap_k = 0.f) {
   extern __shared__ __attribute__((aligned(16))) char dsm[];
   float* red = reinterpret_cast<float*>(dsm);  // [2][4][GT] per-wave max, sum
   float* oacc = red + 8 * GT;                  // [4][GT][64]
@@ -434,6 +449,7 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_attn_gqa(const bf16_t* __restric
 #pragma unroll
     for (int g = 0; g < GT; ++g) {
       a[g] *= scale;
+      if constexpr (CAP) a[g] = dec_cap_score(a[g], cap, cap_k);
       sc[g * C + j] = a[g];
       mx[g] = fmaxf(mx[g], a[g]);
     }
@@ -1216,8 +1232,9 @@ static int dec_attn_chunk(int maxS, int NS) { return (maxS + NS - 1) / NS; }
 // divide min(window, maxS) keys, anchored at the window (k_dec_attn_gqa<GT, true>).
 static int dec_attn_gqa_launch(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const long* pos, bf16_t* o,
                                float* ws, int B, int H, int nh, int nkv, int maxS, int NS, float scale, int window,
-                               hipStream_t st, const float* sink = nullptr) {
+                               hipStream_t st, const float* sink = nullptr, float cap = 0.f) {
   if (B < 1 || H != nh * 64 || nkv < 1 || nh % nkv || maxS < 1 || window < 0) return -1;
+  const float cap_k = cap > 0.f ? 2.f * 1.44269504088896340736f / cap : 0.f;
   if ((NS != 1 && NS != 2 && NS != 4 && NS != 8) || (NS > 1 && !ws)) return -1;
   const int G = nh / nkv, Gw = G < GQA_GMAX ? G : GQA_GMAX, GS = (G + GQA_GMAX - 1) / GQA_GMAX;
   const int C = dec_attn_chunk(window > 0 && window < maxS ? window : maxS, NS);
@@ -1230,7 +1247,13 @@ static int dec_attn_gqa_launch(const bf16_t* q, const bf16_t* kc, const bf16_t* 
   const int grid = B * nkv * GS * NS;
 #define L(GG)                                                                                                   \
   case GG:                                                                                                      \
-    if (window > 0)                                                                                             \
+    if (cap > 0.f && window > 0)                                                                                \
+      k_dec_attn_gqa<GG, true, true><<<grid, DEC_NT, lds, st>>>(q, kc, vc, pos, o, ws, H, nh, nkv, maxS, NS, C, \
+                                                                scale, window, sink, cap, cap_k);               \
+    else if (cap > 0.f)                                                                                         \
+      k_dec_attn_gqa<GG, false, true><<<grid, DEC_NT, lds, st>>>(q, kc, vc, pos, o, ws, H, nh, nkv, maxS, NS, C, \
+                                                                 scale, 0, sink, cap, cap_k);                   \
+    else if (window > 0)                                                                                        \
       k_dec_attn_gqa<GG, true><<<grid, DEC_NT, lds, st>>>(q, kc, vc, pos, o, ws, H, nh, nkv, maxS, NS, C,      \
                                                           scale, window, sink);                                \
     else                                                                                                        \
@@ -1273,6 +1296,15 @@ DLT_API int dlt_dec_attn_gqa_sink(const bf16_t* q, const bf16_t* kc, const bf16_
   return dec_attn_gqa_launch(q, kc, vc, pos, o, ws, B, H, nh, nkv, maxS, NS, scale, window, st, sink);
 }
 
+// The grouped-query step with attention-score soft-capping: scores cap * tanh(scale q.k / cap),
+// cap finite and > 0; window (0 = none) and sink (null = none) as in dlt_dec_attn_gqa_sink.
+DLT_API int dlt_dec_attn_gqa_cap(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const long* pos, bf16_t* o,
+                                 float* ws, int B, int H, int nh, int nkv, int maxS, int NS, float scale, int window,
+                                 const float* sink, float cap, hipStream_t st) {
+  if (!(cap > 0.f) || __builtin_isinf(cap)) return -1;
+  return dec_attn_gqa_launch(q, kc, vc, pos, o, ws, B, H, nh, nkv, maxS, NS, scale, window, st, sink, cap);
+}
+
 DLT_API int dlt_dec_attn(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const long* pos, bf16_t* o, int B,
                          int H, int nh, int maxS, float scale, hipStream_t st) {
   const size_t lds = (size_t)maxS * 4 + 8 * 4 + 4 * 64 * 4;
@@ -1302,6 +1334,22 @@ DLT_API int dlt_dec_attn_sink(const bf16_t* q, const bf16_t* kc, const bf16_t* v
     k_dec_attn<true><<<B * nh, DEC_NT, lds, st>>>(q, kc, vc, pos, o, H, nh, maxS, scale, window, sink);
   else
     k_dec_attn<><<<B * nh, DEC_NT, lds, st>>>(q, kc, vc, pos, o, H, nh, maxS, scale, 0, sink);
+  DLT_CHECK_LAUNCH();
+}
+
+// dlt_dec_attn_sink with attention-score soft-capping: scores cap * tanh(scale q.k / cap), cap
+// finite and > 0; window 0 = none, sink null = none.
+DLT_API int dlt_dec_attn_cap(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const long* pos, bf16_t* o, int B,
+                             int H, int nh, int maxS, float scale, int window, const float* sink, float cap,
+                             hipStream_t st) {
+  if (window < 0 || maxS < 1 || B < 1 || !(cap > 0.f) || __builtin_isinf(cap)) return -1;
+  const size_t lds = (size_t)(window > 0 && window < maxS ? window : maxS) * 4 + 8 * 4 + 4 * 64 * 4;
+  if (H != nh * 64 || lds > 160 * 1024) return -1;
+  const float cap_k = 2.f * 1.44269504088896340736f / cap;
+  if (window > 0)
+    k_dec_attn<true, true><<<B * nh, DEC_NT, lds, st>>>(q, kc, vc, pos, o, H, nh, maxS, scale, window, sink, cap, cap_k);
+  else
+    k_dec_attn<false, true><<<B * nh, DEC_NT, lds, st>>>(q, kc, vc, pos, o, H, nh, maxS, scale, 0, sink, cap, cap_k);
   DLT_CHECK_LAUNCH();
 }
 

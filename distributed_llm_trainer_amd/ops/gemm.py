@@ -247,9 +247,16 @@ def available() -> bool:
 
 
 def report() -> str:
-    buf = ctypes.create_string_buffer(1 << 16)
-    n = lib().dlt_gemm_report(buf, len(buf))
-    return buf.value[:n].decode()
+    """The plan table, one line per key.  dlt_gemm_report fills what fits and returns its length,
+    so a full buffer means a cut table (a process that has tuned a few hundred shapes passes
+    64 KiB, and the keys cut are the last of the sorted table): grow until the table fits."""
+    size = 1 << 16
+    while True:
+        buf = ctypes.create_string_buffer(size)
+        n = lib().dlt_gemm_report(buf, len(buf))
+        if n < size - 1 or size >= 1 << 26:
+            return buf.value[:n].decode()
+        size *= 4
 
 
 def _stream():

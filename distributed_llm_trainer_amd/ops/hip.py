@@ -108,6 +108,10 @@ _SIGS = {
                           c_void_p, c_void_p],
     "dlt_dec_attn_gqa_sink": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                               c_int, c_int, c_float, c_int, c_void_p, c_void_p],
+    "dlt_dec_attn_cap": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int,
+                         c_void_p, c_float, c_void_p],
+    "dlt_dec_attn_gqa_cap": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                             c_int, c_int, c_float, c_int, c_void_p, c_float, c_void_p],
     "dlt_dec_gemv_res": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "dlt_dec_norm_gu": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "dlt_dec_norm_head": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
@@ -203,22 +207,30 @@ def _dec_sink(sink, nh: int, device, name: str) -> torch.Tensor:
     return sink
 
 
-def dec_attn(q, kc, vc, pos, o_out, scale, window=0, sink=None):
+def dec_attn(q, kc, vc, pos, o_out, scale, window=0, sink=None, softcap=None):
     """Decode attention of a multi-head model over keys 0..pos of the caches [B, nh, maxS, 64];
     ``window`` = W > 0: over keys max(0, pos - W + 1)..pos only (a sliding-window layer).
-    ``sink`` (fp32 [nh]): attention sinks, one more softmax logit per head with no value row."""
+    ``sink`` (fp32 [nh]): attention sinks, one more softmax logit per head with no value row.
+    ``softcap`` = CAP (finite, > 0): the scores are CAP * tanh(scale q.k / CAP) (the CAP kernels;
+    the sink is not capped).  None: the call is what it was."""
     window = _dec_window(window, "dec_attn")
     B, nh, maxS, hd = kc.shape
     H = nh * hd
     _req(q, torch.bfloat16, "dec.q", B * H)
     _req(o_out, torch.bfloat16, "dec.o", B * H)
-    if sink is not None:
-        sink = _dec_sink(sink, nh, kc.device, "dec_attn")
+    if sink is not None or softcap is not None:
+        cap = None if softcap is None else _score_cap(softcap, "dec_attn.softcap")
+        if sink is not None:
+            sink = _dec_sink(sink, nh, kc.device, "dec_attn")
         if hd != 64 or vc.shape != kc.shape:
             raise ValueError("dec_attn: caches must be [B, nh, maxS, 64]")
         _req(kc, torch.bfloat16, "dec.k_cache")
         _req(vc, torch.bfloat16, "dec.v_cache")
         _req(pos, torch.int64, "dec.pos", 1)
+        if cap is not None:  # the CAP kernels: window 0 = none, a null sink = none
+            _chk(lib().dlt_dec_attn_cap(_p(q), _p(kc), _p(vc), _p(pos), _p(o_out), B, H, nh, maxS, float(scale),
+                                        window, _p(sink), cap, _stream()), "dec_attn_cap")
+            return
         _chk(lib().dlt_dec_attn_sink(_p(q), _p(kc), _p(vc), _p(pos), _p(o_out), B, H, nh, maxS, float(scale), window,
                                      _p(sink), _stream()), "dec_attn_sink")
         return
@@ -280,7 +292,7 @@ def dec_attn_gqa_workspace(B: int, nh: int, splits: int, device) -> torch.Tensor
     return torch.empty(B * nh * splits * DEC_ATTN_WS, dtype=torch.float32, device=device)
 
 
-def dec_attn_gqa(q, kc, vc, pos, o_out, scale, nh, splits=1, ws=None, window=0, sink=None):
+def dec_attn_gqa(q, kc, vc, pos, o_out, scale, nh, splits=1, ws=None, window=0, sink=None, softcap=None):
     """Decode attention of a grouped-query model: q, o_out [B, nh * 64] bf16, caches
     [B, nkv, maxS, 64]; every K/V row is read once for the nh / nkv query heads of its group.
     ``splits`` > 1 divides the keys over that many workgroups per K/V head (chunks of
@@ -288,7 +300,7 @@ def dec_attn_gqa(q, kc, vc, pos, o_out, scale, nh, splits=1, ws=None, window=0, 
     (:func:`dec_attn_gqa_workspace`).  ``window`` = W > 0: keys max(0, pos - W + 1)..pos only,
     in chunks of ``dec_attn_chunk(min(W, maxS), splits)`` anchored at the window's first key.
     ``sink`` (fp32 [nh], per query head): attention sinks; with ``splits`` > 1 the merge adds the
-    sink once."""
+    sink once.  ``softcap``: as in :func:`dec_attn`."""
     window = _dec_window(window, "dec_attn_gqa")
     if kc.dim() != 4 or kc.shape[3] != 64 or vc.shape != kc.shape:
         raise ValueError("dec_attn_gqa: caches must be [B, nkv, maxS, 64]")
@@ -309,6 +321,13 @@ def dec_attn_gqa(q, kc, vc, pos, o_out, scale, nh, splits=1, ws=None, window=0, 
         _req(ws, torch.float32, "dec.attn_ws", B * nh * splits * DEC_ATTN_WS)
     if sink is not None:
         sink = _dec_sink(sink, nh, kc.device, "dec_attn_gqa")
+    if softcap is not None:  # the CAP kernels: window 0 = none, a null sink = none
+        cap = _score_cap(softcap, "dec_attn_gqa.softcap")
+        _chk(lib().dlt_dec_attn_gqa_cap(_p(q), _p(kc), _p(vc), _p(pos), _p(o_out), _p(ws if splits > 1 else None), B,
+                                        H, nh, nkv, maxS, splits, float(scale), window, _p(sink), cap, _stream()),
+             "dec_attn_gqa_cap")
+        return
+    if sink is not None:
         _chk(lib().dlt_dec_attn_gqa_sink(_p(q), _p(kc), _p(vc), _p(pos), _p(o_out), _p(ws if splits > 1 else None), B,
                                          H, nh, nkv, maxS, splits, float(scale), window, _p(sink), _stream()),
              "dec_attn_gqa_sink")
@@ -900,7 +919,8 @@ class _AttnArgs(ctypes.Structure):
                                          "lo", "hi", "cosT", "sinT")]
                 + [(n, c_int) for n in ("B", "nh", "nkv", "S", "hd", "hk")]
                 + [("scale", c_float), ("dscale", c_float), ("key", c_uint32), ("thr", c_uint32),
-                   ("gen_mask", c_int), ("stride", _AttnStrides), ("sink", c_void_p), ("dsink", c_void_p)])
+                   ("gen_mask", c_int), ("softcap", c_float), ("stride", _AttnStrides), ("sink", c_void_p),
+                   ("dsink", c_void_p)])
 
 
 def _keep_bits_fwd(p, mask, B, nh, S, device, key=0, window=None):
@@ -971,11 +991,33 @@ def _attn_sink(sink, nh: int, device, name: str, grad: bool = False):
     return sink
 
 
-def _f32(name: str, hd: int, doc=None, window=None, sink=None, nkv=None, scale=None):
+def _score_cap(softcap, name: str) -> float:
+    """An attention-score cap (``softcap=`` not None): finite and > 0, also as the kernels' fp32."""
+    cap = _cap32(softcap, name)
+    if cap == 0.0:
+        raise ValueError(f"{name}: the cap must be finite and > 0 (None turns it off), got {softcap!r}")
+    return cap
+
+
+def _attn_cap(softcap, name: str) -> dict:
+    """``softcap=`` of the attention wrappers as the ``softcap`` field of the argument struct:
+    nothing for None (the struct is the one built without the keyword: the plain kernels), else
+    the cap, finite and > 0 also as the fp32 the CAP kernels receive."""
+    if softcap is None:
+        return {}
+    from . import attn_routes
+    cap = _score_cap(softcap, name + ".softcap")
+    attn_routes.check_score_softcap_range(cap, name + ".softcap")
+    return {"softcap": cap}
+
+
+def _f32(name: str, hd: int, doc=None, window=None, sink=None, nkv=None, scale=None, softcap=None):
     """``hip_f32``, for an fp32 call to hand over to: the fp32 routes have no document mask, window,
-    sinks or grouped K/V, and their score scale is 1/sqrt(head_dim)."""
+    sinks, grouped K/V or score cap, and their score scale is 1/sqrt(head_dim)."""
     from . import attn_routes, hip_f32
     rt = attn_routes.route(torch.float32, hd)
+    if softcap is not None:
+        attn_routes.require_score_softcap(rt, name)
     for feature, arg in (("sinks", sink), ("gqa", nkv), ("window", window), ("doc", doc)):
         if arg is not None:
             attn_routes.require(rt, feature, name)
@@ -984,19 +1026,20 @@ def _f32(name: str, hd: int, doc=None, window=None, sink=None, nkv=None, scale=N
     return hip_f32
 
 
-def _attn_fwd_launch(name, src, o, lse, keep, key, lo, B, nh, nkv, S, hd, hk, scale, sink=None):
+def _attn_fwd_launch(name, src, o, lse, keep, key, lo, B, nh, nkv, S, hd, hk, scale, sink=None, softcap=None):
     """dlt_attn_fwd on q / k / v of layout ``src`` (:func:`_head_major`, :func:`_packed_row`)
-    with ``keep`` of :func:`_keep_bits_fwd`; nkv None: the MHA kernels; ``sink``: the SINK forms."""
+    with ``keep`` of :func:`_keep_bits_fwd`; nkv None: the MHA kernels; ``sink``: the SINK forms;
+    ``softcap``: the CAP forms (attention_cap.hip)."""
     (q, k, v), sq, skv = src
     thr, dscale, mask, gen = keep
     a = _AttnArgs(q=q, k=k, v=v, o=_p(o), lse=_p(lse), mask=_p(mask), lo=_p(lo), B=B, nh=nh, nkv=nkv or 0, S=S,
                   hd=hd, hk=hk, scale=scale, dscale=dscale, key=key & 0xFFFFFFFF, thr=thr, gen_mask=int(gen == 1),
-                  stride=_AttnStrides(q=sq, kv=skv), sink=_p(sink))
+                  stride=_AttnStrides(q=sq, kv=skv), sink=_p(sink), **_attn_cap(softcap, name))
     _chk(lib().dlt_attn_fwd(ctypes.byref(a), _stream()), _attn_name(name, nkv, lo))
 
 
 def _attn_bwd_launch(name, src, dst, o, do, lse, keep, doc, rope, B, nh, nkv, S, hd, hk, scale, sink=None,
-                     dsink=None):
+                     dsink=None, softcap=None):
     """dlt_attn_bwd: dq / dk / dv into layout ``dst``; ``keep`` of :func:`_keep_bits_bwd`,
     ``doc`` = (lo, hi), ``rope`` = (cos, sin) or (None, None).  With ``sink`` / ``dsink`` the
     launch ends with k_attn_sink_bwd, which reads lse and the delta workspace dQ wrote."""
@@ -1005,16 +1048,17 @@ def _attn_bwd_launch(name, src, dst, o, do, lse, keep, doc, rope, B, nh, nkv, S,
     thr, dscale, mask = keep
     if (sink is None) != (dsink is None):
         raise ValueError(f"{name}: sink and dsink go together")
+    cap = _attn_cap(softcap, name)
     delta = torch.empty(B, nh, S, dtype=torch.float32, device=lse.device)
     a = _AttnArgs(q=q, k=k, v=v, o=_p(o), lse=_p(lse), mask=_p(mask), dout=_p(do), delta_ws=_p(delta), dq=dq, dk=dk,
                   dv=dv, lo=_p(doc[0]), hi=_p(doc[1]), cosT=_p(rope[0]), sinT=_p(rope[1]), B=B, nh=nh, nkv=nkv or 0,
                   S=S, hd=hd, hk=hk, scale=scale, dscale=dscale, thr=thr,
-                  stride=_AttnStrides(q=sq, kv=skv, dq=sdq, dkv=sdkv), sink=_p(sink), dsink=_p(dsink))
+                  stride=_AttnStrides(q=sq, kv=skv, dq=sdq, dkv=sdkv), sink=_p(sink), dsink=_p(dsink), **cap)
     _chk(lib().dlt_attn_bwd(ctypes.byref(a), _stream()), _attn_name(name, nkv, doc[0]))
 
 
 def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=None, scale=None, doc=None,
-                  nkv=None, window=None, sink=None):
+                  nkv=None, window=None, sink=None, softcap=None):
     """Returns (o [B*S, nh*hd] bf16, aux).  With dropout on, the keep bits are written
     to a bitmask consumed by attention_bwd (no re-hashing in the backward); pass
     ``mask`` from ``attention_dropout_mask`` to skip generating it here.  ``scale``:
@@ -1026,10 +1070,14 @@ def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=
     q - W < k <= q (of its document); it runs on the DOC kernels with the bounds of
     :func:`window_bounds`, and keep bits made here are the banded ones.  ``sink`` (fp32 [nh]):
     attention sinks, one more logit per query head in the softmax denominator (not scaled, no
-    value row; the SINK kernels); the returned lse holds it."""
+    value row; the SINK kernels); the returned lse holds it.  ``softcap`` = CAP (finite, > 0):
+    attention-score soft-capping, scores CAP * tanh(scale q.k / CAP) before the masks and the
+    softmax (the CAP kernels); masked keys stay at -inf, a sink is not capped, and lse is that of
+    the capped scores; at most ``attn_routes.SCORE_SOFTCAP_MAX``.  None: the call, its argument
+    struct and its kernels are what they were."""
     nkv = _head_major_nkv(q, k, v, nkv, "attn")
     if q.dtype == torch.float32:
-        return _f32("attention_fwd", q.shape[3], doc, window, sink, nkv, scale).attention_fwd(
+        return _f32("attention_fwd", q.shape[3], doc, window, sink, nkv, scale, softcap).attention_fwd(
             q, k, v, p, key, causal, store_mask=store_mask, out=out, mask=mask)
     if not causal:
         raise NotImplementedError("only causal attention is implemented (the model is a causal LM)")
@@ -1046,7 +1094,8 @@ def attention_fwd(q, k, v, p, key, causal=True, store_mask=True, out=None, mask=
     keep = _keep_bits_fwd(p, mask, B, nh, S, q.device, key, window)
     sc = 1.0 / math.sqrt(hd) if scale is None else float(scale)
     sink = _attn_sink(sink, nh, q.device, "attn.sink")
-    _attn_fwd_launch("attn_fwd", _head_major(q, k, v), o, lse, keep, key, lo, B, nh, nkv, S, hd, hk, sc, sink)
+    _attn_fwd_launch("attn_fwd", _head_major(q, k, v), o, lse, keep, key, lo, B, nh, nkv, S, hd, hk, sc, sink,
+                     softcap)
     return o, AttnAux((lse, keep[2] if (store_mask or not keep[3]) else None))
 
 
@@ -1065,13 +1114,14 @@ def _packed_dims(qkv, B, S, nh, nkv=None):
 
 
 def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=True, doc=None, nkv=None,
-                         window=None, sink=None):
+                         window=None, sink=None, softcap=None):
     """Causal attention reading q/k/v straight from the packed (roped) [B*S, 3H] QKV.
     Returns (o [B*S, H] bf16, aux) like :func:`attention_fwd`.  With ``nkv`` (grouped-query
     attention) the packed row is [H + 2*KV]; lse and the keep bits stay per query head.
-    ``window``, ``sink``: see :func:`attention_fwd`."""
+    ``window``, ``sink``, ``softcap``: see :func:`attention_fwd`."""
     if qkv.dtype == torch.float32:
-        return _f32("attention_fwd_packed", qkv.shape[1] // (3 * nh), doc, window, sink, nkv).attention_fwd_packed(
+        return _f32("attention_fwd_packed", qkv.shape[1] // (3 * nh), doc, window, sink, nkv,
+                    softcap=softcap).attention_fwd_packed(
             qkv, B, S, nh, p, key, out=out, mask=mask, store_mask=store_mask)
     M, H, hd, KV = _packed_dims(qkv, B, S, nh, nkv)
     window, doc = _window_doc(window, doc, B, S, qkv.device, "attn")
@@ -1082,12 +1132,12 @@ def attention_fwd_packed(qkv, B, S, nh, p, key, out=None, mask=None, store_mask=
     keep = _keep_bits_fwd(p, mask, B, nh, S, qkv.device, key, window)
     sink = _attn_sink(sink, nh, qkv.device, "attn.sink")
     _attn_fwd_launch("attn_fwd_packed", _packed_row(qkv, S, H, hd, KV), o, lse, keep, key, lo, B, nh, nkv, S, hd,
-                     _HK[qkv.dtype], 1.0 / math.sqrt(hd), sink)
+                     _HK[qkv.dtype], 1.0 / math.sqrt(hd), sink, softcap)
     return o, AttnAux((lse, keep[2] if (store_mask or not keep[3]) else None))
 
 
 def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, doc=None, nkv=None, window=None,
-                         sink=None, dsink=None):
+                         sink=None, dsink=None, softcap=None):
     """Backward of :func:`attention_fwd_packed` + the in-place RoPE: returns dqkv
     [B*S, 3H] (gradient w.r.t. the pre-rotation QKV GEMM output); dq/dk/dv are written
     into it by the attention kernels with the inverse rotation in their epilogue.  With
@@ -1095,9 +1145,11 @@ def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, 
     heads in registers, in a fixed order.  ``window``: the forward's.  ``sink`` / ``dsink`` (fp32
     [nh], both or neither): the forward's sinks and their gradient accumulator,
     ``dsink[h] += -sum_{b,q} exp(sink[h] - lse) * rowsum(dO * O)`` in a fixed order (no atomics);
-    dq / dk / dv need only the forward's lse."""
+    dq / dk / dv need only the forward's lse.  ``softcap``: the forward's; dQ and dK/dV rebuild
+    t = tanh(scale q.k / CAP) and carry 1 - t^2 into dS (the CAP kernels)."""
     if qkv.dtype == torch.float32:
-        return _f32("attention_bwd_packed", qkv.shape[1] // (3 * nh), doc, window, sink, nkv).attention_bwd_packed(
+        return _f32("attention_bwd_packed", qkv.shape[1] // (3 * nh), doc, window, sink, nkv,
+                    softcap=softcap).attention_bwd_packed(
             qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=out)
     M, H, hd, KV = _packed_dims(qkv, B, S, nh, nkv)
     Wd = H + 2 * KV
@@ -1117,17 +1169,18 @@ def attention_bwd_packed(qkv, o, do, aux, p, key, B, S, nh, cos, sin, out=None, 
     sink = _attn_sink(sink, nh, qkv.device, "attn_bwd.sink")
     dsink = _attn_sink(dsink, nh, qkv.device, "attn_bwd.dsink", grad=True)
     _attn_bwd_launch("attn_bwd_packed", _packed_row(qkv, S, H, hd, KV), _packed_row(dqkv, S, H, hd, KV), o, do, lse,
-                     keep, (lo, hi), (cos, sin), B, nh, nkv, S, hd, _HK[qkv.dtype], 1.0 / math.sqrt(hd), sink, dsink)
+                     keep, (lo, hi), (cos, sin), B, nh, nkv, S, hd, _HK[qkv.dtype], 1.0 / math.sqrt(hd), sink, dsink,
+                     softcap)
     return dqkv
 
 
 def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, scale=None, doc=None, nkv=None, window=None,
-                  sink=None, dsink=None):
+                  sink=None, dsink=None, softcap=None):
     """Returns dq [B, nh, S, hd] and dk, dv in k's shape ([B, nkv, S, hd] under grouped-query
-    attention, see :func:`attention_fwd`).  ``sink`` / ``dsink``: see :func:`attention_bwd_packed`."""
+    attention, see :func:`attention_fwd`).  ``sink`` / ``dsink``, ``softcap``: see :func:`attention_bwd_packed`."""
     nkv = _head_major_nkv(q, k, v, nkv, "attn_bwd")
     if q.dtype == torch.float32:
-        return _f32("attention_bwd", q.shape[3], doc, window, sink, nkv, scale).attention_bwd(
+        return _f32("attention_bwd", q.shape[3], doc, window, sink, nkv, scale, softcap).attention_bwd(
             q, k, v, o, do, aux, p, key, causal)
     B, nh, S, hd = q.shape
     n = B * nh * S * hd
@@ -1146,7 +1199,7 @@ def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, scale=None, doc=None
     sink = _attn_sink(sink, nh, q.device, "attn_bwd.sink")
     dsink = _attn_sink(dsink, nh, q.device, "attn_bwd.dsink", grad=True)
     _attn_bwd_launch("attn_bwd", _head_major(q, k, v), _head_major(dq, dk, dv), o, do, lse, keep, (lo, hi),
-                     (None, None), B, nh, nkv, S, hd, hk, sc, sink, dsink)
+                     (None, None), B, nh, nkv, S, hd, hk, sc, sink, dsink, softcap)
     return dq, dk, dv
 
 

@@ -213,18 +213,19 @@ def _split_packed(qkv, B, S, nh, nkv=None):
 
 
 def attention_fwd_packed(qkv: torch.Tensor, B: int, S: int, nh: int, p: float, key: int, out=None, mask=None,
-                         doc=None, nkv=None, window=None, sink=None):
+                         doc=None, nkv=None, window=None, sink=None, softcap=None):
     """Causal attention straight on the (already roped) packed [B*S, H + 2*KV] QKV."""
     q, k, v = _split_packed(qkv, B, S, nh, nkv)
-    return attention_fwd(q, k, v, p, key, True, out=out, doc=doc, window=window, sink=sink)
+    return attention_fwd(q, k, v, p, key, True, out=out, doc=doc, window=window, sink=sink, softcap=softcap)
 
 
 def attention_bwd_packed(qkv, o, do, lse, p: float, key: int, B: int, S: int, nh: int,
                          cos: torch.Tensor, sin: torch.Tensor, out=None, doc=None, nkv=None,
-                         window=None, sink=None, dsink=None) -> torch.Tensor:
+                         window=None, sink=None, dsink=None, softcap=None) -> torch.Tensor:
     """Backward of attention_fwd_packed + the in-place RoPE: dqkv [B*S, H + 2*KV] (pre-RoPE)."""
     q, k, v = _split_packed(qkv, B, S, nh, nkv)
-    dq, dk, dv = attention_bwd(q, k, v, o, do, lse, p, key, True, doc=doc, window=window, sink=sink, dsink=dsink)
+    dq, dk, dv = attention_bwd(q, k, v, o, do, lse, p, key, True, doc=doc, window=window, sink=sink, dsink=dsink,
+                               softcap=softcap)
     res = rope_qkv_bwd(dq.float(), dk.float(), dv.float(), cos, sin).to(qkv.dtype)
     if out is not None:
         out.copy_(res)
@@ -354,22 +355,38 @@ def _req_sink(sink, nh: int, device, name: str, grad: bool = False) -> torch.Ten
     return sink.float()
 
 
+def check_score_cap(softcap, name: str = "attn.softcap") -> Optional[float]:
+    """``softcap=`` of the attention ops (the attention-score cap): None is off; otherwise a real
+    number (no bool), finite and > 0."""
+    if softcap is None:
+        return None
+    cap = check_softcap(softcap, name)
+    if cap == 0.0:
+        raise ValueError(f"{name}: the cap must be finite and > 0 (None turns it off), got {softcap!r}")
+    return cap
+
+
 def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, p: float, key: int,
                   causal: bool = True, out=None, doc=None, window=None,
-                  sink=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                  sink=None, softcap=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """q [B, nh, S, hd], k, v [B, nkv, S, hd] -> o [B*S, nh*hd] (q dtype), lse [B, nh, S] fp32.
     ``doc`` = (lo, hi) from :func:`doc_bounds` adds the intra-document mask.  nkv < nh is
     grouped-query attention: query head h attends with kv head h // (nh // nkv).  ``window`` = W
     is sliding-window attention (:func:`window_bounds`, merged with ``doc``).  ``sink`` (fp32
     [nh]) is one more logit per query head in the softmax denominator, not scaled and with no
     value row: p_j = exp(s_j) / (sum_j exp(s_j) + exp(sink[h])), lse = log of that denominator;
-    dropout applies to the p_j only."""
+    dropout applies to the p_j only.  ``softcap`` = CAP: attention-score soft-capping, the scaled
+    scores become CAP * tanh(s / CAP) before the masks (masked keys stay at -inf; the sink is not
+    capped), and lse is that of the capped scores."""
     B, nh, S, hd = q.shape
+    cap = check_score_cap(softcap)
     doc = _fold_window(window, doc, B, S, q.device)
     G = _kv_group(q, k, v, "attn")
     scale = 1.0 / math.sqrt(hd)
     k, v = _rep_kv(k.float(), G), _rep_kv(v.float(), G)
     s = torch.matmul(q.float(), k.transpose(-2, -1)) * scale
+    if cap is not None:
+        s = cap * torch.tanh(s / cap)
     mask = _masked_out(S, q.device, causal, doc, B, "attn")
     if mask is not None:
         s = s.masked_fill(mask, float("-inf"))
@@ -389,13 +406,15 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, p: float, k
 
 
 def attention_bwd(q, k, v, o, do, lse, p: float, key: int, causal: bool = True, doc=None, window=None,
-                  sink=None, dsink=None):
+                  sink=None, dsink=None, softcap=None):
     """Flash-style backward from (o, lse).  do/o are [B*S, H]; returns dq [B,nh,S,hd] and
     dk, dv in k's shape [B,nkv,S,hd] (summed over each kv head's query group in fp32).
     With ``sink`` the forward's ``lse`` already holds the sink, so dq / dk / dv need nothing
     else (the sink column has dP = 0 and delta = rowsum(dO * O) already is sum_j P_j dP_j);
-    ``dsink`` (fp32 [nh]) += -sum_{b,q} exp(sink[h] - lse[b,h,q]) * delta[b,h,q]."""
+    ``dsink`` (fp32 [nh]) += -sum_{b,q} exp(sink[h] - lse[b,h,q]) * delta[b,h,q].
+    ``softcap``: the forward's; with t = tanh(s / CAP), dS carries 1 - t^2 into dq and dk."""
     B, nh, S, hd = q.shape
+    cap = check_score_cap(softcap, "attn_bwd.softcap")
     if (sink is None) != (dsink is None):
         raise ValueError("attn_bwd: sink and dsink go together")
     doc = _fold_window(window, doc, B, S, q.device)
@@ -405,6 +424,10 @@ def attention_bwd(q, k, v, o, do, lse, p: float, key: int, causal: bool = True, 
     of = o.float().view(B, S, nh, hd).transpose(1, 2)
     dof = do.float().view(B, S, nh, hd).transpose(1, 2)
     s = torch.matmul(qf, kf.transpose(-2, -1)) * scale
+    dt2 = None
+    if cap is not None:
+        t = torch.tanh(s / cap)
+        s, dt2 = cap * t, 1.0 - t * t
     mask = _masked_out(S, q.device, causal, doc, B, "attn_bwd")
     if mask is not None:
         s = s.masked_fill(mask, float("-inf"))
@@ -424,6 +447,8 @@ def attention_bwd(q, k, v, o, do, lse, p: float, key: int, causal: bool = True, 
         p_sink = torch.exp(sink.view(1, nh, 1) - lse)
         dsink += -(p_sink * delta.squeeze(-1)).sum(dim=(0, 2))
     ds = prob * (dp - delta)
+    if dt2 is not None:
+        ds = ds * dt2
     dq = torch.matmul(ds, kf) * scale
     dk = torch.matmul(ds.transpose(-2, -1), qf) * scale
     if G > 1:

@@ -275,6 +275,11 @@ def add_model_args(p) -> None:
                         "CAP > 0; Gemma-2 and the GPT-2 speed-run recipes use 30), in training, evaluation and "
                         "generation, and saved in checkpoints.  Overrides the YAML's model.logit_softcap and the "
                         "preset (default: off)")
+    p.add_argument("--attn_softcap", type=float, default=None, metavar="CAP",
+                   help="attention-score soft-capping: every layer's scaled scores are CAP * tanh(scores / CAP) "
+                        "before the masks and the softmax (a finite CAP > 0; Gemma-2 uses 50), in training, "
+                        "evaluation and generation, and saved in checkpoints.  Overrides the YAML's "
+                        "model.attn_softcap and the preset (default: off)")
 
 
 def apply_model_args(args, model_config) -> None:
@@ -290,13 +295,16 @@ def apply_model_args(args, model_config) -> None:
         model_config.attention_sinks = bool(args.attention_sinks)
     sw, swp = getattr(args, "sliding_window", None), getattr(args, "sliding_window_pattern", None)
     cap = getattr(args, "logit_softcap", None)
-    if sw is not None or swp is not None or cap is not None:
+    acap = getattr(args, "attn_softcap", None)
+    if sw is not None or swp is not None or cap is not None or acap is not None:
         if sw is not None:
             model_config.sliding_window = sw
         if swp is not None:
             model_config.sliding_window_pattern = swp
         if cap is not None:
             model_config.logit_softcap = cap
+        if acap is not None:
+            model_config.attn_softcap = acap
         model_config.__post_init__()  # the config's own validation (ValueError)
 
 

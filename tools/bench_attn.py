@@ -8,7 +8,8 @@ attention: N K/V heads shared by groups of nh / N query heads (the GQA kernels; 
 runs them with groups of one, no flag the MHA kernels).  ``--window W`` times sliding-window
 attention (``window=W``: the DOC kernels on ``window_bounds`` and the banded keep-bit
 kernel) against causal in the same process, the two alternating round by round, and the
-banded against the full keep-bit kernel.  The backward is one call (dQ then
+banded against the full keep-bit kernel.  ``--softcap CAP`` times attention-score soft-capping
+(``softcap=CAP``: the CAP kernels) against the plain kernels the same way.  The backward is one call (dQ then
 dK/dV); a kernel trace of this tool (``tools/ab/prof_step.sh`` style: ``rocprofv3
 --kernel-trace --stats``) splits it per kernel."""
 import argparse
@@ -106,6 +107,35 @@ def window_ab(a, q, k, v, key, gkw):
               f"ratio {med(bits['full']) / med(bits['banded']):.2f}x")
 
 
+def softcap_ab(a, q, k, v, key, gkw):
+    """plain vs softcap=CAP (the CAP kernels), head-major, alternating round by round: the forward
+    kernel alone on given keep bits and the backward (dQ + dK/dV) on stored bits.  The causal rows'
+    spread over the rounds is the noise the ratios have to be read against; a kernel trace of this
+    mode splits the backward per kernel."""
+    cases = {"plain": dict(gkw), f"softcap {a.softcap:g}": dict(gkw, softcap=a.softcap)}
+    st = {}
+    for name, kw in cases.items():
+        o, aux = hip.attention_fwd(q, k, v, a.p, key, **kw)
+        st[name] = (o, aux, torch.randn_like(o))
+    rows = {n: [] for n in cases}
+    for r in range(a.rounds):
+        for name, kw in cases.items():
+            o, aux, do = st[name]
+            mkw = {"mask": aux[1]} if a.p > 0 else {}
+            t_k = timeit(lambda: hip.attention_fwd(q, k, v, a.p, key, **mkw, **kw), a.iters)
+            t_b = timeit(lambda: hip.attention_bwd(q, k, v, o, do, aux, a.p, key, **kw), a.iters)
+            rows[name].append((t_k, t_b))
+            print(f"round {r} [{name}] fwd kernel {t_k:.1f} us, bwd {t_b:.1f} us", flush=True)
+    med = lambda xs: sorted(xs)[len(xs) // 2]  # noqa: E731
+    m = {n: [med([row[i] for row in rows[n]]) for i in range(2)] for n in cases}
+    c, w = m["plain"], m[f"softcap {a.softcap:g}"]
+    spread = [(max(row[i] for row in rows["plain"]) - min(row[i] for row in rows["plain"])) / c[i] * 100 for i in range(2)]
+    print(f"B{a.B} nh{a.nh} S{a.S} p{a.p} softcap {a.softcap:g}, medians of {a.rounds} rounds x {a.iters} iterations:")
+    for i, nm in enumerate(("fwd kernel", "bwd (dQ + dK/dV)")):
+        print(f"  {nm}: plain {c[i]:.1f} us, capped {w[i]:.1f} us, ratio {w[i] / c[i]:.2f}x "
+              f"(plain spread over the rounds {spread[i]:.1f} %)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=8)
@@ -122,7 +152,10 @@ def main():
                     help="grouped-query attention with N K/V heads (must divide --nh); default: the MHA kernels")
     ap.add_argument("--window", type=int, default=None, metavar="W",
                     help="also time sliding-window attention of W keys, alternating with causal (--rounds rounds)")
-    ap.add_argument("--rounds", type=int, default=5, help="alternating rounds of the --window comparison")
+    ap.add_argument("--softcap", type=float, default=None, metavar="CAP",
+                    help="time attention-score soft-capping (the CAP kernels) against the plain kernels, alternating "
+                         "(--rounds rounds)")
+    ap.add_argument("--rounds", type=int, default=5, help="alternating rounds of the --window / --softcap comparison")
     ap.add_argument("--only", default="both", choices=("both", "off", "doc"),
                     help="which variants to run (a kernel trace of one variant: --only off / --only doc)")
     a = ap.parse_args()
@@ -145,6 +178,9 @@ def main():
     fl = 4 * a.B * a.nh * a.S * a.S / 2 * 64
     if a.window is not None:
         window_ab(a, q, k, v, key, gkw)
+        return
+    if a.softcap is not None:
+        softcap_ab(a, q, k, v, key, gkw)
         return
     if a.kv_heads is not None:
         nrb = (a.S + 63) // 64

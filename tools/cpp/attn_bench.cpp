@@ -1,6 +1,7 @@
 // Standalone timing of the attention forward kernel at B8 nh12 S1024 hd64 (random data).
 #include "../../distributed_llm_trainer_amd/ops/csrc/attention.hip"
 #include "../../distributed_llm_trainer_amd/ops/csrc/attention_sink.hip"  // dlt_attn_fwd's SINK launcher
+#include "../../distributed_llm_trainer_amd/ops/csrc/attention_cap.hip"   // dlt_attn_fwd's / dlt_attn_bwd's CAP launchers
 #include <cstdio>
 #include <vector>
 __global__ void fill(unsigned short* p, size_t n, unsigned seed) {

@@ -5,6 +5,7 @@
 //     tools/cpp/attn_timing.cpp -o tools/cpp/attn_timing
 #include "../../distributed_llm_trainer_amd/ops/csrc/attention.hip"
 #include "../../distributed_llm_trainer_amd/ops/csrc/attention_sink.hip"  // dlt_attn_fwd's SINK launcher
+#include "../../distributed_llm_trainer_amd/ops/csrc/attention_cap.hip"   // dlt_attn_fwd's / dlt_attn_bwd's CAP launchers
 #include <algorithm>
 #include <cstdio>
 #include <vector>

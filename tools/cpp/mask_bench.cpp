@@ -1,6 +1,7 @@
 // Timing of the attention keep-bit kernel (B8 nh12 S1024) -- used for layout experiments.
 #include "../../distributed_llm_trainer_amd/ops/csrc/attention.hip"
 #include "../../distributed_llm_trainer_amd/ops/csrc/attention_sink.hip"  // dlt_attn_fwd's SINK launcher
+#include "../../distributed_llm_trainer_amd/ops/csrc/attention_cap.hip"   // dlt_attn_fwd's / dlt_attn_bwd's CAP launchers
 #include <cstdio>
 int main() {
   int B = 8, nh = 12, S = 1024, W = S / 32;
