@@ -48,6 +48,15 @@ def _rms(x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
     return xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * w.float()
 
 
+def _branch(a: torch.Tensor, wn, eps: float) -> torch.Tensor:
+    """The fp32 value a branch output ``a`` (o_proj / down_proj, activation dtype) adds to the
+    residual: with post-norms (cfg.post_norm: ``wn`` = ``w.pn1`` / ``w.pn2`` is set) the RMSNorm of
+    ``a`` rounded once to the activation dtype, as the training kernels form it; else ``a``."""
+    if wn is None:
+        return a.float()
+    return _rms(a, wn, eps).to(a.dtype).float()
+
+
 def _rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Tensor:
     # x [B, T, nh, hd] fp32; cos/sin [T, hd/2]
     half = x.shape[-1] // 2
@@ -163,12 +172,12 @@ def forward_cached(model, ids: torch.Tensor, cache: KVCache) -> torch.Tensor:
             s = s.masked_fill(hidden, float("-inf"))
         pr = _sink_softmax(s, w)
         o = torch.matmul(pr, Vv).transpose(1, 2).reshape(B, T, nh * hd).to(dt)
-        h = h + torch.matmul(o, w.wo.t()).float()
+        h = h + _branch(torch.matmul(o, w.wo.t()), getattr(w, "pn1", None), eng.eps)
         n2 = _rms(h, w.ln2, eng.eps).to(dt)
         gu = torch.matmul(n2, w.wgu.t()).float()
         I = cfg.intermediate_size
         a = (F.silu(gu[..., :I]) * gu[..., I:]).to(dt)
-        h = h + torch.matmul(a, w.wdown.t()).float()
+        h = h + _branch(torch.matmul(a, w.wdown.t()), getattr(w, "pn2", None), eng.eps)
         prov.post_forward(i)
     hw = prov.head()
     nf = _rms(h[:, -1], hw.norm, eng.eps).to(dt)
@@ -310,11 +319,12 @@ class DecodeGraph:
             s_ = _cap_scores(torch.matmul(qh, _rep_kv(cache.k[i], cfg).transpose(-2, -1)).float() * scale, cfg)
             pr = _sink_softmax(s_.masked_fill(masked, float("-inf")), w)
             o = torch.matmul(pr.to(dt), _rep_kv(cache.v[i], cfg)).transpose(1, 2).reshape(B, 1, nh * hd)
-            h = h + torch.matmul(o, w.wo.t()).float()
+            h = h + _branch(torch.matmul(o, w.wo.t()), getattr(w, "pn1", None), eng.eps)
             n2 = _rms(h, w.ln2, eng.eps).to(dt)
             gu = torch.matmul(n2, w.wgu.t()).float()
             I = cfg.intermediate_size
-            h = h + torch.matmul((F.silu(gu[..., :I]) * gu[..., I:]).to(dt), w.wdown.t()).float()
+            h = h + _branch(torch.matmul((F.silu(gu[..., :I]) * gu[..., I:]).to(dt), w.wdown.t()),
+                            getattr(w, "pn2", None), eng.eps)
         nf = _rms(h[:, -1], hw.norm, eng.eps).to(dt)
         return _softcap(torch.matmul(nf, hw.lm_head.t())[:, :cfg.vocab_size].float(), cfg)
 
@@ -371,6 +381,8 @@ def _fused_kind(model, B: int) -> Optional[str]:
     ops = model.engine.ops
     cfg = model.config
     if getattr(cfg, "qk_norm", False):  # no fused norm + QKV kernel applies q_norm / k_norm: the ATen step does
+        return None
+    if getattr(cfg, "post_norm", False):  # dec_gemv_res adds the raw branch to the residual: the ATen step norms it
         return None
     norm_lds = B * cfg.hidden_size * 2 + B * 4 * 4 + B * 16 * 4
     if not (hasattr(ops, "dec_norm_qkv") and B in getattr(ops, "DECODE_BATCHES", ())

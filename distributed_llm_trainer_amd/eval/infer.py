@@ -26,14 +26,15 @@ def pick_device(name: str) -> torch.device:
 
 def load_model(path: str, model_size: str = None, device="cpu", num_kv_heads: int = None, qk_norm: bool = None,
                sliding_window: int = None, sliding_window_pattern: int = None, attention_sinks: bool = None,
-               logit_softcap: float = None, attn_softcap: float = None):
+               logit_softcap: float = None, attn_softcap: float = None, post_norm: bool = None):
     """The model of a checkpoint: built from the checkpoint's own config (which carries
     num_kv_heads for a grouped-query model) unless ``model_size`` names a preset;
     ``num_kv_heads`` overrides either, and so does ``qk_norm`` (the checkpoint's config carries
     it for a QK-norm model), ``sliding_window`` and ``sliding_window_pattern`` (a windowed model's
     config carries them too), ``attention_sinks`` (carried by the config of a model with sinks) and
     ``logit_softcap`` (the final-logit cap, carried by the config of a model trained with one) and
-    ``attn_softcap`` (the attention-score cap, carried likewise)."""
+    ``attn_softcap`` (the attention-score cap, carried likewise) and ``post_norm`` (the post-norms,
+    carried by the config of a model that has them)."""
     ckpt = load_checkpoint(path, map_location="cpu")
     cfg = ckpt.get("model_config")
     if model_size is not None or not isinstance(cfg, GPTConfig):
@@ -52,6 +53,8 @@ def load_model(path: str, model_size: str = None, device="cpu", num_kv_heads: in
         cfg = GPTConfig.from_dict({**cfg.to_dict(), "logit_softcap": logit_softcap})
     if attn_softcap is not None:
         cfg = GPTConfig.from_dict({**cfg.to_dict(), "attn_softcap": attn_softcap})
+    if post_norm is not None:
+        cfg = GPTConfig.from_dict({**cfg.to_dict(), "post_norm": bool(post_norm)})
     model = GPT(cfg)
     load_model_state(model, ckpt["model"])
     model = model.to(device)
@@ -90,13 +93,16 @@ def main(argv=None):
                    help="final-logit soft cap of a checkpoint trained with one whose config does not carry it")
     p.add_argument("--attn_softcap", type=float, default=None, metavar="CAP",
                    help="attention-score soft cap of a checkpoint trained with one whose config does not carry it")
+    p.add_argument("--post_norm", action="store_true", default=None,
+                   help="the checkpoint has post-norms (attn_post_norm / mlp_post_norm weights) and its config "
+                        "does not say so")
     args = p.parse_args(argv)
     if args.seed is not None:
         torch.manual_seed(args.seed)
     dev = pick_device(args.device)
     model = load_model(args.checkpoint, args.model_size, dev, args.num_kv_heads, args.qk_norm, args.sliding_window,
                        args.sliding_window_pattern, args.attention_sinks, args.logit_softcap,
-                       args.attn_softcap)
+                       args.attn_softcap, args.post_norm)
     tok = get_tokenizer(args.tokenizer)
     ids = torch.tensor([tok.encode(args.prompt)], dtype=torch.long, device=dev)
     out = model.generate(ids, max_new_tokens=args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,

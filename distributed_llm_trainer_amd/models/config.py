@@ -61,6 +61,11 @@ class GPTConfig:
     # the softmax denominator and has no value row: p_j = exp(s_j) / (sum_j exp(s_j) + exp(sink)).
     attention_sinks: bool = False
 
+    # Post-norms (the Gemma-2/3 "sandwich" block, Grok-1 too): a second RMSNorm over hidden_size on
+    # each branch output, before the hidden dropout and the residual add:
+    # h + dropout(attn_post_norm(attention(input_layernorm(h)))), likewise mlp_post_norm.
+    post_norm: bool = False
+
     # Final-logit soft-capping (Gemma-2's rule, cap 30 there): the model's logits are
     # cap * tanh(lm_head(norm(h)) / cap), in training, evaluation and generation alike.  None = off.
     logit_softcap: Optional[float] = None
@@ -91,6 +96,9 @@ class GPTConfig:
         if not isinstance(self.attention_sinks, (bool, int)) or self.attention_sinks not in (0, 1):
             raise ValueError(f"attention_sinks ({self.attention_sinks!r}) must be a bool")
         self.attention_sinks = bool(self.attention_sinks)
+        if not isinstance(self.post_norm, (bool, int)) or self.post_norm not in (0, 1):
+            raise ValueError(f"post_norm ({self.post_norm!r}) must be a bool")
+        self.post_norm = bool(self.post_norm)
         if self.sliding_window is not None:
             if isinstance(self.sliding_window, bool) or int(self.sliding_window) != self.sliding_window \
                     or self.sliding_window < 1:
@@ -178,6 +186,8 @@ class GPTConfig:
             per_layer += 2 * self.head_dim  # q_norm, k_norm
         if self.attention_sinks:
             per_layer += self.num_heads  # sinks
+        if self.post_norm:
+            per_layer += 2 * h  # attn_post_norm, mlp_post_norm
         return self.vocab_size * h + self.num_layers * per_layer + h
 
     def num_parameters_legacy(self) -> int:
@@ -220,13 +230,16 @@ class GPTConfig:
             del d["qk_norm"]
         if not self.attention_sinks:  # ... and configs without attention sinks
             del d["attention_sinks"]
+        if not self.post_norm:  # ... and configs without post-norms
+            del d["post_norm"]
         for k in ("sliding_window", "sliding_window_pattern", "logit_softcap", "attn_softcap"):  # ... and unwindowed / uncapped ones
             if d[k] is None:
                 del d[k]
         return d
 
     # Pickled configs (checkpoints) follow to_dict(): an MHA config carries no num_kv_heads, one
-    # without QK-norm no qk_norm and one without sinks no attention_sinks, so their pickles are
+    # without QK-norm no qk_norm, one without sinks no attention_sinks and one without post-norms
+    # no post_norm, so their pickles are
     # what they were before the fields existed and older pickles load.
     def __getstate__(self) -> Dict[str, Any]:
         state = dict(self.__dict__)
@@ -236,6 +249,8 @@ class GPTConfig:
             state.pop("qk_norm", None)
         if not state.get("attention_sinks"):
             state.pop("attention_sinks", None)
+        if not state.get("post_norm"):
+            state.pop("post_norm", None)
         for k in ("sliding_window", "sliding_window_pattern", "logit_softcap", "attn_softcap"):
             if state.get(k) is None:
                 state.pop(k, None)
@@ -247,6 +262,7 @@ class GPTConfig:
             self.num_kv_heads = self.num_heads
         self.qk_norm = bool(self.__dict__.get("qk_norm", False))
         self.attention_sinks = bool(self.__dict__.get("attention_sinks", False))
+        self.post_norm = bool(self.__dict__.get("post_norm", False))
         self.__dict__.setdefault("sliding_window", None)
         self.__dict__.setdefault("sliding_window_pattern", None)
         self.__dict__.setdefault("logit_softcap", None)

@@ -23,6 +23,10 @@ autocast path):
         d      = s @ Wdown^T                             [GEMM]  -> (x2, d) to next layer
   head: xf,nf  = add_dropout_rmsnorm(x2, d); logits = nf @ E^T; CE + dlogits in place.
 
+  A post-norm model (cfg.post_norm) norms each branch before its dropout and residual add:
+  x2,n2 = postnorm_add_dropout_rmsnorm(x, a) in place of the second fused kernel, and
+  d = postnorm(s @ Wdown^T); the backward undoes them with postnorm_bwd in place.
+
   The attention backward writes dq/dk/dv straight into the packed [M, 3H] gradient
   with the inverse RoPE rotation applied in its epilogue (no repack kernel).
 
@@ -76,6 +80,8 @@ class LayerWeights:
     qn: Any = None       # QK-norm (cfg.qk_norm): q_norm / k_norm weights [head_dim], else None
     kn: Any = None
     sk: Any = None       # attention sinks (cfg.attention_sinks): [num_heads] logits, else None
+    pn1: Any = None      # post-norms (cfg.post_norm): attn_post_norm / mlp_post_norm weights [H], else None
+    pn2: Any = None
 
 
 @dataclass
@@ -89,6 +95,8 @@ class LayerGrads:
     qn: Any = None       # fp32 [head_dim] gradients of q_norm / k_norm (cfg.qk_norm)
     kn: Any = None
     sk: Any = None       # fp32 [num_heads] gradient of the attention sinks (cfg.attention_sinks)
+    pn1: Any = None      # fp32 [H] gradients of attn_post_norm / mlp_post_norm (cfg.post_norm)
+    pn2: Any = None
 
 
 @dataclass
@@ -155,11 +163,13 @@ class _LayerCache:
     v: Any = None
     o: Any = None
     lse: Any = None
+    a: Any = None      # post-norms: the raw o_proj output [M, H] (attn_post_norm's input), kept like o
     x2: Any = None
     rstd2: Any = None
     n2: Any = None
     gu: Any = None
     s: Any = None
+    dr: Any = None     # post-norms: the raw down_proj output [M, H] (mlp_post_norm's input), kept like o
 
 
 @dataclass
@@ -293,6 +303,16 @@ class GPTEngine:
         # softcap= (the CAP kernels rebuild tanh from q and k, so nothing new is kept); an uncapped
         # model passes no keyword
         self.attn_softcap = getattr(cfg, "attn_softcap", None)
+        # post-norms (cfg.post_norm): a second RMSNorm on each branch output before the hidden dropout
+        # and the residual add.  Attention site: postnorm_add_dropout_rmsnorm_fwd replaces the
+        # add_dropout_rmsnorm_fwd call (the normed branch stays in registers).  MLP site: postnorm_fwd on
+        # the down projection's output, whose result travels on as d.  Backward: postnorm_bwd rewrites
+        # the gradient the following norm's backward left (da, g_d) in place, from the kept raw branch
+        # outputs (c.a, c.dr: +4 * M * H bytes per kept layer under selective checkpointing)
+        self.post_norm = bool(getattr(cfg, "post_norm", False))
+        if self.post_norm and getattr(ops, "backend", "") == "hip" and act_dtype == torch.float32:
+            raise NotImplementedError("this model on the GPU: fp32 activations have no post-norm kernels "
+                                      "(post_norm); use bf16 or fp16 activations")
         if getattr(ops, "backend", "") == "hip":  # the GPU routes; the reference ops have every feature
             attn_routes.check_attention_features("cuda", cfg.head_dim, act_dtype, attn_routes.config_features(cfg),
                                                  self.packed_qkv)
@@ -682,20 +702,31 @@ class GPTEngine:
         else:
             o, lse = ops.attention_fwd(q, k, v, pa, k_attn, True, out=sb("o", H), **kw)
         a = gm.linear(o, w.wo)
-        x2, n2, rstd2 = ops.add_dropout_rmsnorm_fwd(x, a, w.ln2, self.eps, ph, k_resid, self.act_dtype,
-                                                    y_out=sb("n2", H))
-        del a
+        if self.post_norm:
+            x2, n2, rstd2 = ops.postnorm_add_dropout_rmsnorm_fwd(x, a, w.pn1, w.ln2, self.eps, ph, k_resid,
+                                                                 self.act_dtype, y_out=sb("n2", H))
+        else:
+            x2, n2, rstd2 = ops.add_dropout_rmsnorm_fwd(x, a, w.ln2, self.eps, ph, k_resid, self.act_dtype,
+                                                        y_out=sb("n2", H))
+            del a
         gu, s = self._gate_up(st, i, w, n2)
         d_out = gm.linear(s, w.wdown)
+        pn_kept = {}
+        if self.post_norm:
+            # the raw branch outputs are the post-norm backward's inputs; the normed MLP branch
+            # travels on as d (the next layer's, or the final norm's, delta)
+            pn_kept = {"a": a, "dr": d_out}
+            del a
+            d_out = ops.postnorm_fwd(d_out, w.pn2, self.eps)
         if self._s_in_ring(st) or self._refill_s(st):  # a temporary: the backward rewrites s
             s = None
         if save:
             c = _LayerCache(x=x, rstd1=rstd1, n1=n1, q=q, raw=raw, k=k, v=v, o=o, lse=lse,
-                            x2=x2, rstd2=rstd2, n2=n2, gu=gu, s=s)
+                            x2=x2, rstd2=rstd2, n2=n2, gu=gu, s=s, **pn_kept)
         elif st.recompute:
             if self.selective_recompute:
                 keep_qkv, keep_gu, keep_rest = self._ac_keep(M)
-                c = _LayerCache(x=x, o=o, lse=lse, x2=x2)
+                c = _LayerCache(x=x, o=o, lse=lse, x2=x2, **pn_kept)
                 if keep_qkv and self.packed_qkv:
                     c.q, c.raw = q, raw
                 if keep_gu:
@@ -732,7 +763,7 @@ class GPTEngine:
                                                    y_out=sb("n2", H))
         gu, s = self._gate_up(st, i, w, n2, kept=c.gu, need_s=not self._s_in_ring(st))
         return _LayerCache(x=c.x, rstd1=rstd1, n1=n1, q=q, raw=raw, k=k, v=v, o=c.o, lse=c.lse,
-                           x2=c.x2, rstd2=rstd2, n2=n2, gu=gu, s=s)
+                           x2=c.x2, rstd2=rstd2, n2=n2, gu=gu, s=s, a=c.a, dr=c.dr)
 
     def forward(self, ids: torch.Tensor, targets: Optional[torch.Tensor], train: bool,
                 recompute: bool = False, return_logits: bool = False,
@@ -1192,6 +1223,12 @@ class GPTEngine:
                 c = self._layer_recompute(st, i, c)
             w, gr = prov.layer(i), prov.layer_grads(i)
             k_attn, k_resid, k_mlp = self._keys(st.micro, i)
+            if self.post_norm:
+                # g_d (this layer's dd slot) holds dL/d(normed MLP branch): mlp_post_norm's backward
+                # rewrites it in place, and the down data- and weight-gradient GEMMs (per micro-step
+                # or window-deferred) read the slot after it.  gr.pn1 / gr.pn2 are shared with the
+                # other micro-steps like gr.ln1 / gr.ln2: between wait_prev(i) and mark(i)
+                ops.postnorm_bwd(g_d, c.dr, w.pn2, self.eps, gr.pn2)
             # MLP
             # s ring: the SwiGLU backward also rewrites s (the down wgrad operand) into
             # layer i's ring slot, from the same gu with the forward's arithmetic
@@ -1210,6 +1247,8 @@ class GPTEngine:
             dx2, da = ops.rmsnorm_bwd(dn2, c.x2, c.rstd2, w.ln2, g_x2, gr.ln2, ph, k_resid,
                                       ddelta_out=sb(i, "da", H))
             del dn2
+            if self.post_norm:  # da: dL/d(normed attention branch) -> dL/d(o_proj output), in place
+                ops.postnorm_bwd(da, c.a, w.pn1, self.eps, gr.pn1)
             # attention
             dkw = self._attn_kw(st, i, w, gr)
             do = gm.linear_dgrad(da, w.wo)

@@ -116,10 +116,11 @@ class CausalSelfAttention(nn.Module):
         self.attn_softcap = getattr(config, "attn_softcap", None)
 
     def forward(self, hidden_states: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
-                doc_hidden: Optional[torch.Tensor] = None):
+                doc_hidden: Optional[torch.Tensor] = None, post_norm: Optional[nn.Module] = None):
         """``doc_hidden``: bool [B, 1, S, S], True where a query must not see a key because
         it lies before the query's document (``GPT.set_doc_separator``); applied on top of
-        the causal mask in both the naive and the SDPA setting."""
+        the causal mask in both the naive and the SDPA setting.  ``post_norm``: the block's
+        attn_post_norm (config.post_norm), applied to the o_proj output before the dropout."""
         B, S, _ = hidden_states.shape
         q = self.q_proj(hidden_states).view(B, S, self.num_heads, self.head_dim).transpose(1, 2)
         k = self.k_proj(hidden_states).view(B, S, self.num_kv_heads, self.head_dim).transpose(1, 2)
@@ -173,7 +174,10 @@ class CausalSelfAttention(nn.Module):
             probs = F.softmax(scores, dim=-1, dtype=torch.float32).to(scores.dtype)
             out = self.attn_dropout(probs) @ v
         out = out.transpose(1, 2).contiguous().view(B, S, -1)
-        return self.resid_dropout(self.o_proj(out))
+        out = self.o_proj(out)
+        if post_norm is not None:
+            out = post_norm(out)
+        return self.resid_dropout(out)
 
 
 class MLP(nn.Module):
@@ -184,8 +188,13 @@ class MLP(nn.Module):
         self.down_proj = nn.Linear(config.intermediate_size, config.hidden_size, bias=False)
         self.dropout = nn.Dropout(config.dropout)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return self.dropout(self.down_proj(F.silu(self.gate_proj(x)) * self.up_proj(x)))
+    def forward(self, x: torch.Tensor, post_norm: Optional[nn.Module] = None) -> torch.Tensor:
+        """``post_norm``: the block's mlp_post_norm (config.post_norm), applied to the down_proj
+        output before the dropout."""
+        out = self.down_proj(F.silu(self.gate_proj(x)) * self.up_proj(x))
+        if post_norm is not None:
+            out = post_norm(out)
+        return self.dropout(out)
 
 
 class TransformerBlock(nn.Module):
@@ -198,8 +207,19 @@ class TransformerBlock(nn.Module):
         self.attention = CausalSelfAttention(config, config.layer_window(layer_idx))
         self.post_attention_layernorm = RMSNorm(config.hidden_size)
         self.mlp = MLP(config)
+        # Post-norms (config.post_norm): a second RMSNorm on each branch output, before its
+        # dropout and the residual add.  Without the flag the modules (and their state-dict
+        # keys) do not exist; post_attention_layernorm stays the pre-MLP norm either way.
+        self.post_norm = bool(getattr(config, "post_norm", False))
+        if self.post_norm:
+            self.attn_post_norm = RMSNorm(config.hidden_size)
+            self.mlp_post_norm = RMSNorm(config.hidden_size)
 
     def forward(self, hidden_states, attention_mask=None, doc_hidden=None):
+        if self.post_norm:
+            h = hidden_states + self.attention(self.input_layernorm(hidden_states), attention_mask, doc_hidden,
+                                               post_norm=self.attn_post_norm)
+            return h + self.mlp(self.post_attention_layernorm(h), post_norm=self.mlp_post_norm)
         h = hidden_states + self.attention(self.input_layernorm(hidden_states), attention_mask, doc_hidden)
         return h + self.mlp(self.post_attention_layernorm(h))
 
@@ -298,6 +318,9 @@ class GPT(nn.Module):
         if ops is None or ops.backend == "hip":  # before anything is re-homed
             ops_mod.check_attention_features(dev, self.config.head_dim, act_dtype,
                                              ops_mod.attn_routes.config_features(self.config))
+            if getattr(self.config, "post_norm", False) and dev.type == "cuda" and act_dtype == torch.float32:
+                raise NotImplementedError("this model on the GPU: fp32 activations have no post-norm kernels "
+                                          "(post_norm); use bf16 or fp16 activations")
         if provider is None:
             from ..parallel.flat import FlatParamStore
             provider = FlatParamStore(self, dev, compute_dtype=compute_dtype)

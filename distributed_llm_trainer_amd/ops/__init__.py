@@ -18,7 +18,8 @@ _FUNCS = ("rope_tables", "embedding_fwd", "embedding_bwd", "add_dropout_rmsnorm_
           "rope_qkv_fwd", "rope_qkv_bwd", "attention_fwd", "attention_bwd", "swiglu_fwd", "swiglu_bwd",
           "cross_entropy_fwd_bwd", "scale_bf16", "rope_qk_inplace", "attention_fwd_packed",
           "attention_bwd_packed", "lmhead_loss", "lmhead_loss_fits", "doc_bounds", "qknorm_rope_inplace",
-          "qknorm_bwd", "window_bounds")
+          "qknorm_bwd", "window_bounds", "postnorm_fwd", "postnorm_add_dropout_rmsnorm_fwd", "postnorm_bwd",
+          "postnorm_bwd_workspace")
 
 
 def _namespace(mod, name):

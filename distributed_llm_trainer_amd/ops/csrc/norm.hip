@@ -395,6 +395,212 @@ DLT_API int dlt_qknorm_bwd(bf16_t* dqkv, const bf16_t* raw, const float* qw, con
   DLT_CHECK_LAUNCH();
 }
 
+// Post-norms (cfg.post_norm, the Gemma-2/3 sandwich block): a second RMSNorm on a branch
+// output a (the o_proj / down_proj GEMM output as rounded to the activation format), before the
+// hidden dropout and the residual add:  u = round(a * rsqrt(mean(a^2) + eps) * w), fp32 math,
+// one rounding.  Same row layout as the kernels above: one wave per row, NCH chunks per lane.
+//
+// k_postnorm_fwd: a -> u, out of place (the MLP site: u is the next layer's delta).
+template <int NCH, int HK = 0>
+__global__ __launch_bounds__(256) void k_postnorm_fwd(const bf16_t* __restrict__ a, const void* __restrict__ w,
+                                                      int w16, bf16_t* __restrict__ u_out, int M, int H, float eps) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const int nc = H >> 2;
+  const size_t rbase = (size_t)row * H;
+  float av[NCH][4];
+  float sa = 0.f;
+#pragma unroll
+  for (int t = 0; t < NCH; ++t) {
+    const int c = lane + 64 * t;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) av[t][e] = 0.f;
+    if (c < nc) {
+      ld_h4<HK>(a + rbase + (size_t)c * 4, av[t]);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) sa += av[t][e] * av[t][e];
+    }
+  }
+  sa = wave_sum(sa);
+  const float rstd = rsqrtf(sa / (float)H + eps);
+#pragma unroll
+  for (int t = 0; t < NCH; ++t) {
+    const int c = lane + 64 * t;
+    if (c < nc) {
+      const f4 ww = ld_w4<HK>(w, w16, c * 4);
+      u16x4 u;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) u.v[e] = f2h<HK>(av[t][e] * rstd * ww.v[e]);
+      *reinterpret_cast<u16x4*>(u_out + rbase + (size_t)c * 4) = u;
+    }
+  }
+}
+
+// The attention site, fused: k_postnorm_fwd followed by k_add_dropout_rmsnorm_fwd in one pass.
+// u is formed in registers and rounded to the activation format exactly as k_postnorm_fwd
+// stores it, then takes the place of that kernel's delta (same dropout hash, same order of the
+// fp32 operations), so x, y and rstd have the bits of the two-kernel sequence; u itself never
+// goes to memory.  Two wave reductions per row (mean(a^2), mean(x^2)); every load of the row
+// is issued before the first.
+template <int NCH, bool XNT = false, int HK = 0>
+__global__ __launch_bounds__(256) void k_postnorm_add_dropout_rmsnorm_fwd(
+    const float* __restrict__ resid, const bf16_t* __restrict__ a, const void* __restrict__ wp, int wp16,
+    const void* __restrict__ w, int w16, float* __restrict__ x_out, bf16_t* __restrict__ y_out,
+    float* __restrict__ rstd_out, int M, int H, float eps, uint32_t key, uint32_t thr, float dscale) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const int nc = H >> 2;
+  const size_t rbase = (size_t)row * H;
+  float av[NCH][4], xv[NCH][4];
+  float sa = 0.f;
+#pragma unroll
+  for (int t = 0; t < NCH; ++t) {
+    const int c = lane + 64 * t;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { av[t][e] = 0.f; xv[t][e] = 0.f; }
+    if (c < nc) {
+      const size_t off = rbase + (size_t)c * 4;
+      ld_h4<HK>(a + off, av[t]);
+      const f4 r = ld_f4(resid + off);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        xv[t][e] = r.v[e];
+        sa += av[t][e] * av[t][e];
+      }
+    }
+  }
+  sa = wave_sum(sa);
+  const float rstd_a = rsqrtf(sa / (float)H + eps);
+  float ss = 0.f;
+#pragma unroll
+  for (int t = 0; t < NCH; ++t) {
+    const int c = lane + 64 * t;
+    if (c < nc) {
+      const size_t off = rbase + (size_t)c * 4;
+      const f4 pw = ld_w4<HK>(wp, wp16, c * 4);
+      float d[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) d[e] = h2f<HK>(f2h<HK>(av[t][e] * rstd_a * pw.v[e]));
+      if (thr) {
+#pragma unroll
+        for (int e = 0; e < 4; e += 2) {
+          const uint32_t h = lowbias32(key ^ (uint32_t)((off + e) >> 1));
+          xv[t][e] += ((h & 0xffffu) >= thr) ? d[e] * dscale : 0.f;
+          xv[t][e + 1] += ((h >> 16) >= thr) ? d[e + 1] * dscale : 0.f;
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) xv[t][e] += d[e];
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) ss += xv[t][e] * xv[t][e];
+    }
+  }
+  ss = wave_sum(ss);
+  const float rstd = rsqrtf(ss / (float)H + eps);
+  if (lane == 0) rstd_out[row] = rstd;
+#pragma unroll
+  for (int t = 0; t < NCH; ++t) {
+    const int c = lane + 64 * t;
+    if (c < nc) {
+      const size_t off = rbase + (size_t)c * 4;
+      if (XNT) st_f4_nt(x_out + off, xv[t]);
+      else st_f4(x_out + off, xv[t]);
+      const f4 ww = ld_w4<HK>(w, w16, c * 4);
+      u16x4 y;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) y.v[e] = f2h<HK>(xv[t][e] * rstd * ww.v[e]);
+      *reinterpret_cast<u16x4*>(y_out + off) = y;
+    }
+  }
+}
+
+// Backward of k_postnorm_fwd, in place: du [M, H] holds dL/du (the ddelta k_rmsnorm_bwd wrote,
+// dropout already undone) and is overwritten with
+//   da = rstd * (g - xh * mean(g * xh)),  g = du * w,  xh = a * rstd,
+// rstd recomputed from the kept raw a (as k_qknorm_bwd does from raw); fp32 math, one rounding.
+// dw[j] = sum_rows du * xh: a wave walks rows blockIdx.x * 4 + wid, + gridDim.x * 4, ... and adds
+// into registers, the block sums its four waves through LDS in wave order and writes row
+// blockIdx.x of the fp32 workspace (every block writes its row); k_colsum_acc adds the rows into
+// dw in a fixed order -- no float atomics, two calls give the same bits.
+template <int NCH, int HK = 0>
+__global__ __launch_bounds__(256) void k_postnorm_bwd(bf16_t* du, const bf16_t* __restrict__ a,
+                                                      const void* __restrict__ w, int w16,
+                                                      float* __restrict__ dw_part, int M, int H, float eps) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];  // [4][H]
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  const int nc = H >> 2;
+  const float invH = 1.f / (float)H;
+  float dwacc[NCH][4];
+  float wv[NCH][4];
+#pragma unroll
+  for (int t = 0; t < NCH; ++t) {
+    const int c = lane + 64 * t;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { dwacc[t][e] = 0.f; wv[t][e] = 0.f; }
+    if (c < nc) {
+      const f4 q = ld_w4<HK>(w, w16, c * 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) wv[t][e] = q.v[e];
+    }
+  }
+  for (int row = blockIdx.x * 4 + wid; row < M; row += gridDim.x * 4) {
+    const size_t rbase = (size_t)row * H;
+    float gv[NCH][4], xx[NCH][4];
+    float sa = 0.f;
+#pragma unroll
+    for (int t = 0; t < NCH; ++t) {
+      const int c = lane + 64 * t;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { gv[t][e] = 0.f; xx[t][e] = 0.f; }
+      if (c < nc) {
+        const size_t off = rbase + (size_t)c * 4;
+        ld_h4<HK>(du + off, gv[t]);
+        ld_h4<HK>(a + off, xx[t]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sa += xx[t][e] * xx[t][e];
+      }
+    }
+    const float rstd = rsqrtf(wave_sum(sa) * invH + eps);
+    float dot = 0.f;
+#pragma unroll
+    for (int t = 0; t < NCH; ++t)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float xh = xx[t][e] * rstd;
+        dwacc[t][e] += gv[t][e] * xh;
+        gv[t][e] *= wv[t][e];  // g
+        xx[t][e] = xh;
+        dot += gv[t][e] * xh;
+      }
+    dot = wave_sum(dot) * invH;
+#pragma unroll
+    for (int t = 0; t < NCH; ++t) {
+      const int c = lane + 64 * t;
+      if (c < nc) {
+        u16x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o.v[e] = f2h<HK>(rstd * (gv[t][e] - xx[t][e] * dot));
+        *reinterpret_cast<u16x4*>(du + rbase + (size_t)c * 4) = o;
+      }
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < NCH; ++t) {
+    const int c = lane + 64 * t;
+    if (c < nc) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) smem[wid * H + c * 4 + e] = dwacc[t][e];
+    }
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < H; j += 256)
+    dw_part[(size_t)blockIdx.x * H + j] = smem[j] + smem[H + j] + smem[2 * H + j] + smem[3 * H + j];
+}
+
 static inline int nch_of(int H) {
   int n = (H / 4 + 63) / 64;
   if (n > 8 && n <= 12) n = 12;
@@ -500,5 +706,82 @@ DLT_API int dlt_rmsnorm_bwd(const bf16_t* dy, const float* x, const float* rstd,
     if (wide) k_colsum_acc<16><<<(H + 63) / 64, 1024, 0, stream>>>(dw_ws, dw, blocks, H);
     else k_colsum_acc<4><<<(H + 15) / 16, 256, 0, stream>>>(dw_ws, dw, blocks, H);
   }
+  DLT_CHECK_LAUNCH();
+}
+
+// ---- post-norm launchers (the limits of the launchers above: H % 4 == 0, H <= 4096) ----
+#define DLT_NCH_SWITCH(nch, LAUNCH) \
+  switch (nch) {                    \
+    case 1: LAUNCH(1); break;       \
+    case 2: LAUNCH(2); break;       \
+    case 3: LAUNCH(3); break;       \
+    case 4: LAUNCH(4); break;       \
+    case 5: LAUNCH(5); break;       \
+    case 6: LAUNCH(6); break;       \
+    case 7: LAUNCH(7); break;       \
+    case 8: LAUNCH(8); break;       \
+    case 12: LAUNCH(12); break;     \
+    default: LAUNCH(16); break;     \
+  }
+
+// a, u_out [M, H] in the activation format hk; w fp32 or (w16) that format
+DLT_API int dlt_postnorm_fwd(const bf16_t* a, const void* w, int w16, bf16_t* u_out, int M, int H, float eps, int hk,
+                             hipStream_t stream) {
+  if (H % 4 != 0 || H > 4096 || H <= 0 || M <= 0) return -1;
+  const dim3 grid((M + 3) / 4), block(256);
+  const int nch = nch_of(H);
+#define LAUNCH(N) k_postnorm_fwd<N, HKC><<<grid, block, 0, stream>>>(a, w, w16, u_out, M, H, eps)
+  DLT_HK_DISPATCH(hk, DLT_NCH_SWITCH(nch, LAUNCH));
+#undef LAUNCH
+  DLT_CHECK_LAUNCH();
+}
+
+// resid, x_out fp32 [M, H]; a, y_out [M, H] in the activation format hk; wp (the post-norm
+// weight) and w (the following pre-norm's) fp32 or 16-bit; rstd_out fp32 [M]
+DLT_API int dlt_postnorm_add_dropout_rmsnorm_fwd(const float* resid, const bf16_t* a, const void* wp, int wp16,
+                                                 const void* w, int w16, float* x_out, bf16_t* y_out,
+                                                 float* rstd_out, int M, int H, float eps, uint32_t key,
+                                                 uint32_t thr, float dscale, int hk, hipStream_t stream) {
+  if (H % 4 != 0 || H > 4096 || H <= 0 || M <= 0) return -1;
+  const dim3 grid((M + 3) / 4), block(256);
+  const int nch = nch_of(H);
+  const bool nt = nch == 3 && fwd_nt();  // x_out as k_add_dropout_rmsnorm_fwd stores it at H = 768
+#define LAUNCH(N)                                                                                              \
+  if (N == 3 && nt)                                                                                            \
+    k_postnorm_add_dropout_rmsnorm_fwd<3, true, HKC><<<grid, block, 0, stream>>>(                              \
+        resid, a, wp, wp16, w, w16, x_out, y_out, rstd_out, M, H, eps, key, thr, dscale);                      \
+  else                                                                                                         \
+    k_postnorm_add_dropout_rmsnorm_fwd<N, false, HKC><<<grid, block, 0, stream>>>(                             \
+        resid, a, wp, wp16, w, w16, x_out, y_out, rstd_out, M, H, eps, key, thr, dscale)
+  DLT_HK_DISPATCH(hk, DLT_NCH_SWITCH(nch, LAUNCH));
+#undef LAUNCH
+  DLT_CHECK_LAUNCH();
+}
+
+// workgroups of k_postnorm_bwd (= rows of its workspace): k_rmsnorm_bwd's rule
+static inline int postnorm_bwd_blocks(int M) {
+  const int b = (M + 3) / 4;
+  return b > 1024 ? 1024 : b;
+}
+
+// floats of the workspace of dlt_postnorm_bwd (blocks x H)
+DLT_API long dlt_postnorm_bwd_ws(int M, int H) {
+  if (H % 4 != 0 || H > 4096 || H <= 0 || M <= 0) return -1;
+  return (long)postnorm_bwd_blocks(M) * H;
+}
+
+// du [M, H] (rewritten in place), a [M, H] in the activation format hk; w fp32 or 16-bit;
+// dw fp32 [H] accumulated; ws: dlt_postnorm_bwd_ws floats
+DLT_API int dlt_postnorm_bwd(bf16_t* du, const bf16_t* a, const void* w, int w16, float* dw, float* ws, int M, int H,
+                             float eps, int hk, hipStream_t stream) {
+  if (H % 4 != 0 || H > 4096 || H <= 0 || M <= 0) return -1;
+  const int blocks = postnorm_bwd_blocks(M);
+  const dim3 grid(blocks), block(256);
+  const size_t shm = (size_t)4 * H * sizeof(float);
+  const int nch = nch_of(H);
+#define LAUNCH(N) k_postnorm_bwd<N, HKC><<<grid, block, shm, stream>>>(du, a, w, w16, ws, M, H, eps)
+  DLT_HK_DISPATCH(hk, DLT_NCH_SWITCH(nch, LAUNCH));
+#undef LAUNCH
+  k_colsum_acc<4><<<(H + 15) / 16, 256, 0, stream>>>(ws, dw, blocks, H);
   DLT_CHECK_LAUNCH();
 }

@@ -93,6 +93,12 @@ _SIGS = {
                                 c_int, c_int, c_int, c_void_p],
     "dlt_qknorm_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int,
                        c_int, c_int, c_int, c_void_p],
+    "dlt_postnorm_fwd": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_int, c_void_p],
+    "dlt_postnorm_add_dropout_rmsnorm_fwd": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                             c_void_p, c_int, c_int, c_float, c_uint32, c_uint32, c_float, c_int,
+                                             c_void_p],
+    "dlt_postnorm_bwd": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_int,
+                         c_void_p],
     "dlt_dec_norm_qkv": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                          c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "dlt_dec_attn": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p],
@@ -153,6 +159,8 @@ def lib():
         L.dlt_lmhead_loss_scratch.restype = ctypes.c_long
         L.dlt_qknorm_bwd_ws.argtypes = [c_int, c_int, c_int]
         L.dlt_qknorm_bwd_ws.restype = ctypes.c_long
+        L.dlt_postnorm_bwd_ws.argtypes = [c_int, c_int]
+        L.dlt_postnorm_bwd_ws.restype = ctypes.c_long
         if L.dlt_attn_args_size() != ctypes.sizeof(_AttnArgs):
             raise RuntimeError(f"{_LIBPATH}: dlt_attn_args is {L.dlt_attn_args_size()} bytes, _AttnArgs "
                                f"{ctypes.sizeof(_AttnArgs)}: rebuild the library (ops/build.py)")
@@ -785,6 +793,113 @@ def qknorm_bwd(dqkv, raw, B, S, nh, qw, kw, eps, dqw, dkw, nkv=None, ws=None):
     _chk(lib().dlt_qknorm_bwd(_p(dqkv), _p(raw), _p(qw), _p(kw), _p(dqw), _p(dkw), _p(ws), float(eps), M, nh, nkv,
                               hd, hk, _stream()), "qknorm_bwd")
     return dqkv
+
+
+# ---------------------------------------------------------------- post-norms
+def _postnorm_dims(a, name: str):
+    """(M, H) of a branch output [M, H] of a post-norm call: 16-bit, H % 4 == 0, H <= 4096."""
+    if not isinstance(a, torch.Tensor) or a.dim() != 2:
+        raise ValueError(f"{name}: expected a [M, H] tensor")
+    if a.dtype == torch.float32:
+        raise NotImplementedError(f"{name}: post-norms are not implemented for fp32 activations on the GPU")
+    if a.dtype not in _HK:
+        raise TypeError(f"{name}: expected bf16 or fp16 activations, got {a.dtype}")
+    M, H = a.shape
+    if M < 1 or H < 4 or H % 4 or H > 4096:
+        raise ValueError(f"{name}: needs M >= 1, H % 4 == 0 and H <= 4096, got [{M}, {H}]")
+    return M, H
+
+
+def _postnorm_weight(w, H: int, act, device, name: str):
+    """(tensor, is_16bit) of an [H] post-norm weight: validated, then as _norm_weight reads it."""
+    if not isinstance(w, torch.Tensor) or not w.is_cuda or w.numel() != H or w.device != device:
+        raise ValueError(f"{name}: expected a GPU tensor of {H} elements on the device of the activations")
+    return _norm_weight(w, H, name, act)
+
+
+def postnorm_fwd(a, w, eps, out=None):
+    """The post-norm of a branch output: u = round(a * rsqrt(mean(a^2) + eps) * w) over the rows of
+    ``a`` [M, H] (bf16 / fp16, as the GEMM rounded it), fp32 math, one rounding; ``w`` [H] fp32 or in
+    the activation format.  Out of place: returns ``out`` (or a new tensor)."""
+    M, H = _postnorm_dims(a, "postnorm_fwd.a")
+    hk = _req_act(a, a.dtype, "postnorm_fwd.a")
+    wt, w16 = _postnorm_weight(w, H, a.dtype, a.device, "postnorm_fwd.w")
+    u = torch.empty_like(a) if out is None else out
+    _req(u, a.dtype, "postnorm_fwd.out", M * H)
+    if u.device != a.device:
+        raise ValueError("postnorm_fwd.out: expected the device of a")
+    if u.data_ptr() == a.data_ptr():
+        raise ValueError("postnorm_fwd.out: the kernel is out of place (the backward reads the raw a)")
+    _chk(lib().dlt_postnorm_fwd(_p(a), _p(wt), w16, _p(u), M, H, float(eps), hk, _stream()), "postnorm_fwd")
+    return u
+
+
+def postnorm_add_dropout_rmsnorm_fwd(resid, a, w_post, w, eps, p, key, out_dtype=torch.bfloat16, y_out=None):
+    """:func:`postnorm_fwd` of ``a`` with ``w_post`` followed by :func:`add_dropout_rmsnorm_fwd`
+    (resid, u, w, ...) in one kernel: the same bits for (x, y, rstd), and the normed branch u
+    never goes to memory.  ``resid`` fp32 [M, H]; ``a`` [M, H] in ``out_dtype``."""
+    if out_dtype == torch.float32:
+        raise NotImplementedError("postnorm_add_dropout_rmsnorm_fwd: post-norms are not implemented for fp32 "
+                                  "activations on the GPU")
+    M, H = _postnorm_dims(a, "postnorm_rmsnorm.a")
+    hk = _req_act(a, out_dtype, "postnorm_rmsnorm.a")
+    if not isinstance(resid, torch.Tensor):
+        raise ValueError("postnorm_rmsnorm.resid: expected the fp32 residual [M, H]")
+    _req(resid, torch.float32, "postnorm_rmsnorm.resid", M * H)
+    if resid.device != a.device:
+        raise ValueError("postnorm_rmsnorm.resid: expected the device of a")
+    if not 0.0 <= float(p) < 1.0:
+        raise ValueError(f"postnorm_rmsnorm: dropout p ({p}) must be in [0, 1)")
+    wp, wp16 = _postnorm_weight(w_post, H, out_dtype, a.device, "postnorm_rmsnorm.w_post")
+    wn, wn16 = _postnorm_weight(w, H, out_dtype, a.device, "postnorm_rmsnorm.w")
+    y = torch.empty(M, H, dtype=out_dtype, device=a.device) if y_out is None else y_out
+    _req(y, out_dtype, "postnorm_rmsnorm.y", M * H)
+    if y.device != a.device:
+        raise ValueError("postnorm_rmsnorm.y: expected the device of a")
+    x = torch.empty(M, H, dtype=torch.float32, device=a.device)
+    rstd = torch.empty(M, dtype=torch.float32, device=a.device)
+    thr = rng.keep_threshold(p)
+    dscale = 1.0 / (1.0 - p) if thr else 1.0
+    _chk(lib().dlt_postnorm_add_dropout_rmsnorm_fwd(_p(resid), _p(a), _p(wp), wp16, _p(wn), wn16, _p(x), _p(y),
+                                                    _p(rstd), M, H, float(eps), key & 0xFFFFFFFF, thr, dscale, hk,
+                                                    _stream()), "postnorm_add_dropout_rmsnorm_fwd")
+    return x, y, rstd
+
+
+def postnorm_bwd_workspace(M: int, H: int, device) -> torch.Tensor:
+    """fp32 workspace of :func:`postnorm_bwd`: the per-workgroup weight-gradient partials."""
+    n = lib().dlt_postnorm_bwd_ws(int(M), int(H))
+    if n <= 0:
+        raise ValueError(f"postnorm_bwd: no kernel for M={M}, H={H}")
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def postnorm_bwd(du, a, w, eps, dw, ws=None):
+    """Backward of :func:`postnorm_fwd`, in place: ``du`` [M, H] (dL/du, 16-bit) is overwritten with
+    da = rstd * (g - xh * mean(g * xh)), g = du * w, xh = a * rstd, rstd recomputed from the raw
+    ``a``; ``dw`` (fp32 [H]) += sum over rows of du * xh, reduced in a fixed order (no atomics)."""
+    M, H = _postnorm_dims(du, "postnorm_bwd.du")
+    hk = _req_act(du, du.dtype, "postnorm_bwd.du")
+    if not isinstance(a, torch.Tensor):
+        raise ValueError("postnorm_bwd.a: expected the raw branch output [M, H]")
+    _req(a, du.dtype, "postnorm_bwd.a", M * H)
+    if tuple(a.shape) != (M, H):
+        raise ValueError(f"postnorm_bwd.a: expected [{M}, {H}], got {list(a.shape)}")
+    if a.data_ptr() == du.data_ptr():
+        raise ValueError("postnorm_bwd.a: must not alias du (du is rewritten in place)")
+    wt, w16 = _postnorm_weight(w, H, du.dtype, du.device, "postnorm_bwd.w")
+    _req(dw, torch.float32, "postnorm_bwd.dw", H)
+    n_ws = lib().dlt_postnorm_bwd_ws(M, H)
+    if ws is None:
+        ws = torch.empty(n_ws, dtype=torch.float32, device=du.device)
+    else:
+        _req(ws, torch.float32, "postnorm_bwd.ws", n_ws)
+    for t, n in ((a, "a"), (dw, "dw"), (ws, "ws")):
+        if t.device != du.device:
+            raise ValueError(f"postnorm_bwd.{n}: expected the device of du")
+    _chk(lib().dlt_postnorm_bwd(_p(du), _p(a), _p(wt), w16, _p(dw), _p(ws), M, H, float(eps), hk, _stream()),
+         "postnorm_bwd")
+    return du
 
 
 def _off(t: torch.Tensor, elems: int):

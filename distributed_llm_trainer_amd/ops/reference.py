@@ -88,10 +88,59 @@ def rmsnorm_bwd(dy: torch.Tensor, x: torch.Tensor, rstd: torch.Tensor, weight: t
     ddelta = None
     if want_ddelta:
         ddelta = dropout_apply(dx, key_prev, p_prev).to(out_dt)
+        if ddelta is dx:  # fp32 without dropout: its own tensor, as the kernels' (postnorm_bwd rewrites it in place)
+            ddelta = dx.clone()
         if ddelta_out is not None:
             ddelta_out.copy_(ddelta)
             ddelta = ddelta_out
     return dx, ddelta
+
+
+# ---------------------------------------------------------------- post-norms
+def _postnorm_check(a: torch.Tensor, name: str) -> None:
+    if a.dim() != 2:
+        raise ValueError(f"{name}: expected [M, H], got {list(a.shape)}")
+
+
+def postnorm_fwd(a: torch.Tensor, w: torch.Tensor, eps: float, out=None) -> torch.Tensor:
+    """The post-norm of a branch output (cfg.post_norm): u = a * rsqrt(mean(a^2) + eps) * w over
+    the rows of ``a`` [M, H] (the GEMM output as rounded to the activation dtype), fp32 math,
+    rounded once to a's dtype.  Out of place."""
+    _postnorm_check(a, "postnorm_fwd.a")
+    x = a.float()
+    u = (x * torch.rsqrt(x.pow(2).mean(dim=-1, keepdim=True) + eps) * w.float()).to(a.dtype)
+    if out is not None:
+        out.copy_(u)
+        return out
+    return u
+
+
+def postnorm_add_dropout_rmsnorm_fwd(resid: torch.Tensor, a: torch.Tensor, w_post: torch.Tensor, w: torch.Tensor,
+                                     eps: float, p: float, key: int, out_dtype=torch.bfloat16, y_out=None):
+    """:func:`postnorm_fwd` of ``a`` then :func:`add_dropout_rmsnorm_fwd` with the rounded u as its
+    delta (the HIP kernel fuses the two; the rounding of u is part of the definition)."""
+    return add_dropout_rmsnorm_fwd(resid, postnorm_fwd(a, w_post, eps), w, eps, p, key, out_dtype, y_out=y_out)
+
+
+def postnorm_bwd_workspace(M: int, H: int, device):
+    """The HIP kernel's weight-gradient workspace; the reference needs none."""
+    return None
+
+
+def postnorm_bwd(du: torch.Tensor, a: torch.Tensor, w: torch.Tensor, eps: float, dw: torch.Tensor, ws=None):
+    """Backward of :func:`postnorm_fwd`, in place: ``du`` (dL/du) is overwritten with
+    da = rstd * (g - xh * mean(g * xh)), g = du * w, xh = a * rstd, rstd from the raw ``a``; fp32
+    math, rounded once.  ``dw`` += sum over rows of du * xh."""
+    _postnorm_check(du, "postnorm_bwd.du")
+    if a.shape != du.shape or a.dtype != du.dtype:
+        raise ValueError("postnorm_bwd.a: expected the shape and dtype of du")
+    x, g0 = a.float(), du.float()
+    rstd = torch.rsqrt(x.pow(2).mean(dim=-1, keepdim=True) + eps)
+    xh = x * rstd
+    g = g0 * w.float()
+    dw += (g0 * xh).sum(dim=0).to(dw.dtype)
+    du.copy_((rstd * (g - xh * (g * xh).mean(dim=-1, keepdim=True))).to(du.dtype))
+    return du
 
 
 # ------------------------------------------------------------------- RoPE

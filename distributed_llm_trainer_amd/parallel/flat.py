@@ -86,6 +86,11 @@ class FlatLayout:
                 # later segment stays 16-byte aligned in the fp32 buffers and the bf16 shadow.
                 # The padding is zero and stays zero under AdamW (zero gradient, no decay).
                 add(f"layers.{i}.attention.sinks", (cfg.num_heads,), alloc=sinks_alloc(cfg.num_heads))
+            if getattr(cfg, "post_norm", False):
+                # post-norm weights (no decay): the tail of the layer's norm segment, after
+                # ln1 | ln2 | q_norm | k_norm | sinks+padding, so no earlier offset moves
+                add(f"layers.{i}.attn_post_norm.weight", (H,))
+                add(f"layers.{i}.mlp_post_norm.weight", (H,))
         add("norm.weight", (H,))
         self.total = off
         self.segments = segs
@@ -149,6 +154,7 @@ class FlatParamStore(ParamProvider):
             return buf[s.offset:s.offset + s.numel]
 
         self._layers, self._lgrads = [], []
+        pn = bool(getattr(cfg, "post_norm", False))
         for i in range(cfg.num_layers):
             p = f"layers.{i}."
             self._layers.append(LayerWeights(
@@ -160,7 +166,9 @@ class FlatParamStore(ParamProvider):
                 ln2=vec(self.flat, p + "post_attention_layernorm.weight"),
                 qn=vec(self.flat, p + "attention.q_norm.weight") if cfg.qk_norm else None,
                 kn=vec(self.flat, p + "attention.k_norm.weight") if cfg.qk_norm else None,
-                sk=vec(self.flat, p + "attention.sinks") if cfg.attention_sinks else None))
+                sk=vec(self.flat, p + "attention.sinks") if cfg.attention_sinks else None,
+                pn1=vec(self.flat, p + "attn_post_norm.weight") if pn else None,
+                pn2=vec(self.flat, p + "mlp_post_norm.weight") if pn else None))
             self._lgrads.append(LayerGrads(
                 wqkv=v(self.grad, p + "attention.q_proj.weight", QKV, H),
                 wo=v(self.grad, p + "attention.o_proj.weight", H, H),
@@ -170,7 +178,9 @@ class FlatParamStore(ParamProvider):
                 ln2=vec(self.grad, p + "post_attention_layernorm.weight"),
                 qn=vec(self.grad, p + "attention.q_norm.weight") if cfg.qk_norm else None,
                 kn=vec(self.grad, p + "attention.k_norm.weight") if cfg.qk_norm else None,
-                sk=vec(self.grad, p + "attention.sinks") if cfg.attention_sinks else None))
+                sk=vec(self.grad, p + "attention.sinks") if cfg.attention_sinks else None,
+                pn1=vec(self.grad, p + "attn_post_norm.weight") if pn else None,
+                pn2=vec(self.grad, p + "mlp_post_norm.weight") if pn else None))
         e = bn["embed_tokens.weight"]
         self._head = HeadWeights(
             embed=self.flat[e.offset:e.offset + e.numel].view(e.shape),
@@ -202,6 +212,10 @@ class FlatParamStore(ParamProvider):
                 sk = bn[f"layers.{i}.attention.sinks"]
                 assert sk.offset == end
                 end = sk.offset + sinks_alloc(sk.numel)
+            if getattr(self.cfg, "post_norm", False):  # then the two post-norm weights
+                p2 = bn[f"layers.{i}.mlp_post_norm.weight"]
+                assert bn[f"layers.{i}.attn_post_norm.weight"].offset == end and p2.offset == end + H
+                end = p2.offset + H
             units[i] = [(a, b), (n1.offset, end)]
         return units
 

@@ -89,7 +89,7 @@ class FlatUnit:
         self.host_bufs = []      # cpu_offload: pinned staging buffers, one per pending reduce
         self.refs = 0            # chains (forward / backward of a micro-step) using `full`
         self.ready_ev = None     # HIP event: `full` is complete (recorded after the gather wait)
-        self.norm_grad = None    # bf16-gradient mode: fp32 ln1 | ln2 (| q_norm | k_norm | sinks) gradients
+        self.norm_grad = None    # bf16-gradient mode: fp32 ln1 | ln2 (| q_norm | k_norm | sinks | post-norms) gradients
         self.head_q = []         # root unit: gradient buffers of backwards issued but not yet reduced
 
     def local_slice(self) -> Tuple[int, int]:
@@ -198,6 +198,9 @@ class FSDPRuntime(ParamProvider):
                 add(p + "attention.k_norm.weight", (cfg.head_dim,))
             if cfg.attention_sinks:  # [num_heads] sink logits, allocated rounded up to 8 (FlatLayout)
                 add(p + "attention.sinks", (cfg.num_heads,), alloc=sinks_alloc(cfg.num_heads))
+            if getattr(cfg, "post_norm", False):  # post-norm weights: the tail of the unit (FlatLayout's order)
+                add(p + "attn_post_norm.weight", (H,))
+                add(p + "mlp_post_norm.weight", (H,))
         return segs, off
 
     @torch.no_grad()
@@ -404,21 +407,28 @@ class FSDPRuntime(ParamProvider):
         raise KeyError(name)
 
     def _qk_views(self, u: FlatUnit, buf: torch.Tensor, p: str) -> dict:
-        """The qn / kn fields (QK-norm weights or gradients) and the sk field (attention sinks)
-        of a layer unit's buffer; empty without cfg.qk_norm / cfg.attention_sinks."""
+        """The qn / kn fields (QK-norm weights or gradients), the sk field (attention sinks) and the
+        pn1 / pn2 fields (post-norms) of a layer unit's buffer; empty without cfg.qk_norm /
+        cfg.attention_sinks / cfg.post_norm."""
         d = {}
         if self.cfg.qk_norm:
             d["qn"] = self._view(u, buf, p + "attention.q_norm.weight")
             d["kn"] = self._view(u, buf, p + "attention.k_norm.weight")
         if self.cfg.attention_sinks:
             d["sk"] = self._view(u, buf, p + "attention.sinks")
+        if getattr(self.cfg, "post_norm", False):
+            d["pn1"] = self._view(u, buf, p + "attn_post_norm.weight")
+            d["pn2"] = self._view(u, buf, p + "mlp_post_norm.weight")
         return d
 
     def _side_numel(self) -> int:
-        """Elements of the fp32 side buffer of the bf16-gradient mode: ln1 | ln2 | q_norm | k_norm | sinks."""
+        """Elements of the fp32 side buffer of the bf16-gradient mode: ln1 | ln2 | q_norm | k_norm | sinks
+        (allocated rounded up to 8, so what follows stays 16-byte aligned) | attn_post_norm | mlp_post_norm."""
         cfg = self.cfg
-        return 2 * cfg.hidden_size + (2 * cfg.head_dim if cfg.qk_norm else 0) + \
-            (cfg.num_heads if cfg.attention_sinks else 0)
+        pn = getattr(cfg, "post_norm", False)
+        sk = (sinks_alloc(cfg.num_heads) if pn else cfg.num_heads) if cfg.attention_sinks else 0
+        return 2 * cfg.hidden_size + (2 * cfg.head_dim if cfg.qk_norm else 0) + sk + \
+            (2 * cfg.hidden_size if pn else 0)
 
     def _qk_side(self, norm_grad: torch.Tensor) -> dict:
         """The same fields in the fp32 side buffer of the bf16-gradient mode (after ln1 | ln2)."""
@@ -429,6 +439,10 @@ class FSDPRuntime(ParamProvider):
             off += 2 * cfg.head_dim
         if cfg.attention_sinks:
             d["sk"] = norm_grad[off:off + cfg.num_heads]
+            off += sinks_alloc(cfg.num_heads)
+        if getattr(cfg, "post_norm", False):
+            H = cfg.hidden_size
+            d["pn1"], d["pn2"] = norm_grad[off:off + H], norm_grad[off + H:off + 2 * H]
         return d
 
     def layer(self, i):

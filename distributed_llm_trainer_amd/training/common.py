@@ -280,6 +280,11 @@ def add_model_args(p) -> None:
                         "before the masks and the softmax (a finite CAP > 0; Gemma-2 uses 50), in training, "
                         "evaluation and generation, and saved in checkpoints.  Overrides the YAML's "
                         "model.attn_softcap and the preset (default: off)")
+    p.add_argument("--post_norm", action="store_true", default=None,
+                   help="post-norms (the Gemma-2/3 sandwich block): a second RMSNorm on the attention and the MLP "
+                        "branch output, before the hidden dropout and the residual add, with an attn_post_norm "
+                        "and an mlp_post_norm weight per layer.  Overrides the YAML's model.post_norm and the "
+                        "preset (default: off)")
 
 
 def apply_model_args(args, model_config) -> None:
@@ -293,6 +298,8 @@ def apply_model_args(args, model_config) -> None:
         model_config.qk_norm = bool(args.qk_norm)
     if getattr(args, "attention_sinks", None) is not None:
         model_config.attention_sinks = bool(args.attention_sinks)
+    if getattr(args, "post_norm", None) is not None:
+        model_config.post_norm = bool(args.post_norm)
     sw, swp = getattr(args, "sliding_window", None), getattr(args, "sliding_window_pattern", None)
     cap = getattr(args, "logit_softcap", None)
     acap = getattr(args, "attn_softcap", None)
