@@ -640,8 +640,10 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16(const bf16_t* __restrict__
               gb_unpack(gb_pack(acc[t + 3][mt]), x2);
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
-                acc[t][mt][e] = x1[e] * cc[e] - x2[e] * ss[e];
-                acc[t + 3][mt][e] = x2[e] * cc[e] + x1[e] * ss[e];
+                // one explicit product and one fma each: left to the compiler, the two staging
+                // forms contracted a * c - b * s differently and differed in a bf16 ulp
+                acc[t][mt][e] = __builtin_fmaf(x1[e], cc[e], -(x2[e] * ss[e]));
+                acc[t + 3][mt][e] = __builtin_fmaf(x2[e], cc[e], x1[e] * ss[e]);
               }
             }
           }

@@ -1760,7 +1760,7 @@ def gemm_bf16_fits192(M: int, N: int, K: int) -> bool:
 def gemm_bf16(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
     """C[M,N] = A[M,K] @ B[N,K]^T (bf16 or fp16 in/out, one format; fp32 accumulate) with
     the hand-written persistent MFMA kernel.  Returns None (nothing launched) when the
-    shape does not tile (M % 256, N % 192, K % 128)."""
+    shape does not tile (M % 256, N % 192 or N % 128, K % 128)."""
     M, K = a.shape
     N = b.shape[0]
     if not gemm_bf16_fits(M, N, K) or b.shape[1] != K:
@@ -1919,7 +1919,7 @@ def gemm_dgrad(dy: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = 
     """dX[M, Nout] = dY[M, Nred] @ W[Nred, Nout] with W read as stored (the data gradient
     of a projection y = x @ W^T) by the hand-written persistent MFMA kernel in its
     reduction-major-B form; bf16 or fp16 (all three tensors one dtype).  None (nothing
-    launched) when the shape does not tile (M % 256, Nout % 192, Nred % 128)."""
+    launched) when the shape does not tile (M % 256, Nout % 192 or Nout % 128, Nred % 128)."""
     M, Nred = dy.shape
     Nout = w.shape[1]
     if not gemm_bf16_fits(M, Nout, Nred) or w.shape[0] != Nred:

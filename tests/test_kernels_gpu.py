@@ -356,6 +356,7 @@ def test_attn_launch_rejects_bad_args():
     assert (dq != 7.0).any() and (dk != 7.0).any() and (dv != 7.0).any()
 
 
+# the GEMMs at the workload's shapes and the planner; tests/test_gemm_kernels_gpu.py holds every launch path to fp64 references
 @pytest.mark.parametrize("M,N,K", [(8192, 2304, 768), (8192, 768, 3072), (1000, 300, 200), (256, 50304, 768)])
 def test_gemm_planner(M, N, K):
     from distributed_llm_trainer_amd.ops import gemm
