@@ -133,6 +133,15 @@ def _cap_scores(s: torch.Tensor, cfg) -> torch.Tensor:
 
 
 @torch.no_grad()
+def _glu(cfg, gu: torch.Tensor, I: int) -> torch.Tensor:
+    """act(gate) * up of an fp32 [.., 2I] gate | up row: the model's cfg.mlp_activation."""
+    g, u = gu[..., :I], gu[..., I:]
+    if getattr(cfg, "mlp_activation", "swiglu") == "geglu":
+        return F.gelu(g, approximate="tanh") * u
+    return F.silu(g) * u
+
+
+@torch.no_grad()
 def forward_cached(model, ids: torch.Tensor, cache: KVCache) -> torch.Tensor:
     """Append ``ids`` [B, T] at positions cache.len.. ; returns last-position logits [B, V]."""
     eng = model.engine
@@ -176,7 +185,7 @@ def forward_cached(model, ids: torch.Tensor, cache: KVCache) -> torch.Tensor:
         n2 = _rms(h, w.ln2, eng.eps).to(dt)
         gu = torch.matmul(n2, w.wgu.t()).float()
         I = cfg.intermediate_size
-        a = (F.silu(gu[..., :I]) * gu[..., I:]).to(dt)
+        a = _glu(cfg, gu, I).to(dt)
         h = h + _branch(torch.matmul(a, w.wdown.t()), getattr(w, "pn2", None), eng.eps)
         prov.post_forward(i)
     hw = prov.head()
@@ -215,6 +224,9 @@ class DecodeGraph:
         # fused HIP step (ops/csrc/decode.hip): 5 kernels per layer instead of ~25 ATen ops
         # (a grouped-query model: the _gqa forms of the two attention-side kernels)
         self.kind = _fused_kind(model, B)
+        # cfg.mlp_activation "geglu": k_dec_norm_gu's GeGLU form; a SwiGLU model passes no keyword
+        act = getattr(cfg, "mlp_activation", "swiglu")
+        self.act_kw = {} if act == "swiglu" else {"activation": act}
         self.fused = self.kind is not None
         if self.kind == "gqa":
             # key chunks per K/V head and the partials they merge through: allocated once,
@@ -273,7 +285,7 @@ class DecodeGraph:
                                  cache.v[i], cfg.num_heads)
                 ops.dec_attn(self.qb, cache.k[i], cache.v[i], self.pos, self.ob, scale, **wkw)
             ops.dec_gemv_res(self.ob, w.wo, self.h)
-            ops.dec_norm_gu(self.h, w.ln2, eng.eps, w.wgu, self.sb)
+            ops.dec_norm_gu(self.h, w.ln2, eng.eps, w.wgu, self.sb, **self.act_kw)
             ops.dec_gemv_res(self.sb, w.wdown, self.h)
         cap = getattr(cfg, "logit_softcap", None)
         if cap is None:
@@ -323,7 +335,7 @@ class DecodeGraph:
             n2 = _rms(h, w.ln2, eng.eps).to(dt)
             gu = torch.matmul(n2, w.wgu.t()).float()
             I = cfg.intermediate_size
-            h = h + _branch(torch.matmul((F.silu(gu[..., :I]) * gu[..., I:]).to(dt), w.wdown.t()),
+            h = h + _branch(torch.matmul(_glu(cfg, gu, I).to(dt), w.wdown.t()),
                             getattr(w, "pn2", None), eng.eps)
         nf = _rms(h[:, -1], hw.norm, eng.eps).to(dt)
         return _softcap(torch.matmul(nf, hw.lm_head.t())[:, :cfg.vocab_size].float(), cfg)

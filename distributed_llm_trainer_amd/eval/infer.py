@@ -26,7 +26,8 @@ def pick_device(name: str) -> torch.device:
 
 def load_model(path: str, model_size: str = None, device="cpu", num_kv_heads: int = None, qk_norm: bool = None,
                sliding_window: int = None, sliding_window_pattern: int = None, attention_sinks: bool = None,
-               logit_softcap: float = None, attn_softcap: float = None, post_norm: bool = None):
+               logit_softcap: float = None, attn_softcap: float = None, post_norm: bool = None,
+               mlp_activation: str = None):
     """The model of a checkpoint: built from the checkpoint's own config (which carries
     num_kv_heads for a grouped-query model) unless ``model_size`` names a preset;
     ``num_kv_heads`` overrides either, and so does ``qk_norm`` (the checkpoint's config carries
@@ -34,7 +35,8 @@ def load_model(path: str, model_size: str = None, device="cpu", num_kv_heads: in
     config carries them too), ``attention_sinks`` (carried by the config of a model with sinks) and
     ``logit_softcap`` (the final-logit cap, carried by the config of a model trained with one) and
     ``attn_softcap`` (the attention-score cap, carried likewise) and ``post_norm`` (the post-norms,
-    carried by the config of a model that has them)."""
+    carried by the config of a model that has them) and ``mlp_activation`` (a GeGLU model's config
+    carries it)."""
     ckpt = load_checkpoint(path, map_location="cpu")
     cfg = ckpt.get("model_config")
     if model_size is not None or not isinstance(cfg, GPTConfig):
@@ -55,6 +57,8 @@ def load_model(path: str, model_size: str = None, device="cpu", num_kv_heads: in
         cfg = GPTConfig.from_dict({**cfg.to_dict(), "attn_softcap": attn_softcap})
     if post_norm is not None:
         cfg = GPTConfig.from_dict({**cfg.to_dict(), "post_norm": bool(post_norm)})
+    if mlp_activation is not None:
+        cfg = GPTConfig.from_dict({**cfg.to_dict(), "mlp_activation": mlp_activation})
     model = GPT(cfg)
     load_model_state(model, ckpt["model"])
     model = model.to(device)
@@ -96,13 +100,15 @@ def main(argv=None):
     p.add_argument("--post_norm", action="store_true", default=None,
                    help="the checkpoint has post-norms (attn_post_norm / mlp_post_norm weights) and its config "
                         "does not say so")
+    p.add_argument("--mlp_activation", choices=["swiglu", "geglu"], default=None,
+                   help="the gated MLP's activation of a checkpoint whose config does not carry it")
     args = p.parse_args(argv)
     if args.seed is not None:
         torch.manual_seed(args.seed)
     dev = pick_device(args.device)
     model = load_model(args.checkpoint, args.model_size, dev, args.num_kv_heads, args.qk_norm, args.sliding_window,
                        args.sliding_window_pattern, args.attention_sinks, args.logit_softcap,
-                       args.attn_softcap, args.post_norm)
+                       args.attn_softcap, args.post_norm, args.mlp_activation)
     tok = get_tokenizer(args.tokenizer)
     ids = torch.tensor([tok.encode(args.prompt)], dtype=torch.long, device=dev)
     out = model.generate(ids, max_new_tokens=args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,

@@ -23,6 +23,9 @@ from dataclasses import asdict, dataclass, fields
 from typing import Any, Dict, Optional
 
 
+MLP_ACTIVATIONS = ("swiglu", "geglu")
+
+
 @dataclass
 class GPTConfig:
     """Configuration for the GPT model.  Defaults are the "GPT-2 124M" preset."""
@@ -75,6 +78,11 @@ class GPTConfig:
     # softmax; masked keys stay at -inf and a sink is not capped.  None = off.
     attn_softcap: Optional[float] = None
 
+    # The gated MLP's activation: "swiglu" (silu(gate) * up) or "geglu" (Gemma's
+    # gelu_tanh(gate) * up, gelu_tanh(g) = 0.5 g (1 + tanh(sqrt(2/pi) (g + 0.044715 g^3)))).  Same
+    # parameters and shapes either way.  (``activation`` above stays unread.)
+    mlp_activation: str = "swiglu"
+
     # Sliding-window (local) attention: query q sees key k iff q - W < k <= q, W keys with its
     # own (the Mistral / Gemma rule).  With sliding_window_pattern = N, layer i (0-based) is
     # global (plain causal) iff (i + 1) % N == 0 (Gemma-3's rule); unset, every layer is windowed.
@@ -111,6 +119,8 @@ class GPTConfig:
             if isinstance(n, bool) or int(n) != n or n < 2:
                 raise ValueError(f"sliding_window_pattern ({n!r}) must be an integer >= 2")
             self.sliding_window_pattern = int(n)
+        if self.mlp_activation not in MLP_ACTIVATIONS:
+            raise ValueError(f"mlp_activation ({self.mlp_activation!r}) must be one of {MLP_ACTIVATIONS}")
         if self.logit_softcap is not None:
             c = self.logit_softcap
             if isinstance(c, bool) or not isinstance(c, (int, float)) or not math.isfinite(c) or c <= 0:
@@ -235,11 +245,13 @@ class GPTConfig:
         for k in ("sliding_window", "sliding_window_pattern", "logit_softcap", "attn_softcap"):  # ... and unwindowed / uncapped ones
             if d[k] is None:
                 del d[k]
+        if self.mlp_activation == "swiglu":  # ... and SwiGLU ones
+            del d["mlp_activation"]
         return d
 
     # Pickled configs (checkpoints) follow to_dict(): an MHA config carries no num_kv_heads, one
     # without QK-norm no qk_norm, one without sinks no attention_sinks and one without post-norms
-    # no post_norm, so their pickles are
+    # no post_norm, and a SwiGLU one no mlp_activation, so their pickles are
     # what they were before the fields existed and older pickles load.
     def __getstate__(self) -> Dict[str, Any]:
         state = dict(self.__dict__)
@@ -254,6 +266,8 @@ class GPTConfig:
         for k in ("sliding_window", "sliding_window_pattern", "logit_softcap", "attn_softcap"):
             if state.get(k) is None:
                 state.pop(k, None)
+        if state.get("mlp_activation") == "swiglu":
+            state.pop("mlp_activation", None)
         return state
 
     def __setstate__(self, state: Dict[str, Any]) -> None:
@@ -267,6 +281,7 @@ class GPTConfig:
         self.__dict__.setdefault("sliding_window_pattern", None)
         self.__dict__.setdefault("logit_softcap", None)
         self.__dict__.setdefault("attn_softcap", None)
+        self.__dict__.setdefault("mlp_activation", "swiglu")
 
     @classmethod
     def from_dict(cls, d: Dict[str, Any]) -> "GPTConfig":

@@ -313,6 +313,14 @@ class GPTEngine:
         if self.post_norm and getattr(ops, "backend", "") == "hip" and act_dtype == torch.float32:
             raise NotImplementedError("this model on the GPU: fp32 activations have no post-norm kernels "
                                       "(post_norm); use bf16 or fp16 activations")
+        # the gated MLP's activation (cfg.mlp_activation): a GeGLU model passes activation="geglu" at
+        # its two MLP sites (_gate_up; the down data gradient / swiglu_bwd), which launch the GeGLU
+        # forms of the same kernels under the same per-shape picks; a SwiGLU model passes no keyword
+        act = getattr(cfg, "mlp_activation", "swiglu")
+        self.act_kw = {} if act == "swiglu" else {"activation": act}
+        if self.act_kw and getattr(ops, "backend", "") == "hip" and act_dtype == torch.float32:
+            raise NotImplementedError("this model on the GPU: fp32 activations have no GeGLU kernels "
+                                      "(mlp_activation); use bf16 or fp16 activations")
         if getattr(ops, "backend", "") == "hip":  # the GPU routes; the reference ops have every feature
             attn_routes.check_attention_features("cuda", cfg.head_dim, act_dtype, attn_routes.config_features(cfg),
                                                  self.packed_qkv)
@@ -656,10 +664,10 @@ class GPTEngine:
         slot = None if self._s_in_ring(st) else self._sb(st, i, "s", n2.shape[0], self.cfg.intermediate_size,
                                                          n2.device)
         if kept is None and hasattr(gm, "linear_swiglu"):
-            gu, s = gm.linear_swiglu(n2, w.wgu, ops, s_out=slot)
+            gu, s = gm.linear_swiglu(n2, w.wgu, ops, s_out=slot, **self.act_kw)
             return gu, s if need_s else None
         gu = gm.linear(n2, w.wgu) if kept is None else kept
-        return gu, ops.swiglu_fwd(gu, out=slot) if need_s else None
+        return gu, ops.swiglu_fwd(gu, out=slot, **self.act_kw) if need_s else None
 
     def _layer_forward(self, st: _StepState, i: int, r, d, key_d: int, p_d: float,
                        save: bool):
@@ -1238,10 +1246,10 @@ class GPTEngine:
                 s_new = torch.empty(M, I, dtype=c.gu.dtype, device=c.gu.device)
                 s_kw = {"s_out": s_new}
             if hasattr(gm, "linear_dgrad_swiglu"):  # down dgrad with the SwiGLU backward in its epilogue (when faster)
-                dgu = gm.linear_dgrad_swiglu(g_d, w.wdown, c.gu, ops, out=sb(i, "dgu", 2 * I), **s_kw)
+                dgu = gm.linear_dgrad_swiglu(g_d, w.wdown, c.gu, ops, out=sb(i, "dgu", 2 * I), **s_kw, **self.act_kw)
             else:
                 ds = gm.linear_dgrad(g_d, w.wdown)
-                dgu = ops.swiglu_bwd(c.gu, ds, out=sb(i, "dgu", 2 * I), **s_kw)
+                dgu = ops.swiglu_bwd(c.gu, ds, out=sb(i, "dgu", 2 * I), **s_kw, **self.act_kw)
                 del ds
             dn2 = gm.linear_dgrad(dgu, w.wgu)
             dx2, da = ops.rmsnorm_bwd(dn2, c.x2, c.rstd2, w.ln2, g_x2, gr.ln2, ph, k_resid,

@@ -187,11 +187,15 @@ class MLP(nn.Module):
         self.up_proj = nn.Linear(config.hidden_size, config.intermediate_size, bias=False)
         self.down_proj = nn.Linear(config.intermediate_size, config.hidden_size, bias=False)
         self.dropout = nn.Dropout(config.dropout)
+        self.geglu = getattr(config, "mlp_activation", "swiglu") == "geglu"
 
     def forward(self, x: torch.Tensor, post_norm: Optional[nn.Module] = None) -> torch.Tensor:
         """``post_norm``: the block's mlp_post_norm (config.post_norm), applied to the down_proj
         output before the dropout."""
-        out = self.down_proj(F.silu(self.gate_proj(x)) * self.up_proj(x))
+        if getattr(self, "geglu", False):  # config.mlp_activation "geglu": gelu_tanh(gate) * up
+            out = self.down_proj(F.gelu(self.gate_proj(x), approximate="tanh") * self.up_proj(x))
+        else:
+            out = self.down_proj(F.silu(self.gate_proj(x)) * self.up_proj(x))
         if post_norm is not None:
             out = post_norm(out)
         return self.dropout(out)
@@ -321,6 +325,10 @@ class GPT(nn.Module):
             if getattr(self.config, "post_norm", False) and dev.type == "cuda" and act_dtype == torch.float32:
                 raise NotImplementedError("this model on the GPU: fp32 activations have no post-norm kernels "
                                           "(post_norm); use bf16 or fp16 activations")
+            if getattr(self.config, "mlp_activation", "swiglu") != "swiglu" and dev.type == "cuda" \
+                    and act_dtype == torch.float32:
+                raise NotImplementedError("this model on the GPU: fp32 activations have no GeGLU kernels "
+                                          "(mlp_activation); use bf16 or fp16 activations")
         if provider is None:
             from ..parallel.flat import FlatParamStore
             provider = FlatParamStore(self, dev, compute_dtype=compute_dtype)

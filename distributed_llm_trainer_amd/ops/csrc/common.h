@@ -78,6 +78,51 @@ __device__ __forceinline__ uint32_t drop_bits(uint32_t key, uint64_t idx) {
 // emits for `1.f / x` is a ~10-instruction sequence, which dominated the SwiGLU GEMM
 // epilogue.  Every SwiGLU kernel uses this one so the fused and unfused paths agree.
 __device__ __forceinline__ float dlt_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
+// GeGLU (mlp_activation "geglu"): tanh-GELU is exactly g * sigmoid(z(g)) with
+// z(g) = 2 sqrt(2/pi) (g + 0.044715 g^3), so every GeGLU kernel is its SwiGLU form with
+// phi = dlt_sigmoid(z(g)) in place of dlt_sigmoid(g) and, in the backward, the inner
+// derivative z'(g) = 2 sqrt(2/pi) (1 + 0.134145 g^2):
+//   act = g phi, act' = phi + g phi (1 - phi) z'(g).
+// Every operation is an explicit product or fma (nothing left for the compiler to contract
+// differently in two kernels), so fused and unfused forms agree bit for bit.
+// z and z' are taken at g clamped to +-16: |z(16)| = 318, where exp(-z) has already
+// underflowed to 0 / overflowed to inf and phi is exactly 1 / 0, so the clamp changes no
+// result and g^2 cannot overflow (bf16's largest finite g would give z' = inf and 0 * inf).
+// e = exp(-z) is returned for the backward: 1 - phi = e / (1 + e) = e phi, a product, never
+// the cancelling subtraction; e = inf (phi = 0) takes 1 - phi = 1.  Saturated gates give
+// phi (1 - phi) = 0 exactly, so act' = phi exactly and no NaN.
+#define DLT_GELU_K 1.5957691216057308f  // 2 sqrt(2 / pi)
+__device__ __forceinline__ float dlt_gelu_phi(float g, float& gc, float& e) {
+  gc = fminf(fmaxf(g, -16.f), 16.f);
+  const float z = (DLT_GELU_K * gc) * __builtin_fmaf(0.044715f, gc * gc, 1.f);
+  e = __expf(-z);
+  return __builtin_amdgcn_rcpf(1.f + e);  // dlt_sigmoid(z), e kept
+}
+__device__ __forceinline__ float dlt_gelu_phi(float g) {
+  float gc, e;
+  return dlt_gelu_phi(g, gc, e);
+}
+// act'(g) from dlt_gelu_phi's (phi, gc, e)
+__device__ __forceinline__ float dlt_gelu_dact(float phi, float gc, float e) {
+  const float omp = e < INFINITY ? e * phi : 1.f;
+  const float dz = __builtin_fmaf(DLT_GELU_K * 0.134145f, gc * gc, DLT_GELU_K);
+  return __builtin_fmaf(gc * (phi * omp), dz, phi);
+}
+// A GeGLU result on its way to the 16-bit store: opaque to instruction selection, so the fp32
+// product is rounded to fp32 and then converted in every kernel.  Left to the compiler, the fp16
+// k_gemm_fw4 epilogue got v_fma_mixlo_f16 (product and fp16 conversion in one instruction) where
+// k_geglu_fwd has v_mul_f32 + v_cvt_pk_f16_f32, and the two differed in the last fp16 bit.
+__device__ __forceinline__ float dlt_glu_pin(float x) {
+  asm("" : "+v"(x));
+  return x;
+}
+// The gate's multiplier of a gated MLP, ACT = 0: SwiGLU (sigmoid(g)), 1: GeGLU (phi)
+enum { DLT_ACT_SWIGLU = 0, DLT_ACT_GEGLU = 1 };
+template <int ACT>
+__device__ __forceinline__ float dlt_glu_gate(float g) {
+  if constexpr (ACT == DLT_ACT_GEGLU) return dlt_gelu_phi(g);
+  else return dlt_sigmoid(g);
+}
 // tanh(x / cap) of the final-logit soft cap, k2 = 2 log2(e) / cap: with a = exp2(-|x| k2) in [0, 1]
 // and r = rcp(1 + a) it is copysign((1 - a) r, x), and 1 - tanh^2 = 4 a r^2 (a and r are returned for
 // it).  Nothing overflows; an underflowing a gives exactly +-1 and a derivative of exactly 0.

@@ -175,6 +175,9 @@ __device__ __forceinline__ void rows_dot(const bf16_t* const (&wrow)[NR], int K,
 
 }  // namespace
 
+// DLT_GEGLU_TU: this file as included by decode_geglu.hip, which sees only the helpers above,
+// k_dec_norm_gu and its GeGLU launcher.
+#ifndef DLT_GEGLU_TU
 // grid ((nh + 2 nkv) * 4): workgroup g owns dims {8c..8c+7} u {8c+32..8c+39} (c = g % 4:
 // the 8 NeoX RoPE pairs of a quarter head) of head hb = g / 4 of the packed q | k | v row
 // (nh query heads, then nkv key heads, then nkv value heads; weight rows hb * 64 ..) -- 16
@@ -608,9 +611,12 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_gemv_res(const bf16_t* __restric
   }
 }
 
+#endif  // DLT_GEGLU_TU
+
 // s[b][i] = bf16(silu(g) * u), g = bf16(n2 . Wgu[i]), u = bf16(n2 . Wgu[I + i]); 8 columns
-// per workgroup, 2 per wave (4 rows: gate, up of each).
-template <int B>
+// per workgroup, 2 per wave (4 rows: gate, up of each).  ACT 1 (GeGLU): gelu_tanh(g) * u,
+// geglu.hip's arithmetic.
+template <int B, int ACT = DLT_ACT_SWIGLU>
 __global__ __launch_bounds__(DEC_NT) void k_dec_norm_gu(const float* __restrict__ h, const void* __restrict__ lnw,
                                                         int wbf16, float eps, const bf16_t* __restrict__ wgu,
                                                         bf16_t* __restrict__ s, int H, int I) {
@@ -634,12 +640,15 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_norm_gu(const float* __restrict_
 #pragma unroll
         for (int b = 0; b < B; ++b) {
           const float gb = bf_round(acc[2 * c][b]), ub = bf_round(acc[2 * c + 1][b]);
-          s[(size_t)b * I + i0 + c] = f2bf(gb * dlt_sigmoid(gb) * ub);
+          float sv = gb * dlt_glu_gate<ACT>(gb) * ub;
+          if constexpr (ACT == DLT_ACT_GEGLU) sv = dlt_glu_pin(sv);
+          s[(size_t)b * I + i0 + c] = f2bf(sv);
         }
       }
   }
 }
 
+#ifndef DLT_GEGLU_TU
 // logits[b][r] = float(bf16(RMSNorm(h[b]) . E[r])) for r < V; 16 rows per workgroup.
 // CAP: the model's final-logit soft cap, cap * tanh(x / cap) of that rounded value in fp32
 // (dlt_cap_tanh, the cross-entropy CAP forms' formulation), applied before the store.  CAP is
@@ -1186,6 +1195,7 @@ __global__ __launch_bounds__(SMP_NT) void k_dec_topk_draw(const int* __restrict_
 }
 
 __global__ void k_dec_advance(long* pos) { pos[0] += 1; }
+#endif  // DLT_GEGLU_TU
 
 // ------------------------------------------------------------------------ launchers
 #define DEC_DISPATCH(B, CALL)          \
@@ -1198,6 +1208,19 @@ __global__ void k_dec_advance(long* pos) { pos[0] += 1; }
   }
 
 static size_t dec_lds(int B, int K) { return (size_t)B * K * 2 + (size_t)B * 4 * 4 + (size_t)B * 16 * 4; }
+
+#ifdef DLT_GEGLU_TU
+// dlt_dec_norm_gu for the GeGLU MLP
+DLT_API int dlt_dec_norm_gu_geglu(const float* h, const void* lnw, int wbf16, float eps, const bf16_t* wgu, bf16_t* s,
+                                  int B, int H, int I, hipStream_t st) {
+  if (H <= 0 || I <= 0 || H % 8 || dec_lds(B, H) > 160 * 1024) return -1;
+#define L(BB) \
+  k_dec_norm_gu<BB, DLT_ACT_GEGLU><<<(I + 7) / 8, DEC_NT, dec_lds(BB, H), st>>>(h, lnw, wbf16, eps, wgu, s, H, I)
+  DEC_DISPATCH(B, L)
+#undef L
+  DLT_CHECK_LAUNCH();
+}
+#else
 
 DLT_API int dlt_dec_norm_qkv_gqa(const float* h, const void* lnw, int wbf16, float eps, const bf16_t* wqkv,
                                  const float* cosT, const float* sinT, const long* pos, bf16_t* qout, bf16_t* kc,
@@ -1433,3 +1456,4 @@ DLT_API int dlt_dec_advance(long* pos, hipStream_t st) {
   k_dec_advance<<<1, 1, 0, st>>>(pos);
   DLT_CHECK_LAUNCH();
 }
+#endif  // DLT_GEGLU_TU

@@ -101,7 +101,9 @@ __device__ __forceinline__ int gb_brow(int q, int g) {
 //           gradient, [M, I]) and, per element, the SwiGLU backward of gpt.py:280 on the
 //           kept gu = [gate | up] (same math as k_swiglu_bwd on the bf16-rounded ds):
 //           dgu[:, j] = ds * u * sig(g) * (1 + g (1 - sig(g))), dgu[:, I + j] = ds * silu(g).
-enum { GB_EPI_STORE = 0, GB_EPI_ROPE = 1, GB_EPI_SWIGLU = 2, GB_EPI_SWIGLU_BWD = 3 };
+//   GB_EPI_GEGLU (or-ed into SWIGLU / SWIGLU_BWD): the same two epilogues for the GeGLU MLP,
+//           gate multiplier phi = sigmoid(z(g)) (common.h dlt_gelu_phi; geglu.hip's math).
+enum { GB_EPI_STORE = 0, GB_EPI_ROPE = 1, GB_EPI_SWIGLU = 2, GB_EPI_SWIGLU_BWD = 3, GB_EPI_GEGLU = 4 };
 
 // Diagnostic build only (tools/cpp/gemm_bench.cpp defines GB_STAMPS): per-wave s_memtime
 // sums of the first K-iteration of a tile, the rest of its K-loop and its epilogue, plus
@@ -194,10 +196,13 @@ __device__ __forceinline__ void gb_unpack(uint2 p, float (&f)[4]) {
 // schedule and its counted waits are unchanged.
 // HK: operand / output format, 0 = bf16, 1 = IEEE half (plain store epilogue only).
 // LATE (ROPE / SWIGLU_BWD only): epilogue-first staging of the next tile, see the loop.
-template <int BN, int EPI, bool BT = false, int HK = 0, bool LATE = false>
+template <int BN, int EPIA, bool BT = false, int HK = 0, bool LATE = false>
 __global__ __launch_bounds__(512, 1) void k_gemm_bf16(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B,
                                                       bf16_t* __restrict__ C, int M, int N, int K, int lda, int ldb,
                                                       int ldc, int flags, GbEpi ep) {
+  // EPIA = EPI | GB_EPI_GEGLU: the SWIGLU / SWIGLU_BWD epilogues with the GeGLU gate
+  constexpr int EPI = EPIA & 3, ACT = (EPIA & GB_EPI_GEGLU) ? DLT_ACT_GEGLU : DLT_ACT_SWIGLU;
+  static_assert(ACT == DLT_ACT_SWIGLU || EPI == GB_EPI_SWIGLU || EPI == GB_EPI_SWIGLU_BWD, "GeGLU: a gated epilogue");
   static_assert(EPI == GB_EPI_STORE || BN == 192, "pair epilogues need the 192-column tile");
   static_assert(!BT || (BN == 192 && (EPI == GB_EPI_STORE || EPI == GB_EPI_SWIGLU_BWD)) ||
                     (BN == 128 && EPI == GB_EPI_STORE),
@@ -697,7 +702,10 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16(const bf16_t* __restrict__
             gb_unpack(pk[t + 3], u);
             floatx4_t sv;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) sv[e] = g[e] * dlt_sigmoid(g[e]) * u[e];
+            for (int e = 0; e < 4; ++e) {
+              sv[e] = g[e] * dlt_glu_gate<ACT>(g[e]) * u[e];
+              if constexpr (ACT == DLT_ACT_GEGLU) sv[e] = dlt_glu_pin(sv[e]);
+            }
             sp[t] = gb_pack(sv);
           }
           if (lt) {
@@ -800,10 +808,20 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16(const bf16_t* __restrict__
               floatx4_t r, sv;
 #pragma unroll
               for (int e = 0; e < 2; ++e) {
-                const float sg = dlt_sigmoid(g[e]);
-                r[e] = d[e] * u[e] * sg * (1.f + g[e] * (1.f - sg));
-                r[2 + e] = d[e] * g[e] * sg;
-                sv[e] = g[e] * sg * u[e];  // s = silu(g) * u: k_swiglu_fwd's arithmetic, same bits
+                if constexpr (ACT == DLT_ACT_GEGLU) {
+                  // k_geglu_bwd's arithmetic, same bits: phi once, shared by dg, du and s
+                  float gc, ex;
+                  const float phi = dlt_gelu_phi(g[e], gc, ex);
+                  const float act = g[e] * phi;
+                  r[e] = dlt_glu_pin(d[e] * (u[e] * dlt_gelu_dact(phi, gc, ex)));
+                  r[2 + e] = dlt_glu_pin(d[e] * act);
+                  sv[e] = dlt_glu_pin(act * u[e]);
+                } else {
+                  const float sg = dlt_sigmoid(g[e]);
+                  r[e] = d[e] * u[e] * sg * (1.f + g[e] * (1.f - sg));
+                  r[2 + e] = d[e] * g[e] * sg;
+                  sv[e] = g[e] * sg * u[e];  // s = silu(g) * u: k_swiglu_fwd's arithmetic, same bits
+                }
                 sv[2 + e] = 0.f;
               }
               const uint2 pr = gb_pack_hk<HK>(r);  // (dg0, dg1), (du0, du1)
@@ -910,6 +928,38 @@ static inline bool gb_shape_ok(int M, int N, int K, int lda, int ldb, int ldc) {
   return M > 0 && N > 0 && M % 256 == 0 && K % 128 == 0 && K >= 128 && (lda | ldb | ldc) % 8 == 0;
 }
 
+#ifdef DLT_GEGLU_TU
+// This file as included by gemm_bf16_geglu.hip: only the GeGLU forms of the two gated
+// epilogues are instantiated and exported there (same checks, grids and arguments as
+// dlt_gemm_bf16_down_swiglu_bwd / dlt_gemm_bf16_gu_swiglu below).
+DLT_API int dlt_gemm_bf16_down_geglu_bwd(const bf16_t* dd, const bf16_t* Wdown, const bf16_t* gu, bf16_t* dgu,
+                                         bf16_t* s_out, int M, int I, int H, int flags, int hk, hipStream_t st) {
+  if (!gb_shape_ok(M, I, H, H, I, 2 * I) || I % 192) return -1;
+  const int ntiles = (M / 256) * (I / 192);
+  GbEpi ep{nullptr, nullptr, 1, 0, s_out, 2 * I, I, gu};
+  if (flags & 4096) {
+    DLT_HK_DISPATCH(hk, k_gemm_bf16<192, GB_EPI_SWIGLU_BWD | GB_EPI_GEGLU, true, HKC, true>
+                            <<<gb_launch_grid(ntiles, flags), 512, 0, st>>>(dd, Wdown, dgu, M, I, H, H, I, 2 * I,
+                                                                           flags, ep));
+  } else {
+    DLT_HK_DISPATCH(hk, k_gemm_bf16<192, GB_EPI_SWIGLU_BWD | GB_EPI_GEGLU, true, HKC>
+                            <<<gb_launch_grid(ntiles, flags), 512, 0, st>>>(dd, Wdown, dgu, M, I, H, H, I, 2 * I,
+                                                                           flags, ep));
+  }
+  DLT_CHECK_LAUNCH();
+}
+
+DLT_API int dlt_gemm_bf16_gu_geglu(const bf16_t* A, const bf16_t* W, bf16_t* gu, bf16_t* s_out, int M, int I, int K,
+                                   int flags, hipStream_t st) {
+  const int N = 2 * I;
+  if (!gb_shape_ok(M, N, K, K, K, N) || I % 96) return -1;
+  GbEpi ep{nullptr, nullptr, 1, 0, s_out, I, I};
+  const int ntiles = (M / 256) * (I / 96);
+  k_gemm_bf16<192, GB_EPI_SWIGLU | GB_EPI_GEGLU>
+      <<<gb_launch_grid(ntiles, flags), 512, 0, st>>>(A, W, gu, M, N, K, K, K, N, flags, ep);
+  DLT_CHECK_LAUNCH();
+}
+#else
 // C = A . B^T (bf16, or IEEE half with hk = 1).  Only the 192-column tile is
 // instantiated: the 256-column one needs 256 accumulator + fragment VGPRs per lane and
 // spills at 8 waves per CU.
@@ -994,3 +1044,4 @@ DLT_API int dlt_gemm_bf16_gu_swiglu(const bf16_t* A, const bf16_t* W, bf16_t* gu
   k_gemm_bf16<192, GB_EPI_SWIGLU><<<gb_launch_grid(ntiles, flags), 512, 0, st>>>(A, W, gu, M, N, K, K, K, N, flags, ep);
   DLT_CHECK_LAUNCH();
 }
+#endif  // DLT_GEGLU_TU

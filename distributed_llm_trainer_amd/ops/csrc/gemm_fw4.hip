@@ -130,7 +130,7 @@ struct F4Frags {
 
 }  // namespace
 
-template <int HK, int SCHED, int TT, bool SW, bool LSE = false>
+template <int HK, int SCHED, int TT, bool SW, bool LSE = false, int ACT = DLT_ACT_SWIGLU>
 __global__ __launch_bounds__(256, 1) void k_gemm_fw4(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B,
                                                      bf16_t* __restrict__ C, int M, int N, int K, int lda, int ldb,
                                                      int ldc, int flags, bf16_t* __restrict__ S, int ldS,
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256, 1) void k_gemm_fw4(const bf16_t* __restrict__ 
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wid & 1, wn = wid >> 1;
   const int l16 = lane & 15, q = lane >> 4;
-  constexpr bool swiglu = SW;  // flags 1024: the gate/up projection with the SwiGLU epilogue
+  constexpr bool swiglu = SW;  // flags 1024: the gate/up projection with the SwiGLU epilogue (ACT 1: GeGLU)
   constexpr int T = TT;  // tiles per workgroup (flags 4096: two, the second's first stages prefetched)
 
   // tile j of this workgroup -> (tm, tn): block b runs on the XCD of b % 8 (round-robin
@@ -435,7 +435,8 @@ __global__ __launch_bounds__(256, 1) void k_gemm_fw4(const bf16_t* __restrict__ 
             for (int h = 0; h < 2; ++h) {
               const float gv = h2f<HK>((uint16_t)(G[w0] >> (16 * h)));
               const float uv = h2f<HK>((uint16_t)(U[w0] >> (16 * h)));
-              sv[h] = gv * dlt_sigmoid(gv) * uv;
+              sv[h] = gv * dlt_glu_gate<ACT>(gv) * uv;
+              if constexpr (ACT == DLT_ACT_GEGLU) sv[h] = dlt_glu_pin(sv[h]);
             }
             o2[e >> 1] = (uint32_t)f2h<HK>(sv[0]) | ((uint32_t)f2h<HK>(sv[1]) << 16);
           }
@@ -475,6 +476,35 @@ __global__ __launch_bounds__(256, 1) void k_gemm_fw4(const bf16_t* __restrict__ 
   }
 }
 
+#ifdef DLT_GEGLU_TU
+// This file as included by gemm_fw4_geglu.hip: only the GeGLU form of the gate/up epilogue
+// is instantiated and exported there.  dlt_gemm_fw4's arguments and checks with flags 1024
+// implied (one tile per workgroup; flags: C store policy, tile order and schedule as below).
+DLT_API int dlt_gemm_fw4_geglu(const bf16_t* A, const bf16_t* B, bf16_t* C, int M, int N, int K, int lda, int ldb,
+                               int ldc, int flags, int hk, bf16_t* S, int ldS, hipStream_t st) {
+  if (M <= 0 || N <= 0 || K <= 0 || M % F4_BM || N % 256 || K % F4_BK || K < 2 * F4_BK || lda % 8 || ldb % 8 ||
+      ldc % 8 || lda < K || ldb < K || ldc < N)
+    return -1;
+  const int sched_bits = flags & (16 | 128);
+  if (sched_bits == 16 || sched_bits == 128 || (flags & 4096)) return -1;
+  if (S == nullptr || ldS < N / 2 || ldS % 8 || 128L * ldS * 2 > 0x7fffffffL ||
+      (long)(N / 2 + 127) * ldb * 2 > 0xffffffffL)
+    return -1;
+  const long tiles = (long)(M / F4_BM) * (N / F4_BN);
+  if (tiles > 0x7fffffff || 128L * ldc * 2 > 0x7fffffffL || 256L * lda * 2 > 0xffffffffL ||
+      256L * ldb * 2 > 0xffffffffL)
+    return -1;
+  const int grid = (int)tiles;
+  flags |= 1024;
+  if (sched_bits)
+    DLT_HK_DISPATCH(hk, k_gemm_fw4<HKC, 5, 1, true, false, DLT_ACT_GEGLU>
+                            <<<grid, 256, 0, st>>>(A, B, C, M, N, K, lda, ldb, ldc, flags, S, ldS));
+  else
+    DLT_HK_DISPATCH(hk, k_gemm_fw4<HKC, 4, 1, true, false, DLT_ACT_GEGLU>
+                            <<<grid, 256, 0, st>>>(A, B, C, M, N, K, lda, ldb, ldc, flags, S, ldS));
+  DLT_CHECK_LAUNCH();
+}
+#else
 // flags: 1 = write-through (sc1) C stores, 4 = nt C stores; tile order 2 = row-major, 2048 = half-height
 // XCD bands (default XCD row bands); schedule 16 | 128 = SCHED 5 (else SCHED 4); 1024 = SwiGLU epilogue;
 // 4096 = two tiles per workgroup (the second tile's first stages prefetched behind the first's epilogue)
@@ -580,3 +610,4 @@ DLT_API int dlt_lmhead_loss(const bf16_t* A, const bf16_t* W, const int64_t* tar
                                        2 * ntn, V);
   DLT_CHECK_LAUNCH();
 }
+#endif  // DLT_GEGLU_TU

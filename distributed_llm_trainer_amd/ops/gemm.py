@@ -467,10 +467,14 @@ class HipGemm:
             unfused()
         return y
 
-    def linear_swiglu(self, x: torch.Tensor, w: torch.Tensor, ops, s_out: torch.Tensor = None):
+    def linear_swiglu(self, x: torch.Tensor, w: torch.Tensor, ops, s_out: torch.Tensor = None,
+                      activation: str = "swiglu"):
         """(gu, s): gu = x @ Wgu^T and s = silu(gate) * up, fused in the GEMM epilogue or
-        as linear + ``ops.swiglu_fwd`` (raced once per shape like :meth:`linear`)."""
+        as linear + ``ops.swiglu_fwd`` (raced once per shape like :meth:`linear`).
+        ``activation`` "geglu": s = gelu_tanh(gate) * up, the GeGLU form of whichever path the
+        shape's pick (plan kinds "swiglu" / "swiglu4", shared by both activations) names."""
         from . import hip
+        act = {} if not hip._geglu(activation, "linear_swiglu.activation") else {"activation": activation}
         M = x.shape[0]
         I2 = w.shape[0]
         gu = torch.empty(M, I2, dtype=x.dtype, device=x.device)
@@ -478,15 +482,15 @@ class HipGemm:
 
         def unfused():
             self.linear(x, w, out=gu)
-            ops.swiglu_fwd(gu, out=s)
+            ops.swiglu_fwd(gu, out=s, **act)
 
         def fused():
-            hip.gemm_gu_swiglu(x, w, gu_out=gu, s_out=s)
+            hip.gemm_gu_swiglu(x, w, gu_out=gu, s_out=s, **act)
         # the 4-wave k_gemm_fw4 with the SwiGLU epilogue: plan kind "swiglu4" (its launch flags)
         # or DLT_GEMM_FW4_SWIGLU=<flags> (A/B knob)
         fw4 = os.environ.get("DLT_GEMM_FW4_SWIGLU") or self._choice.get(("swiglu4", M, I2, x.shape[1]))
         if fw4 is not None and self._hand16_ok(x, w) and s.is_contiguous() and \
-                hip.gemm_fw4_swiglu(x, w, gu_out=gu, s_out=s, flags=int(fw4)) is not None:
+                hip.gemm_fw4_swiglu(x, w, gu_out=gu, s_out=s, flags=int(fw4), **act) is not None:
             return gu, s
         ok = I2 % 192 == 0 and hip.gemm_bf16_fits192(M, I2, x.shape[1]) and s.is_contiguous()
         if ok and self._fused_pick("swiglu", x, w, fused, unfused):
@@ -537,13 +541,16 @@ class HipGemm:
         return dx
 
     def linear_dgrad_swiglu(self, dd: torch.Tensor, wdown: torch.Tensor, gu: torch.Tensor, ops,
-                            out: torch.Tensor = None, s_out: torch.Tensor = None) -> torch.Tensor:
+                            out: torch.Tensor = None, s_out: torch.Tensor = None,
+                            activation: str = "swiglu") -> torch.Tensor:
         """dgu[M, 2I]: the down projection's data gradient ds = dd @ Wdown and the SwiGLU
         backward against the kept gu, fused in one hand-written kernel
         (``hip.gemm_down_swiglu_bwd``) or as ``linear_dgrad`` + ``ops.swiglu_bwd`` --
         raced once per shape (kind "dswiglu").  ``s_out``: also (re)writes the SwiGLU
-        output s = silu(g) * u there (the forward's bits; engine s ring)."""
+        output s = silu(g) * u there (the forward's bits; engine s ring).  ``activation``
+        "geglu": the GeGLU backward and s, under the same picks (no plan kind of its own)."""
         from . import hip
+        act = {} if not hip._geglu(activation, "linear_dgrad_swiglu.activation") else {"activation": activation}
         M, H = dd.shape
         I = wdown.shape[1]
         dgu = torch.empty(M, 2 * I, dtype=dd.dtype, device=dd.device) if out is None else out
@@ -551,12 +558,12 @@ class HipGemm:
         def unfused():
             ds = self.linear_dgrad(dd, wdown)
             if s_out is not None:
-                ops.swiglu_bwd(gu, ds, out=dgu, s_out=s_out)
+                ops.swiglu_bwd(gu, ds, out=dgu, s_out=s_out, **act)
             else:
-                ops.swiglu_bwd(gu, ds, out=dgu)
+                ops.swiglu_bwd(gu, ds, out=dgu, **act)
 
         def fused():
-            hip.gemm_down_swiglu_bwd(dd, wdown, gu, out=dgu, s_out=s_out)
+            hip.gemm_down_swiglu_bwd(dd, wdown, gu, out=dgu, s_out=s_out, **act)
         # bf16 and fp16 race separately (kind "dswiglu" / "dswiglu16")
         kind = "dswiglu" if dd.dtype == torch.bfloat16 else "dswiglu16"
         ok = (self._dgrad_on and self._race and hip.gemm_bf16_fits192(M, I, H) and tuple(gu.shape) == (M, 2 * I)

@@ -18,7 +18,7 @@ from typing import Optional
 import torch
 
 from . import rng
-from .reference import check_softcap  # noqa: F401  (one validation for both backends)
+from .reference import check_mlp_activation, check_softcap  # noqa: F401  (one validation for both backends)
 
 _LIB = None
 # DLT_KERNEL_DEBUG=1 loads the bounds-checked build (ops/build.py --debug);
@@ -129,6 +129,15 @@ _SIGS = {
                          c_int, c_int, c_void_p, c_void_p],
     "dlt_dec_sample_ws_ints": [c_int],
     "dlt_dec_advance": [c_void_p, c_void_p],
+    # GeGLU forms (csrc/*geglu.hip): the arguments of their SwiGLU namesakes
+    "dlt_geglu_fwd": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
+    "dlt_geglu_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
+    "dlt_gemm_fw4_geglu": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                           c_void_p, c_int, c_void_p],
+    "dlt_gemm_bf16_gu_geglu": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+    "dlt_gemm_bf16_down_geglu_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                     c_int, c_void_p],
+    "dlt_dec_norm_gu_geglu": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
 }
 
 
@@ -361,15 +370,17 @@ def dec_gemv_res(x, w, h):
     _chk(lib().dlt_dec_gemv_res(_p(x), _p(w), _p(h), B, R, K, _stream()), "dec_gemv_res")
 
 
-def dec_norm_gu(h, ln, eps, wgu, s_out):
+def dec_norm_gu(h, ln, eps, wgu, s_out, activation: str = "swiglu"):
+    """``activation``: the gated MLP's ("swiglu" / "geglu", k_dec_norm_gu's ACT forms)."""
+    geglu = _geglu(activation, "dec_norm_gu.activation")
     B, H = h.shape
     I = wgu.shape[0] // 2
     _req(h, torch.float32, "dec.h", B * H)
     w, wbf16 = _norm_weight(ln, H, "dec.ln2")
     _dec_w(wgu, "dec.wgu")
     _req(s_out, torch.bfloat16, "dec.s", B * I)
-    _chk(lib().dlt_dec_norm_gu(_p(h), _p(w), wbf16, float(eps), _p(wgu), _p(s_out), B, H, I, _stream()),
-         "dec_norm_gu")
+    fn = lib().dlt_dec_norm_gu_geglu if geglu else lib().dlt_dec_norm_gu
+    _chk(fn(_p(h), _p(w), wbf16, float(eps), _p(wgu), _p(s_out), B, H, I, _stream()), "dec_norm_gu")
 
 
 def dec_norm_head(h, ln, eps, emb, logits, V, softcap: float = 0.0):
@@ -1319,8 +1330,22 @@ def attention_bwd(q, k, v, o, do, aux, p, key, causal=True, scale=None, doc=None
 
 
 # ----------------------------------------------------------------- SwiGLU
-def swiglu_fwd(gu, out=None):
+def _geglu(activation, name: str) -> bool:
+    """The gated MLP's activation of a launcher: True for "geglu" (the GeGLU kernel forms),
+    False for "swiglu" (the default: what was launched before the argument existed)."""
+    return check_mlp_activation(activation, name)
+
+
+def _no_f32_geglu(name: str):
+    raise NotImplementedError(f"{name}: fp32 activations have no GeGLU kernels; use bf16 or fp16")
+
+
+def swiglu_fwd(gu, out=None, activation: str = "swiglu"):
+    """``activation`` "geglu": gelu_tanh(gate) * up (k_geglu_fwd)."""
+    geglu = _geglu(activation, "swiglu_fwd.activation")
     if gu.dtype == torch.float32:
+        if geglu:
+            _no_f32_geglu("swiglu_fwd")
         from . import hip_f32
         return hip_f32.swiglu_fwd(gu, out=out)
     M, twoI = gu.shape
@@ -1328,13 +1353,18 @@ def swiglu_fwd(gu, out=None):
     if out is None:
         out = torch.empty(M, twoI // 2, dtype=gu.dtype, device=gu.device)
     _req(out, gu.dtype, "swiglu.out", M * twoI // 2)
-    _chk(lib().dlt_swiglu_fwd(_p(gu), _p(out), M, twoI // 2, hk, _stream()), "swiglu_fwd")
+    fn = lib().dlt_geglu_fwd if geglu else lib().dlt_swiglu_fwd
+    _chk(fn(_p(gu), _p(out), M, twoI // 2, hk, _stream()), "swiglu_fwd")
     return out
 
 
-def swiglu_bwd(gu, da, out=None, s_out=None):
-    """dgu = SwiGLU backward; ``s_out``: also writes s = silu(g) * u (the forward's bits)."""
+def swiglu_bwd(gu, da, out=None, s_out=None, activation: str = "swiglu"):
+    """dgu = SwiGLU backward; ``s_out``: also writes s = silu(g) * u (the forward's bits).
+    ``activation`` "geglu": the GeGLU backward and s (k_geglu_bwd)."""
+    geglu = _geglu(activation, "swiglu_bwd.activation")
     if gu.dtype == torch.float32:
+        if geglu:
+            _no_f32_geglu("swiglu_bwd")
         from . import hip_f32
         return hip_f32.swiglu_bwd(gu, da, out=out, s_out=s_out)
     M, twoI = gu.shape
@@ -1345,8 +1375,9 @@ def swiglu_bwd(gu, da, out=None, s_out=None):
     _req(out, gu.dtype, "swiglu_bwd.out", M * twoI)
     if s_out is not None:
         _req(s_out, gu.dtype, "swiglu_bwd.s_out", M * twoI // 2)
-    _chk(lib().dlt_swiglu_bwd(_p(gu), _p(da), _p(out), _p(s_out) if s_out is not None else None, M, twoI // 2, hk,
-                              _stream()), "swiglu_bwd")
+    fn = lib().dlt_geglu_bwd if geglu else lib().dlt_swiglu_bwd
+    _chk(fn(_p(gu), _p(da), _p(out), _p(s_out) if s_out is not None else None, M, twoI // 2, hk, _stream()),
+         "swiglu_bwd")
     return out
 
 
@@ -1848,11 +1879,12 @@ def gemm_fw4_swiglu_fits(M: int, I2: int, K: int) -> bool:
 
 
 def gemm_fw4_swiglu(x: torch.Tensor, wgu: torch.Tensor, gu_out: Optional[torch.Tensor] = None,
-                    s_out: Optional[torch.Tensor] = None, flags: Optional[int] = None):
+                    s_out: Optional[torch.Tensor] = None, flags: Optional[int] = None, activation: str = "swiglu"):
     """(gu[M, 2I], s[M, I]): gu = x @ Wgu^T (gate rows [0, I), up rows [I, 2I)) by the 4-wave
     k_gemm_fw4 with s = silu(gate) * up in its epilogue (csrc/gemm_fw4.hip, flags 1024;
     k_swiglu_fwd's arithmetic, same bits).  None if the shape does not tile (I % 128,
-    M % 256, K % 64)."""
+    M % 256, K % 64).  ``activation`` "geglu": s = gelu_tanh(gate) * up (k_geglu_fwd's bits)."""
+    geglu = _geglu(activation, "gemm_fw4_swiglu.activation")
     M, K = x.shape
     I2 = wgu.shape[0]
     I = I2 // 2
@@ -1867,7 +1899,8 @@ def gemm_fw4_swiglu(x: torch.Tensor, wgu: torch.Tensor, gu_out: Optional[torch.T
     fl = (_FW4_FLAGS if flags is None else flags) & ~(16 | 128)
     if flags is not None and (flags & (16 | 128)) == (16 | 128):
         fl |= 16 | 128  # SCHED 5
-    _chk(lib().dlt_gemm_fw4(_p(x), _p(wgu), _p(gu), M, I2, K, K, K, I2, (fl | 1024) & ~4096, hk, _p(s), I, _stream()),
+    fn = lib().dlt_gemm_fw4_geglu if geglu else lib().dlt_gemm_fw4
+    _chk(fn(_p(x), _p(wgu), _p(gu), M, I2, K, K, K, I2, (fl | 1024) & ~4096, hk, _p(s), I, _stream()),
          "gemm_fw4_swiglu")
     return gu, s
 
@@ -1896,10 +1929,11 @@ def gemm_qkv_rope(x: torch.Tensor, wqkv: torch.Tensor, S: int, cos: torch.Tensor
 
 
 def gemm_gu_swiglu(x: torch.Tensor, wgu: torch.Tensor, gu_out: Optional[torch.Tensor] = None,
-                   s_out: Optional[torch.Tensor] = None):
+                   s_out: Optional[torch.Tensor] = None, activation: str = "swiglu"):
     """(gu[M, 2I], s[M, I]) with gu = x @ Wgu^T (gate rows [0, I), up rows [I, 2I)) and
     s = silu(gate) * up computed in the GEMM epilogue.  None if the shape does not tile
-    (I % 96, M % 256, K % 128)."""
+    (I % 96, M % 256, K % 128).  ``activation`` "geglu": s = gelu_tanh(gate) * up."""
+    geglu = _geglu(activation, "gemm_gu_swiglu.activation")
     M, K = x.shape
     I2 = wgu.shape[0]
     I = I2 // 2
@@ -1911,7 +1945,8 @@ def gemm_gu_swiglu(x: torch.Tensor, wgu: torch.Tensor, gu_out: Optional[torch.Te
     s = torch.empty(M, I, dtype=torch.bfloat16, device=x.device) if s_out is None else s_out
     _req(gu, torch.bfloat16, "gemm_gu_swiglu.gu", M * I2)
     _req(s, torch.bfloat16, "gemm_gu_swiglu.s", M * I)
-    _chk(lib().dlt_gemm_bf16_gu_swiglu(_p(x), _p(wgu), _p(gu), _p(s), M, I, K, _fwd_flags(), _stream()), "gemm_gu_swiglu")
+    fn = lib().dlt_gemm_bf16_gu_geglu if geglu else lib().dlt_gemm_bf16_gu_swiglu
+    _chk(fn(_p(x), _p(wgu), _p(gu), _p(s), M, I, K, _fwd_flags(), _stream()), "gemm_gu_swiglu")
     return gu, s
 
 
@@ -1937,13 +1972,14 @@ def gemm_dgrad(dy: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = 
 
 
 def gemm_down_swiglu_bwd(dd: torch.Tensor, wdown: torch.Tensor, gu: torch.Tensor,
-                         out: Optional[torch.Tensor] = None, s_out: Optional[torch.Tensor] = None
-                         ) -> Optional[torch.Tensor]:
+                         out: Optional[torch.Tensor] = None, s_out: Optional[torch.Tensor] = None,
+                         activation: str = "swiglu") -> Optional[torch.Tensor]:
     """dgu[M, 2I] = SwiGLU backward of ds = dd[M, H] @ Wdown[H, I] (bf16-rounded) against
     the kept gu[M, 2I] -- the down projection's data gradient and ``swiglu_bwd`` in one
     kernel (same math and roundings as the unfused pair).  ``s_out`` [M, I] (optional):
     also writes s = silu(g) * u with the forward's bits (``swiglu_bwd``'s s_out).  None
-    if it does not tile."""
+    if it does not tile.  ``activation`` "geglu": the GeGLU backward and s."""
+    geglu = _geglu(activation, "gemm_down_swiglu_bwd.activation")
     M, H = dd.shape
     I = wdown.shape[1]
     if not gemm_bf16_fits192(M, I, H) or wdown.shape[0] != H or tuple(gu.shape) != (M, 2 * I):
@@ -1956,8 +1992,9 @@ def gemm_down_swiglu_bwd(dd: torch.Tensor, wdown: torch.Tensor, gu: torch.Tensor
     _req(c, dt, "gemm_down_swiglu_bwd.out", M * 2 * I)
     if s_out is not None:
         _req(s_out, dt, "gemm_down_swiglu_bwd.s_out", M * I)
-    _chk(lib().dlt_gemm_bf16_down_swiglu_bwd(_p(dd), _p(wdown), _p(gu), _p(c), _p(s_out), M, I, H, _GB_FLAGS,
-                                             _WG_HK[dt], _stream()), "gemm_down_swiglu_bwd")
+    fn = lib().dlt_gemm_bf16_down_geglu_bwd if geglu else lib().dlt_gemm_bf16_down_swiglu_bwd
+    _chk(fn(_p(dd), _p(wdown), _p(gu), _p(c), _p(s_out), M, I, H, _GB_FLAGS, _WG_HK[dt], _stream()),
+         "gemm_down_swiglu_bwd")
     return c
 
 

@@ -508,27 +508,55 @@ def attention_bwd(q, k, v, o, do, lse, p: float, key: int, causal: bool = True, 
 
 
 # ----------------------------------------------------------------- SwiGLU
-def swiglu_fwd(gu: torch.Tensor, out=None) -> torch.Tensor:
-    """gu [M, 2I] (gate | up) -> silu(gate) * up [M, I]."""
+GELU_K = 2.0 * math.sqrt(2.0 / math.pi)  # gelu_tanh(g) = g * sigmoid(GELU_K * (g + 0.044715 g^3))
+
+
+def check_mlp_activation(activation, name: str = "swiglu.activation") -> bool:
+    """The gated MLP's activation of an op: True for "geglu", False for "swiglu" (the default)."""
+    if activation not in ("swiglu", "geglu"):
+        raise ValueError(f"{name}: expected 'swiglu' or 'geglu', got {activation!r}")
+    return activation == "geglu"
+
+
+def _gelu_z(g: torch.Tensor):
+    """(gc, z(gc)) with gc = g clamped to +-16, where sigmoid(z) is already exactly 0 / 1 in fp32
+    (as the kernels do, csrc/common.h: keeps g^2 finite for any gate)."""
+    gc = g.clamp(-16.0, 16.0)
+    return gc, GELU_K * (gc + 0.044715 * gc * gc * gc)
+
+
+def _gate_phi(g: torch.Tensor, geglu: bool) -> torch.Tensor:
+    """The gate's multiplier: act(g) = g * phi."""
+    return torch.sigmoid(_gelu_z(g)[1]) if geglu else torch.sigmoid(g)
+
+
+def swiglu_fwd(gu: torch.Tensor, out=None, activation: str = "swiglu") -> torch.Tensor:
+    """gu [M, 2I] (gate | up) -> silu(gate) * up [M, I] ("geglu": gelu_tanh(gate) * up)."""
+    geglu = check_mlp_activation(activation)
     i = gu.shape[-1] // 2
     g, u = gu[:, :i].float(), gu[:, i:].float()
-    r = (g * torch.sigmoid(g) * u).to(gu.dtype)
+    r = (g * _gate_phi(g, geglu) * u).to(gu.dtype)
     if out is not None:
         out.copy_(r)
         return out
     return r
 
 
-def swiglu_bwd(gu: torch.Tensor, da: torch.Tensor, out=None, s_out=None) -> torch.Tensor:
+def swiglu_bwd(gu: torch.Tensor, da: torch.Tensor, out=None, s_out=None, activation: str = "swiglu") -> torch.Tensor:
     """``s_out``: also writes s = silu(g) * u (as swiglu_fwd)."""
+    geglu = check_mlp_activation(activation, "swiglu_bwd.activation")
     i = gu.shape[-1] // 2
     if s_out is not None:
-        swiglu_fwd(gu, out=s_out)
+        swiglu_fwd(gu, out=s_out, activation=activation)
     g, u = gu[:, :i].float(), gu[:, i:].float()
     d = da.float()
-    sg = torch.sigmoid(g)
+    sg = _gate_phi(g, geglu)
     silu = g * sg
-    dg = d * u * sg * (1.0 + g * (1.0 - sg))
+    if geglu:  # act' = phi + g phi (1 - phi) z'(g); 1 - phi = sigmoid(-z), no cancellation
+        gc, z = _gelu_z(g)
+        dg = d * u * (sg + gc * sg * torch.sigmoid(-z) * (GELU_K * (1.0 + 0.134145 * gc * gc)))
+    else:
+        dg = d * u * sg * (1.0 + g * (1.0 - sg))
     du = d * silu
     r = torch.cat([dg, du], dim=-1).to(gu.dtype)
     if out is not None:

@@ -285,6 +285,10 @@ def add_model_args(p) -> None:
                         "branch output, before the hidden dropout and the residual add, with an attn_post_norm "
                         "and an mlp_post_norm weight per layer.  Overrides the YAML's model.post_norm and the "
                         "preset (default: off)")
+    p.add_argument("--mlp_activation", choices=["swiglu", "geglu"], default=None,
+                   help="the gated MLP's activation: swiglu (silu(gate) * up) or geglu (Gemma's "
+                        "gelu_tanh(gate) * up); same parameters either way, saved in checkpoints.  Overrides the "
+                        "YAML's model.mlp_activation and the preset (default: swiglu)")
 
 
 def apply_model_args(args, model_config) -> None:
@@ -303,7 +307,8 @@ def apply_model_args(args, model_config) -> None:
     sw, swp = getattr(args, "sliding_window", None), getattr(args, "sliding_window_pattern", None)
     cap = getattr(args, "logit_softcap", None)
     acap = getattr(args, "attn_softcap", None)
-    if sw is not None or swp is not None or cap is not None or acap is not None:
+    act = getattr(args, "mlp_activation", None)
+    if sw is not None or swp is not None or cap is not None or acap is not None or act is not None:
         if sw is not None:
             model_config.sliding_window = sw
         if swp is not None:
@@ -312,6 +317,8 @@ def apply_model_args(args, model_config) -> None:
             model_config.logit_softcap = cap
         if acap is not None:
             model_config.attn_softcap = acap
+        if act is not None:
+            model_config.mlp_activation = act
         model_config.__post_init__()  # the config's own validation (ValueError)
 
 
