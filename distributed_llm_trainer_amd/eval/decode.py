@@ -26,7 +26,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn.functional as F
@@ -222,8 +222,12 @@ class DecodeGraph:
         self.pos = torch.full((1,), pos, dtype=torch.long, device=dev)
         self.kpos = torch.arange(cfg.max_seq_len, device=dev)
         # fused HIP step (ops/csrc/decode.hip): 5 kernels per layer instead of ~25 ATen ops
-        # (a grouped-query model: the _gqa forms of the two attention-side kernels)
-        self.kind = _fused_kind(model, B)
+        # (a grouped-query model: the _gqa forms of the two attention-side kernels; a QK-norm model:
+        # dec_norm_qkv_qkn; a post-norm model: dec_gemv_out and the post= forms of the norm kernels)
+        step = _fused_step(model, B)
+        self.kind = step.kind if step is not None else None
+        self.qkn = step is not None and step.qk_norm
+        self.pn = step is not None and step.post_norm
         # cfg.mlp_activation "geglu": k_dec_norm_gu's GeGLU form; a SwiGLU model passes no keyword
         act = getattr(cfg, "mlp_activation", "swiglu")
         self.act_kw = {} if act == "swiglu" else {"activation": act}
@@ -241,6 +245,9 @@ class DecodeGraph:
             self.ob = torch.empty(B, H, dtype=torch.bfloat16, device=dev)
             self.sb = torch.empty(B, I, dtype=torch.bfloat16, device=dev)
             self.lg = torch.empty(B, cfg.vocab_size, dtype=torch.float32, device=dev)
+            if self.pn:  # the second residual buffer and the raw branch, outside the capture
+                self.h2 = torch.empty_like(self.h)
+                self.ab = torch.empty(B, H, dtype=torch.bfloat16, device=dev)
         self.sample = sample if self.fused else None
         if self.sample is not None:
             self.sample_ws = model.engine.ops.dec_sample_workspace(B, dev)
@@ -267,31 +274,53 @@ class DecodeGraph:
         hw = prov.head()
         self.h.copy_(hw.embed.index_select(0, self.ids.view(-1)))
         scale = 1.0 / math.sqrt(cfg.head_dim)
+        # Post-norms (self.pn): dec_gemv_out stores the raw branch to self.ab and the next norm kernel
+        # adds its post-norm to the residual it reads (post=), storing the sum to the OTHER of the
+        # two residual buffers: ``h`` is the one that holds the residual, ``post`` what is pending.
+        h, other, post = self.h, getattr(self, "h2", None), None
         for i in range(cfg.num_layers):
             w = prov.layer(i)
             W = _layer_window(cfg, i) or 0
             wkw = {"window": W} if W else {}  # a global layer calls the kernels it always did
+            pkw = {}
+            if post is not None:  # layer i - 1's mlp post-norm: reads h, writes other
+                pkw = {"post": (self.ab, post, other)}
             if getattr(w, "sk", None) is not None:  # attention sinks: the kernels' sink= forms
                 wkw["sink"] = w.sk
             if getattr(cfg, "attn_softcap", None) is not None:  # a capped model: the CAP kernels
                 wkw["softcap"] = cfg.attn_softcap
+            if self.qkn:
+                ops.dec_norm_qkv_qkn(h, w.ln1, eng.eps, w.wqkv, w.qn, w.kn, cos_t, sin_t, self.pos, self.qb,
+                                     cache.k[i], cache.v[i], cfg.num_heads, cfg.num_kv_heads, **pkw)
+            elif self.kind == "gqa":
+                ops.dec_norm_qkv_gqa(h, w.ln1, eng.eps, w.wqkv, cos_t, sin_t, self.pos, self.qb, cache.k[i],
+                                     cache.v[i], cfg.num_heads, cfg.num_kv_heads, **pkw)
+            else:
+                ops.dec_norm_qkv(h, w.ln1, eng.eps, w.wqkv, cos_t, sin_t, self.pos, self.qb, cache.k[i],
+                                 cache.v[i], cfg.num_heads, **pkw)
+            if post is not None:
+                h, other = other, h
             if self.kind == "gqa":
-                ops.dec_norm_qkv_gqa(self.h, w.ln1, eng.eps, w.wqkv, cos_t, sin_t, self.pos, self.qb, cache.k[i],
-                                     cache.v[i], cfg.num_heads, cfg.num_kv_heads)
                 ops.dec_attn_gqa(self.qb, cache.k[i], cache.v[i], self.pos, self.ob, scale, cfg.num_heads,
                                  splits=self.kv_splits, ws=self.attn_ws, **wkw)
             else:
-                ops.dec_norm_qkv(self.h, w.ln1, eng.eps, w.wqkv, cos_t, sin_t, self.pos, self.qb, cache.k[i],
-                                 cache.v[i], cfg.num_heads)
                 ops.dec_attn(self.qb, cache.k[i], cache.v[i], self.pos, self.ob, scale, **wkw)
-            ops.dec_gemv_res(self.ob, w.wo, self.h)
-            ops.dec_norm_gu(self.h, w.ln2, eng.eps, w.wgu, self.sb, **self.act_kw)
-            ops.dec_gemv_res(self.sb, w.wdown, self.h)
+            if self.pn:
+                ops.dec_gemv_out(self.ob, w.wo, self.ab)
+                ops.dec_norm_gu(h, w.ln2, eng.eps, w.wgu, self.sb, post=(self.ab, w.pn1, other), **self.act_kw)
+                h, other = other, h
+                ops.dec_gemv_out(self.sb, w.wdown, self.ab)
+                post = w.pn2
+            else:
+                ops.dec_gemv_res(self.ob, w.wo, h)
+                ops.dec_norm_gu(h, w.ln2, eng.eps, w.wgu, self.sb, **self.act_kw)
+                ops.dec_gemv_res(self.sb, w.wdown, h)
+        hkw = {} if post is None else {"post": (self.ab, post, None)}  # the head stores no residual
         cap = getattr(cfg, "logit_softcap", None)
         if cap is None:
-            ops.dec_norm_head(self.h, hw.norm, eng.eps, hw.lm_head, self.lg, cfg.vocab_size)
+            ops.dec_norm_head(h, hw.norm, eng.eps, hw.lm_head, self.lg, cfg.vocab_size, **hkw)
         else:  # the CAP kernel: the sampler below reads capped logits
-            ops.dec_norm_head(self.h, hw.norm, eng.eps, hw.lm_head, self.lg, cfg.vocab_size, softcap=cap)
+            ops.dec_norm_head(h, hw.norm, eng.eps, hw.lm_head, self.lg, cfg.vocab_size, softcap=cap, **hkw)
         if self.sample is not None:
             sm = self.sample
             ops.dec_sample(self.lg, sm["temperature"], sm["top_k"], sm["seed"], self.pos, self.ids, sm["hist"],
@@ -378,11 +407,47 @@ def _gqa_splits(cfg, B: int) -> int:
     return _dec_kv_splits(B, cfg.num_kv_heads, cfg.max_seq_len)
 
 
+class FusedStep(NamedTuple):
+    """A model's fused HIP decode step: the attention layout and which norm forms it needs."""
+    kind: str        # "mha" | "gqa"
+    qk_norm: bool    # dec_norm_qkv_qkn in place of dec_norm_qkv / dec_norm_qkv_gqa
+    post_norm: bool  # dec_gemv_out + the post= forms of the norm kernels, two residual buffers
+
+
+def _fused_step(model, B: int) -> Optional[FusedStep]:
+    """The fused HIP decode step ``DecodeGraph`` captures, or None (the ATen step).  The conditions
+    are :func:`_fused_kind`'s without its two norm refusals: a QK-norm and / or post-norm model
+    takes the same attention kernels and the norm forms of the others (csrc/decode_norms.hip),
+    which need those ops to be present and a bf16 engine."""
+    cfg = model.config
+    qkn, pn = bool(getattr(cfg, "qk_norm", False)), bool(getattr(cfg, "post_norm", False))
+    if qkn or pn:
+        ops = model.engine.ops
+        if not (hasattr(ops, "dec_norm_qkv_qkn") and hasattr(ops, "dec_gemv_out")):
+            return None
+        if getattr(model.engine, "act_dtype", torch.bfloat16) != torch.bfloat16:
+            return None
+        # k_dec_norm_qkv_qkn stages 16 partials and a whole head's outputs per batch row (dec_lds_qkn)
+        if qkn and B * cfg.hidden_size * 2 + B * 16 * 4 + B * 64 * 4 > DEC_LDS_MAX:
+            return None
+    kind = _kind_without_norms(model, B)
+    return None if kind is None else FusedStep(kind, qkn, pn)
+
+
 def _fused_kind(model, B: int) -> Optional[str]:
+    """The fused step WITHOUT norm forms: :func:`_fused_step`'s kind for a model with neither
+    QK-norm nor post-norms, None for a model with either (what this function answered before the
+    norm forms existed; ``DecodeGraph`` and ``kv_cached_generate`` ask :func:`_fused_step`)."""
+    cfg = model.config
+    if getattr(cfg, "qk_norm", False) or getattr(cfg, "post_norm", False):
+        return None
+    return _kind_without_norms(model, B)
+
+
+def _kind_without_norms(model, B: int) -> Optional[str]:
     """Which fused HIP decode step applies: ``"mha"`` (``dec_norm_qkv`` / ``dec_attn``),
     ``"gqa"`` (num_kv_heads < num_heads: ``dec_norm_qkv_gqa`` / ``dec_attn_gqa``) or None,
-    for which ``DecodeGraph`` captures the ATen step instead (always for a QK-norm model: the
-    fused norm + QKV kernels do not apply q_norm / k_norm).  Both kinds need HIP ops, a
+    for which ``DecodeGraph`` captures the ATen step instead.  Both kinds need HIP ops, a
     supported batch, head_dim 64, ``DLT_DECODE_FUSED != 0`` and the LDS of their kernels to
     fit one CU: the norm + GEMV kernels stage one normed bf16 row per batch entry
     (``dec_lds`` in decode.hip); ``k_dec_attn`` keeps all ``max_seq_len`` scores of a
@@ -392,10 +457,6 @@ def _fused_kind(model, B: int) -> Optional[str]:
     (:func:`_attn_keys`); a model with global layers needs what those need."""
     ops = model.engine.ops
     cfg = model.config
-    if getattr(cfg, "qk_norm", False):  # no fused norm + QKV kernel applies q_norm / k_norm: the ATen step does
-        return None
-    if getattr(cfg, "post_norm", False):  # dec_gemv_res adds the raw branch to the residual: the ATen step norms it
-        return None
     norm_lds = B * cfg.hidden_size * 2 + B * 4 * 4 + B * 16 * 4
     if not (hasattr(ops, "dec_norm_qkv") and B in getattr(ops, "DECODE_BATCHES", ())
             and cfg.head_dim == 64 and norm_lds <= DEC_LDS_MAX
@@ -479,7 +540,7 @@ def kv_cached_generate(model, input_ids: torch.Tensor, max_new_tokens: int = 100
     out = input_ids
     n_dev = min(max_new_tokens - 1, cfg.max_seq_len - cache.len)
     if (n_dev > 0 and temperature > 0 and _graph_ok(model, input_ids.device)
-            and _fused_kind(model, B) is not None and os.environ.get("DLT_DECODE_DEVICE_LOOP", "1") != "0"):
+            and _fused_step(model, B) is not None and os.environ.get("DLT_DECODE_DEVICE_LOOP", "1") != "0"):
         # first token from the prefill logits (ATen sampling), then one graph replay per
         # token: the fused step samples on the device and feeds itself (no host round trip)
         lg = filter_logits(logits / temperature, top_k, top_p, min_p)

@@ -40,9 +40,15 @@ def _src_flags(src: str):
     return GEGLU_FLAGS if os.path.basename(src).endswith("geglu.hip") else []
 
 
+# wrapper sources: each #includes the named source of its directory
+WRAPPERS = {"decode_norms.hip": "decode.hip"}
+
+
 def _src_deps(src: str, headers):
-    """Headers plus, for a wrapper ``X_geglu.hip`` (it #includes ``X.hip``), that source."""
+    """Headers plus, for a wrapper ``X_geglu.hip`` (it #includes ``X.hip``) or one of WRAPPERS, that source."""
     inc = src[:-len("_geglu.hip")] + ".hip" if src.endswith("_geglu.hip") else None
+    if os.path.basename(src) in WRAPPERS:
+        inc = os.path.join(os.path.dirname(src), WRAPPERS[os.path.basename(src)])
     return list(headers) + ([inc] if inc and os.path.exists(inc) else [])
 
 

@@ -14,6 +14,11 @@
 //   dec_gemv_res    : h += o . Wo^T  /  h += s . Wdown^T      (residual add in fp32)
 //   dec_norm_gu     : h -> RMSNorm -> gate/up GEMV -> SwiGLU -> s
 //   dec_norm_head   : h -> RMSNorm -> lm_head GEMV -> fp32 logits
+// and, for QK-norm / post-norm models, in decode_norms.hip (which includes this file for the
+// helpers and the PN forms of the three norm + GEMV kernels below):
+//   dec_norm_qkv_qkn: dec_norm_qkv with the per-head RMSNorm of q and k before RoPE (a head per workgroup)
+//   dec_gemv_out    : a = bf16(o . Wo^T) / bf16(s . Wdown^T), the raw branch of a post-norm model
+//   post= (PN) forms: the next norm kernel first forms h + bf16(RMSNorm(a) * w_pn) (stage_postnorm_normed)
 //
 // GEMV shape: a wave computes 4 output rows at once, lanes across K (16-byte weight loads:
 // the weight stream, which dominates the bytes, is coalesced, and all 4 rows' loads are in
@@ -41,12 +46,23 @@ __device__ __forceinline__ float norm_w(const void* w, int wbf16, int i) {
   return wbf16 ? bf2f(reinterpret_cast<const bf16_t*>(w)[i]) : reinterpret_cast<const float*>(w)[i];
 }
 
+// the NW per-wave partials of a row, summed left to right
+template <int NW>
+__device__ __forceinline__ float red_row(const float* r) {
+  float t = r[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) t += r[w];
+  return t;
+}
+
 // xs[b][k] (bf16, LDS) = bf16(h[b][k] * rsqrt(mean(h[b]^2) + eps) * w[k]) for b < B.
 // float4 loads, every row's loads issued before the reductions (the per-element loop
 // was a chain of dependent round trips: most of a kernel's time).
-template <int B>
+// NT: threads of the workgroup (red holds NT / 64 partials per row).
+template <int B, int NT = DEC_NT>
 __device__ void stage_normed(const float* __restrict__ h, int K, const void* w, int wbf16, float eps, bf16_t* xs,
                              float* red) {
+  constexpr int NW = NT / 64;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int nch = K >> 2;  // float4 chunks per row (K % 8 == 0)
   float ss[B];
@@ -54,7 +70,7 @@ __device__ void stage_normed(const float* __restrict__ h, int K, const void* w, 
   for (int b = 0; b < B; ++b) {
     ss[b] = 0.f;
 #pragma unroll 2
-    for (int c = tid; c < nch; c += DEC_NT) {
+    for (int c = tid; c < nch; c += NT) {
       const float4 x = *reinterpret_cast<const float4*>(h + (size_t)b * K + 4 * c);
       ss[b] += x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w;
     }
@@ -62,15 +78,94 @@ __device__ void stage_normed(const float* __restrict__ h, int K, const void* w, 
 #pragma unroll
   for (int b = 0; b < B; ++b) {
     const float t = wave_sum64(ss[b]);
-    if (lane == 0) red[b * 4 + wid] = t;
+    if (lane == 0) red[b * NW + wid] = t;
   }
   __syncthreads();
 #pragma unroll
   for (int b = 0; b < B; ++b) {
-    const float rstd = rsqrtf((red[b * 4] + red[b * 4 + 1] + red[b * 4 + 2] + red[b * 4 + 3]) / (float)K + eps);
+    const float rstd = rsqrtf(red_row<NW>(red + b * NW) / (float)K + eps);
 #pragma unroll 2
-    for (int c = tid; c < nch; c += DEC_NT) {
+    for (int c = tid; c < nch; c += NT) {
       const float4 x = *reinterpret_cast<const float4*>(h + (size_t)b * K + 4 * c);
+      u16x4 y;
+      y.v[0] = f2bf(x.x * rstd * norm_w(w, wbf16, 4 * c));
+      y.v[1] = f2bf(x.y * rstd * norm_w(w, wbf16, 4 * c + 1));
+      y.v[2] = f2bf(x.z * rstd * norm_w(w, wbf16, 4 * c + 2));
+      y.v[3] = f2bf(x.w * rstd * norm_w(w, wbf16, 4 * c + 3));
+      *reinterpret_cast<u16x4*>(xs + b * K + 4 * c) = y;
+    }
+  }
+  __syncthreads();
+}
+
+// stage_normed with a post-norm prologue (cfg.post_norm): the residual row is
+//   x[b] = h_in[b] + bf16(a[b] * rsqrt(mean(a[b]^2) + eps) * pn_w)
+// with a [B][K] bf16 the raw branch output that k_dec_gemv_out stored, and xs = bf16(RMSNorm(x) * w)
+// as above.  Three passes (sum a^2; x and sum x^2; x again, normed, to LDS); x lives in neither
+// registers nor LDS between passes, the re-reads come from L2.  Every workgroup computes the
+// same bits from the same code; workgroup 0 alone stores x to h_out (nullable).  h_out must not
+// alias h_in: another workgroup may still be reading it.
+template <int B, int NT = DEC_NT>
+__device__ void stage_postnorm_normed(const float* __restrict__ h_in, const bf16_t* __restrict__ a, const void* pnw,
+                                      int pnbf16, float* __restrict__ h_out, int K, const void* w, int wbf16,
+                                      float eps, bf16_t* xs, float* red) {
+  constexpr int NW = NT / 64;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int nch = K >> 2;
+  float ss[B], rsa[B];
+#pragma unroll
+  for (int b = 0; b < B; ++b) {
+    ss[b] = 0.f;
+#pragma unroll 2
+    for (int c = tid; c < nch; c += NT) {
+      const u16x4 v = *reinterpret_cast<const u16x4*>(a + (size_t)b * K + 4 * c);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) ss[b] = fmaf(bf2f(v.v[e]), bf2f(v.v[e]), ss[b]);
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < B; ++b) {
+    const float t = wave_sum64(ss[b]);
+    if (lane == 0) red[b * NW + wid] = t;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int b = 0; b < B; ++b) rsa[b] = rsqrtf(red_row<NW>(red + b * NW) / (float)K + eps);
+  __syncthreads();  // every rstd_a read before red[] takes the sums of x^2
+  // x of chunk c of row b: the same expression in passes 2 and 3 (the same bits)
+  auto x_of = [&](int b, int c) {
+    const float4 hv = *reinterpret_cast<const float4*>(h_in + (size_t)b * K + 4 * c);
+    const u16x4 v = *reinterpret_cast<const u16x4*>(a + (size_t)b * K + 4 * c);
+    float4 x;
+    x.x = hv.x + bf_round(bf2f(v.v[0]) * rsa[b] * norm_w(pnw, pnbf16, 4 * c));
+    x.y = hv.y + bf_round(bf2f(v.v[1]) * rsa[b] * norm_w(pnw, pnbf16, 4 * c + 1));
+    x.z = hv.z + bf_round(bf2f(v.v[2]) * rsa[b] * norm_w(pnw, pnbf16, 4 * c + 2));
+    x.w = hv.w + bf_round(bf2f(v.v[3]) * rsa[b] * norm_w(pnw, pnbf16, 4 * c + 3));
+    return x;
+  };
+  const bool store = h_out != nullptr && blockIdx.x == 0;
+#pragma unroll
+  for (int b = 0; b < B; ++b) {
+    ss[b] = 0.f;
+#pragma unroll 2
+    for (int c = tid; c < nch; c += NT) {
+      const float4 x = x_of(b, c);
+      ss[b] += x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w;
+      if (store) *reinterpret_cast<float4*>(h_out + (size_t)b * K + 4 * c) = x;
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < B; ++b) {
+    const float t = wave_sum64(ss[b]);
+    if (lane == 0) red[b * NW + wid] = t;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int b = 0; b < B; ++b) {
+    const float rstd = rsqrtf(red_row<NW>(red + b * NW) / (float)K + eps);
+#pragma unroll 2
+    for (int c = tid; c < nch; c += NT) {
+      const float4 x = x_of(b, c);
       u16x4 y;
       y.v[0] = f2bf(x.x * rstd * norm_w(w, wbf16, 4 * c));
       y.v[1] = f2bf(x.y * rstd * norm_w(w, wbf16, 4 * c + 1));
@@ -176,19 +271,27 @@ __device__ __forceinline__ void rows_dot(const bf16_t* const (&wrow)[NR], int K,
 }  // namespace
 
 // DLT_GEGLU_TU: this file as included by decode_geglu.hip, which sees only the helpers above,
-// k_dec_norm_gu and its GeGLU launcher.
+// k_dec_norm_gu and its GeGLU launcher.  DLT_NORMS_TU: as included by decode_norms.hip, which
+// sees the helpers and the three norm + GEMV kernel templates (for their PN forms) and no launcher.
+#if defined(DLT_GEGLU_TU) || defined(DLT_NORMS_TU)
+#define DLT_DEC_PART_TU 1
+#endif
+// PN (post-norm prologue, stage_postnorm_normed): the residual row is h + bf16(RMSNorm(pa) * pnw),
+// stored to hout by workgroup 0.  Compile-time: the plain forms never read pa / pnw / hout.
 #ifndef DLT_GEGLU_TU
 // grid ((nh + 2 nkv) * 4): workgroup g owns dims {8c..8c+7} u {8c+32..8c+39} (c = g % 4:
 // the 8 NeoX RoPE pairs of a quarter head) of head hb = g / 4 of the packed q | k | v row
 // (nh query heads, then nkv key heads, then nkv value heads; weight rows hb * 64 ..) -- 16
 // rows, 4 per wave, one load round trip.  nkv == nh is the multi-head layout [3H, H].
-template <int B>
+template <int B, bool PN = false>
 __global__ __launch_bounds__(DEC_NT) void k_dec_norm_qkv(const float* __restrict__ h, const void* __restrict__ lnw,
                                                          int wbf16, float eps, const bf16_t* __restrict__ wqkv,
                                                          const float* __restrict__ cosT, const float* __restrict__ sinT,
                                                          const long* __restrict__ posp, bf16_t* __restrict__ qout,
                                                          bf16_t* __restrict__ kc, bf16_t* __restrict__ vc, int H, int nh,
-                                                         int nkv, int maxS) {
+                                                         int nkv, int maxS, const bf16_t* __restrict__ pa = nullptr,
+                                                         const void* __restrict__ pnw = nullptr, int pnbf16 = 0,
+                                                         float* __restrict__ hout = nullptr) {
   extern __shared__ __attribute__((aligned(16))) char dsm[];
   bf16_t* xs = reinterpret_cast<bf16_t*>(dsm);                       // [B][H]
   float* red = reinterpret_cast<float*>(dsm + (size_t)B * H * 2);     // [B][4]
@@ -204,7 +307,10 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_norm_qkv(const float* __restrict
   for (int r = 0; r < 4; ++r) rows[r] = wqkv + (size_t)(hb * 64 + dim_of(wid * 4 + r)) * H;
   RowsPre<4, 2> pre;
   rows_pre<4, 2>(rows, H, pre);
-  stage_normed<B>(h, H, lnw, wbf16, eps, xs, red);
+  if constexpr (PN)
+    stage_postnorm_normed<B>(h, pa, pnw, pnbf16, hout, H, lnw, wbf16, eps, xs, red);
+  else
+    stage_normed<B>(h, H, lnw, wbf16, eps, xs, red);
   float acc[4][B];
   rows_dot<B, 4, 2>(rows, H, xs, pre, acc);
   if (lane == 0) {
@@ -234,6 +340,9 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_norm_qkv(const float* __restrict
       (blk == 1 ? kc : vc)[(((size_t)b * nkv + head) * maxS + pos) * 64 + d] = f2bf(y);
   }
 }
+#endif  // DLT_GEGLU_TU
+
+#ifndef DLT_DEC_PART_TU
 
 // Attention-score soft-capping of the decode attention kernels (their CAP forms): the fp32 score
 // s = scale q.k becomes cap * tanh(s / cap), cap_k = 2 log2(e) / cap.
@@ -611,15 +720,18 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_gemv_res(const bf16_t* __restric
   }
 }
 
-#endif  // DLT_GEGLU_TU
+#endif  // DLT_DEC_PART_TU
 
 // s[b][i] = bf16(silu(g) * u), g = bf16(n2 . Wgu[i]), u = bf16(n2 . Wgu[I + i]); 8 columns
 // per workgroup, 2 per wave (4 rows: gate, up of each).  ACT 1 (GeGLU): gelu_tanh(g) * u,
 // geglu.hip's arithmetic.
-template <int B, int ACT = DLT_ACT_SWIGLU>
+template <int B, int ACT = DLT_ACT_SWIGLU, bool PN = false>
 __global__ __launch_bounds__(DEC_NT) void k_dec_norm_gu(const float* __restrict__ h, const void* __restrict__ lnw,
                                                         int wbf16, float eps, const bf16_t* __restrict__ wgu,
-                                                        bf16_t* __restrict__ s, int H, int I) {
+                                                        bf16_t* __restrict__ s, int H, int I,
+                                                        const bf16_t* __restrict__ pa = nullptr,
+                                                        const void* __restrict__ pnw = nullptr, int pnbf16 = 0,
+                                                        float* __restrict__ hout = nullptr) {
   extern __shared__ __attribute__((aligned(16))) char dsm[];
   bf16_t* xs = reinterpret_cast<bf16_t*>(dsm);
   float* red = reinterpret_cast<float*>(dsm + (size_t)B * H * 2);
@@ -630,7 +742,10 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_norm_gu(const float* __restrict_
                            wgu + (size_t)(I + ib) * H};
   RowsPre<4, 2> pre;
   rows_pre<4, 2>(rows, H, pre);
-  stage_normed<B>(h, H, lnw, wbf16, eps, xs, red);
+  if constexpr (PN)
+    stage_postnorm_normed<B>(h, pa, pnw, pnbf16, hout, H, lnw, wbf16, eps, xs, red);
+  else
+    stage_normed<B>(h, H, lnw, wbf16, eps, xs, red);
   float acc[4][B];
   rows_dot<B, 4, 2>(rows, H, xs, pre, acc);
   if (lane == 0) {
@@ -653,10 +768,13 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_norm_gu(const float* __restrict_
 // CAP: the model's final-logit soft cap, cap * tanh(x / cap) of that rounded value in fp32
 // (dlt_cap_tanh, the cross-entropy CAP forms' formulation), applied before the store.  CAP is
 // compile-time: the plain form never reads `cap`.
-template <int B, bool CAP = false>
+template <int B, bool CAP = false, bool PN = false>
 __global__ __launch_bounds__(DEC_NT) void k_dec_norm_head(const float* __restrict__ h, const void* __restrict__ lnw,
                                                           int wbf16, float eps, const bf16_t* __restrict__ emb,
-                                                          float* __restrict__ logits, int H, int V, float cap) {
+                                                          float* __restrict__ logits, int H, int V, float cap,
+                                                          const bf16_t* __restrict__ pa = nullptr,
+                                                          const void* __restrict__ pnw = nullptr, int pnbf16 = 0,
+                                                          float* __restrict__ hout = nullptr) {
   extern __shared__ __attribute__((aligned(16))) char dsm[];
   bf16_t* xs = reinterpret_cast<bf16_t*>(dsm);
   float* red = reinterpret_cast<float*>(dsm + (size_t)B * H * 2);
@@ -667,7 +785,10 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_norm_head(const float* __restric
   for (int r = 0; r < 4; ++r) rows[r] = emb + (size_t)min(r0 + r, V - 1) * H;
   RowsPre<4, 2> pre;
   rows_pre<4, 2>(rows, H, pre);
-  stage_normed<B>(h, H, lnw, wbf16, eps, xs, red);
+  if constexpr (PN)
+    stage_postnorm_normed<B>(h, pa, pnw, pnbf16, hout, H, lnw, wbf16, eps, xs, red);
+  else
+    stage_normed<B>(h, H, lnw, wbf16, eps, xs, red);
   float acc[4][B];
   rows_dot<B, 4, 2>(rows, H, xs, pre, acc);
   if (lane == 0) {
@@ -687,6 +808,8 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_norm_head(const float* __restric
   }
 }
 
+#endif  // DLT_GEGLU_TU
+#ifndef DLT_DEC_PART_TU
 // ---------------------------------------------------------------- top-k sampling
 // GPT.generate's sampling step (gpt.py:474-482): logits / temperature, keep the values >=
 // the k-th largest (ties kept, as masked_fill(lg < v[:, [-1]], -inf) does), softmax,
@@ -1195,7 +1318,7 @@ __global__ __launch_bounds__(SMP_NT) void k_dec_topk_draw(const int* __restrict_
 }
 
 __global__ void k_dec_advance(long* pos) { pos[0] += 1; }
-#endif  // DLT_GEGLU_TU
+#endif  // DLT_DEC_PART_TU
 
 // ------------------------------------------------------------------------ launchers
 #define DEC_DISPATCH(B, CALL)          \
@@ -1209,7 +1332,9 @@ __global__ void k_dec_advance(long* pos) { pos[0] += 1; }
 
 static size_t dec_lds(int B, int K) { return (size_t)B * K * 2 + (size_t)B * 4 * 4 + (size_t)B * 16 * 4; }
 
-#ifdef DLT_GEGLU_TU
+#if defined(DLT_NORMS_TU)
+// decode_norms.hip has its own launchers
+#elif defined(DLT_GEGLU_TU)
 // dlt_dec_norm_gu for the GeGLU MLP
 DLT_API int dlt_dec_norm_gu_geglu(const float* h, const void* lnw, int wbf16, float eps, const bf16_t* wgu, bf16_t* s,
                                   int B, int H, int I, hipStream_t st) {
@@ -1456,4 +1581,4 @@ DLT_API int dlt_dec_advance(long* pos, hipStream_t st) {
   k_dec_advance<<<1, 1, 0, st>>>(pos);
   DLT_CHECK_LAUNCH();
 }
-#endif  // DLT_GEGLU_TU
+#endif  // launchers

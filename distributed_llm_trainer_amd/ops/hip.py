@@ -138,6 +138,18 @@ _SIGS = {
     "dlt_gemm_bf16_down_geglu_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                      c_int, c_void_p],
     "dlt_dec_norm_gu_geglu": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
+    # QK-norm and post-norm forms of the decode step (csrc/decode_norms.hip)
+    "dlt_dec_norm_qkv_pn": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                            c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                            c_void_p],
+    "dlt_dec_norm_qkv_qkn": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                             c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "dlt_dec_gemv_out": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
+    "dlt_dec_norm_gu_pn": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                           c_int, c_int, c_int, c_int, c_void_p],
+    "dlt_dec_norm_head_pn": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                             c_void_p, c_float, c_int, c_int, c_int, c_void_p],
 }
 
 
@@ -186,9 +198,42 @@ def _dec_w(t: torch.Tensor, name: str) -> None:
         raise ValueError(f"{name}: expected a contiguous, 16-byte aligned bf16 weight")
 
 
-def dec_norm_qkv(h, ln, eps, wqkv, cos, sin, pos, q_out, kc, vc, nh):
+DEC_LDS_MAX = 160 * 1024  # bytes of LDS per workgroup (dec_lds / dec_lds_qkn in csrc/decode*.hip)
+
+
+def _dec_post(post, h, name: str, need_out: bool = True):
+    """``post=(a, pn_w, h_out)`` of the norm + GEMV decode kernels (their PN forms, a post-norm
+    model): the residual row they norm is ``h + bf16(rmsnorm(a) * pn_w)`` with ``a`` [B, H] bf16 the
+    raw branch :func:`dec_gemv_out` stored, and it is stored to ``h_out`` (fp32 [B, H]; None only
+    where ``need_out`` is False: the head).  ``h_out`` must not overlap ``h``: other workgroups
+    still read ``h`` while the first one stores.  Returns (a, pn_w, is_16bit, h_out)."""
+    if not isinstance(post, (tuple, list)) or len(post) != 3:
+        raise ValueError(f"{name}: post must be (a, pn_w, h_out)")
+    a, pn, h_out = post
+    B, H = h.shape
+    _req(a, torch.bfloat16, f"{name}.post.a", B * H)
+    w, wbf16 = _norm_weight(pn, H, f"{name}.post.pn_w")
+    if a.device != h.device or w.device != h.device:
+        raise ValueError(f"{name}: post tensors must be on {h.device}")
+    if h_out is None:
+        if need_out:
+            raise ValueError(f"{name}: post needs h_out")
+        return a, w, wbf16, None
+    _req(h_out, torch.float32, f"{name}.post.h_out", B * H)
+    if h_out.device != h.device:
+        raise ValueError(f"{name}: post tensors must be on {h.device}")
+    lo, hi = h.data_ptr(), h.data_ptr() + B * H * 4
+    if h_out.data_ptr() < hi and lo < h_out.data_ptr() + B * H * 4:
+        raise ValueError(f"{name}: post h_out must not alias h (workgroups read h while one stores h_out)")
+    return a, w, wbf16, h_out
+
+
+def dec_norm_qkv(h, ln, eps, wqkv, cos, sin, pos, q_out, kc, vc, nh, post=None):
     """h [B, H] fp32 -> RMSNorm -> QKV GEMV -> RoPE; k/v rows written into the caches
-    [B, nh, maxS, 64] at device position ``pos`` (int64 [1]); q (roped, bf16) into q_out."""
+    [B, nh, maxS, 64] at device position ``pos`` (int64 [1]); q (roped, bf16) into q_out.
+    ``post``: see :func:`_dec_post` (None: the call that was always made)."""
+    if post is not None:
+        return dec_norm_qkv_gqa(h, ln, eps, wqkv, cos, sin, pos, q_out, kc, vc, nh, nh, post=post)
     B, H = h.shape
     _req(h, torch.float32, "dec.h", B * H)
     w, wbf16 = _norm_weight(ln, H, "dec.ln1")
@@ -264,9 +309,12 @@ def dec_attn(q, kc, vc, pos, o_out, scale, window=0, sink=None, softcap=None):
          "dec_attn")
 
 
-def dec_norm_qkv_gqa(h, ln, eps, wqkv, cos, sin, pos, q_out, kc, vc, nh, nkv):
+def dec_norm_qkv_gqa(h, ln, eps, wqkv, cos, sin, pos, q_out, kc, vc, nh, nkv, post=None, qk_norm=None):
     """:func:`dec_norm_qkv` for a grouped-query model: wqkv [H + 2 * nkv * 64, H] laid out
-    q | k | v, caches [B, nkv, maxS, 64]; RoPE on the nh query and nkv key heads."""
+    q | k | v, caches [B, nkv, maxS, 64]; RoPE on the nh query and nkv key heads.
+    ``post``: see :func:`_dec_post`.  ``qk_norm=(q_norm, k_norm)``: :func:`dec_norm_qkv_qkn`."""
+    if h.dim() != 2:
+        raise ValueError("dec_norm_qkv_gqa: h must be [B, H]")
     B, H = h.shape
     nkv = _req_nkv(nh, nkv, "dec_norm_qkv_gqa")
     _req(h, torch.float32, "dec.h", B * H)
@@ -280,8 +328,58 @@ def dec_norm_qkv_gqa(h, ln, eps, wqkv, cos, sin, pos, q_out, kc, vc, nh, nkv):
     if (H != nh * 64 or kc.shape != (B, nkv, maxS, 64) or vc.shape != kc.shape
             or wqkv.shape != (H + 2 * nkv * 64, H) or cos.shape[0] < maxS or sin.shape[0] < maxS):
         raise ValueError("dec_norm_qkv_gqa: shape mismatch")
+    if any(t.device != h.device for t in (wqkv, cos, sin, pos, q_out, kc, vc, w)):
+        raise ValueError(f"dec_norm_qkv_gqa: every tensor must be on {h.device}")
+    pa = pw = pbf = ho = None
+    if post is not None:
+        pa, pw, pbf, ho = _dec_post(post, h, "dec_norm_qkv")
+    if qk_norm is not None:
+        _req(cos, torch.float32, "dec.cos")
+        _req(sin, torch.float32, "dec.sin")
+        qn, qbf = _norm_weight(qk_norm[0], 64, "dec.q_norm")
+        kn, kbf = _norm_weight(qk_norm[1], 64, "dec.k_norm")
+        if qbf != kbf or qn.device != h.device or kn.device != h.device:
+            raise ValueError("dec_norm_qkv_qkn: q_norm and k_norm must share a dtype and the device of h")
+        if B not in DECODE_BATCHES or B * H * 2 + B * 16 * 4 + B * 64 * 4 > DEC_LDS_MAX:
+            raise ValueError(f"dec_norm_qkv_qkn: B must be one of {DECODE_BATCHES} and B * H fit the LDS budget")
+        _chk(lib().dlt_dec_norm_qkv_qkn(_p(h), _p(w), wbf16, float(eps), _p(wqkv), _p(qn), _p(kn), qbf, _p(cos),
+                                        _p(sin), _p(pos), _p(q_out), _p(kc), _p(vc), _p(pa), _p(pw), pbf or 0,
+                                        _p(ho), B, H, nh, nkv, maxS, _stream()), "dec_norm_qkv_qkn")
+        return
+    if post is not None:
+        if B not in DECODE_BATCHES or B * H * 2 + B * 4 * 4 + B * 16 * 4 > DEC_LDS_MAX:
+            raise ValueError(f"dec_norm_qkv: B must be one of {DECODE_BATCHES} and B * H fit the LDS budget")
+        _chk(lib().dlt_dec_norm_qkv_pn(_p(h), _p(w), wbf16, float(eps), _p(wqkv), _p(cos), _p(sin), _p(pos),
+                                       _p(q_out), _p(kc), _p(vc), _p(pa), _p(pw), pbf, _p(ho), B, H, nh, nkv, maxS,
+                                       _stream()), "dec_norm_qkv_pn")
+        return
     _chk(lib().dlt_dec_norm_qkv_gqa(_p(h), _p(w), wbf16, float(eps), _p(wqkv), _p(cos), _p(sin), _p(pos), _p(q_out),
                                     _p(kc), _p(vc), B, H, nh, nkv, maxS, _stream()), "dec_norm_qkv_gqa")
+
+
+def dec_norm_qkv_qkn(h, ln, eps, wqkv, qn, kn, cos, sin, pos, q_out, kc, vc, nh, nkv, post=None):
+    """:func:`dec_norm_qkv_gqa` for a QK-norm model (k_dec_norm_qkv_qkn: one workgroup per head):
+    every query / key head's bf16 GEMV output is RMS-normed over its 64 dims in fp32 with
+    ``qn`` / ``kn`` ([64], fp32 or bf16) before RoPE; the cache holds normalised, rotated keys.
+    ``nkv == nh`` is the multi-head layout.  ``post``: see :func:`_dec_post`."""
+    dec_norm_qkv_gqa(h, ln, eps, wqkv, cos, sin, pos, q_out, kc, vc, nh, nkv, post=post, qk_norm=(qn, kn))
+
+
+def dec_gemv_out(x, w, a_out):
+    """a_out = bf16(x @ w^T): the raw branch of a post-norm model (:func:`dec_gemv_res` without the
+    residual add); x [B, K] bf16, w [R, K] bf16, a_out [B, R] bf16."""
+    if x.dim() != 2 or w.dim() != 2:
+        raise ValueError("dec_gemv_out: x must be [B, K] and w [R, K]")
+    B, K = x.shape
+    R = w.shape[0]
+    _req(x, torch.bfloat16, "dec.x", B * K)
+    _dec_w(w, "dec.w")
+    _req(a_out, torch.bfloat16, "dec.a", B * R)
+    if w.shape[1] != K or K % 8 or R < 1 or B not in DECODE_BATCHES or B * K * 2 > DEC_LDS_MAX:
+        raise ValueError("dec_gemv_out: shape mismatch (K % 8 == 0, B a decode batch, B * K within the LDS budget)")
+    if w.device != x.device or a_out.device != x.device:
+        raise ValueError(f"dec_gemv_out: every tensor must be on {x.device}")
+    _chk(lib().dlt_dec_gemv_out(_p(x), _p(w), _p(a_out), B, R, K, _stream()), "dec_gemv_out")
 
 
 DEC_ATTN_SPLITS = (1, 2, 4, 8)  # key chunks per K/V head of dec_attn_gqa
@@ -370,8 +468,9 @@ def dec_gemv_res(x, w, h):
     _chk(lib().dlt_dec_gemv_res(_p(x), _p(w), _p(h), B, R, K, _stream()), "dec_gemv_res")
 
 
-def dec_norm_gu(h, ln, eps, wgu, s_out, activation: str = "swiglu"):
-    """``activation``: the gated MLP's ("swiglu" / "geglu", k_dec_norm_gu's ACT forms)."""
+def dec_norm_gu(h, ln, eps, wgu, s_out, activation: str = "swiglu", post=None):
+    """``activation``: the gated MLP's ("swiglu" / "geglu", k_dec_norm_gu's ACT forms).
+    ``post``: see :func:`_dec_post`."""
     geglu = _geglu(activation, "dec_norm_gu.activation")
     B, H = h.shape
     I = wgu.shape[0] // 2
@@ -379,12 +478,21 @@ def dec_norm_gu(h, ln, eps, wgu, s_out, activation: str = "swiglu"):
     w, wbf16 = _norm_weight(ln, H, "dec.ln2")
     _dec_w(wgu, "dec.wgu")
     _req(s_out, torch.bfloat16, "dec.s", B * I)
+    if post is not None:
+        pa, pw, pbf, ho = _dec_post(post, h, "dec_norm_gu")
+        if (wgu.shape != (2 * I, H) or B not in DECODE_BATCHES or B * H * 2 + B * 4 * 4 + B * 16 * 4 > DEC_LDS_MAX
+                or wgu.device != h.device or s_out.device != h.device):
+            raise ValueError("dec_norm_gu: shape or device mismatch")
+        _chk(lib().dlt_dec_norm_gu_pn(_p(h), _p(w), wbf16, float(eps), _p(wgu), _p(s_out), _p(pa), _p(pw), pbf,
+                                      _p(ho), int(geglu), B, H, I, _stream()), "dec_norm_gu_pn")
+        return
     fn = lib().dlt_dec_norm_gu_geglu if geglu else lib().dlt_dec_norm_gu
     _chk(fn(_p(h), _p(w), wbf16, float(eps), _p(wgu), _p(s_out), B, H, I, _stream()), "dec_norm_gu")
 
 
-def dec_norm_head(h, ln, eps, emb, logits, V, softcap: float = 0.0):
-    """``softcap`` (0 = off): the model's final-logit cap, logits = cap * tanh(logits / cap) (the CAP kernel)."""
+def dec_norm_head(h, ln, eps, emb, logits, V, softcap: float = 0.0, post=None):
+    """``softcap`` (0 = off): the model's final-logit cap, logits = cap * tanh(logits / cap) (the CAP kernel).
+    ``post``: see :func:`_dec_post`; its ``h_out`` may be None (the head stores no residual)."""
     cap = _cap32(softcap, "dec_norm_head.softcap")
     B, H = h.shape
     _req(h, torch.float32, "dec.h", B * H)
@@ -393,6 +501,14 @@ def dec_norm_head(h, ln, eps, emb, logits, V, softcap: float = 0.0):
     _req(logits, torch.float32, "dec.logits", B * V)
     if emb.shape[0] < V or emb.shape[1] != H:
         raise ValueError("dec_norm_head: shape mismatch")
+    if post is not None:
+        pa, pw, pbf, ho = _dec_post(post, h, "dec_norm_head", need_out=False)
+        if (B not in DECODE_BATCHES or B * H * 2 + B * 4 * 4 + B * 16 * 4 > DEC_LDS_MAX
+                or emb.device != h.device or logits.device != h.device):
+            raise ValueError("dec_norm_head: shape or device mismatch")
+        _chk(lib().dlt_dec_norm_head_pn(_p(h), _p(w), wbf16, float(eps), _p(emb), _p(logits), _p(pa), _p(pw), pbf,
+                                        _p(ho), cap, B, H, V, _stream()), "dec_norm_head_pn")
+        return
     if cap != 0.0:
         _chk(lib().dlt_dec_norm_head_cap(_p(h), _p(w), wbf16, float(eps), _p(emb), _p(logits), B, H, V, cap,
                                          _stream()), "dec_norm_head_cap")
