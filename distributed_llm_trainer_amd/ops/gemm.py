@@ -128,9 +128,10 @@ def load_plan(path: str, shipped: bool = False) -> None:
     # one-tile-per-workgroup 4-wave 256 x 256 one with
     # AGPR accumulators (csrc/gemm_fw4.hip; "fw4:<flags>" with its own launch flags), null =
     # hipBLASLt; the
-    # round-2 integer tile configs of the retired gemm_tn kernels read as "library");
+    # round-2 integer tile configs of the retired gemm_tn kernels read as "library"); "r64" = the
+    # 64-granular kernel (csrc/gemm_r64.hip), raced only for shapes neither of the others takes;
     # "fused": "kind:MxNxK" -> fused epilogue picked (older keys without a kind are ignored)
-    _PINNED["tn"] = {tuple(int(x) for x in k.split("x")): (c if c in ("bf16", "fw4") or str(c).startswith("fw4:") else None)
+    _PINNED["tn"] = {tuple(int(x) for x in k.split("x")): (c if c in ("bf16", "fw4", "r64") or str(c).startswith("fw4:") else None)
                      for k, c in plan.get("tn", {}).items()}
     for k, c in plan.get("fused", {}).items():
         if ":" in k:
@@ -384,6 +385,23 @@ class HipGemm:
         return (self._race and x.is_contiguous() and w.is_contiguous() and x.dtype in dtypes
                 and w.dtype == x.dtype and not torch.cuda.is_current_stream_capturing())
 
+    @staticmethod
+    def _tn_candidates(M: int, N: int, K: int):
+        """The hand-written forward kernels raced for a shape: the persistent and the 4-wave
+        kernel where they tile; the 64-granular one only for the shapes neither takes."""
+        from . import hip
+        cands = [name for name, fits in (("bf16", hip.gemm_bf16_fits), ("fw4", hip.gemm_fw4_fits)) if fits(M, N, K)]
+        return cands or (["r64"] if hip.gemm_r64_fits(M, N, K) else [])
+
+    @staticmethod
+    def _dgrad_hand(M: int, Nout: int, Nred: int):
+        """The hand-written data-gradient launcher that fits the shape (what a True "dgrad" /
+        "dgrad16" pick runs), or None: ``hip.gemm_dgrad``, else ``hip.gemm_r64_dgrad``."""
+        from . import hip
+        if hip.gemm_bf16_fits(M, Nout, Nred):
+            return hip.gemm_dgrad
+        return hip.gemm_r64_dgrad if hip.gemm_r64_fits(M, Nout, Nred) else None
+
     def _pick(self, x, w, y):
         """Forward projection race, once per shape: hipBLASLt (None), the persistent
         hand-written kernel ("bf16") or the one-tile-per-workgroup one ("fw4"); a hand-written pick
@@ -397,13 +415,9 @@ class HipGemm:
         choice = None
         t_lib = _time_of(lambda: self._lib_linear(x, w, y))
         best = self.RACE_MARGIN * t_lib
-        cands = []
-        if hip.gemm_bf16_fits(*key):
-            cands.append(("bf16", lambda: hip.gemm_bf16(x, w, out=y)))
-        if hip.gemm_fw4_fits(*key):
-            cands.append(("fw4", lambda: hip.gemm_fw4(x, w, out=y)))
-        for name, fn in cands:
-            t = _time_of(fn)
+        run = {"bf16": hip.gemm_bf16, "fw4": hip.gemm_fw4, "r64": hip.gemm_r64}
+        for name in self._tn_candidates(*key):
+            t = _time_of(lambda: run[name](x, w, out=y))
             if t < best:
                 best, choice = t, name
         self._choice[key] = choice
@@ -420,6 +434,8 @@ class HipGemm:
         if pick == "bf16" and (x.dtype == torch.bfloat16 or self._fp16_hand) and hip.gemm_bf16(x, w, out=y) is not None:
             return y
         if pick == "fw4" and hip.gemm_fw4(x, w, out=y) is not None:
+            return y
+        if pick == "r64" and (x.dtype == torch.bfloat16 or self._fp16_hand) and hip.gemm_r64(x, w, out=y) is not None:
             return y
         if isinstance(pick, str) and pick.startswith("fw4:") and hip.gemm_fw4(x, w, out=y, flags=int(pick[4:])) is not None:
             return y  # "fw4:<flags>": the kernel with its own launch flags (schedule / store flavour)
@@ -500,10 +516,13 @@ class HipGemm:
         return gu, s
 
     def report_choices(self) -> dict:
-        names = {"bf16": "hand-written gemm_bf16 (persistent)", "fw4": "hand-written gemm_fw4"}
+        from . import hip
+        names = {"bf16": "hand-written gemm_bf16 (persistent)", "fw4": "hand-written gemm_fw4",
+                 "r64": "hand-written gemm_r64"}
         out = {f"M{k[0]}xN{k[1]}xK{k[2]}": ("hipBLASLt" if c is None else names.get(c, f"hand-written gemm_{c}"))
                for k, c in self._choice.items() if len(k) == 3}
-        out.update({f"{k[0]} M{k[1]}xN{k[2]}xK{k[3]}": (("hand-written gemm_dgrad" if c else "hipBLASLt")
+        out.update({f"{k[0]} M{k[1]}xN{k[2]}xK{k[3]}": ((("hand-written gemm_r64" if self._dgrad_hand(*k[1:]) is hip.gemm_r64_dgrad
+                                                         else "hand-written gemm_dgrad") if c else "hipBLASLt")
                                                        if k[0].startswith("dgrad") else
                                                        (f"fused gemm_fw4 (flags {c})" if c is not None else "not used")
                                                        if k[0] == "swiglu4" else
@@ -522,20 +541,22 @@ class HipGemm:
         _gemm(0, 0, K, M, N, w, _rowmajor(w), dy, _rowmajor(dy), dx, K)
 
     def linear_dgrad(self, dy: torch.Tensor, w: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
-        """dX[M, K] = dY[M, N] @ W[N, K]: the hand-written reduction-major-B kernel
-        (``hip.gemm_dgrad``, W read as stored) or hipBLASLt, raced once per shape (kind
-        "dgrad" in the plan's "fused" table; ``DLT_GEMM_DGRAD=0``: library only)."""
+        """dX[M, K] = dY[M, N] @ W[N, K]: the hand-written reduction-major-B kernel that fits
+        the shape (``hip.gemm_dgrad``, or ``hip.gemm_r64_dgrad`` where that one does not tile;
+        W read as stored) or hipBLASLt, raced once per shape (kind "dgrad" in the plan's
+        "fused" table; ``DLT_GEMM_DGRAD=0``: library only)."""
         from . import hip
         M, N = dy.shape
         K = w.shape[1]
         dx = torch.empty(M, K, dtype=dy.dtype, device=dy.device) if out is None else out
-        ok = self._dgrad_on and self._race and hip.gemm_bf16_fits(M, K, N) and self._hand16_ok(dy, w, dx)
+        hand = self._dgrad_hand(M, K, N)
+        ok = self._dgrad_on and self._race and hand is not None and self._hand16_ok(dy, w, dx)
         # bf16 and fp16 race separately (kind "dgrad" / "dgrad16"): one format's pick must
         # not decide the other's
         kind = "dgrad" if dy.dtype == torch.bfloat16 else "dgrad16"
-        if ok and self._fused_pick(kind, dy, w, lambda: hip.gemm_dgrad(dy, w, out=dx),
+        if ok and self._fused_pick(kind, dy, w, lambda: hand(dy, w, out=dx),
                                    lambda: self._lib_dgrad(dy, w, dx), key=(kind, M, K, N)):
-            hip.gemm_dgrad(dy, w, out=dx)
+            hand(dy, w, out=dx)
         else:
             self._lib_dgrad(dy, w, dx)
         return dx

@@ -75,6 +75,8 @@ _SIGS = {
                      c_int, c_void_p],
     "dlt_lmhead_loss": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                         c_int, c_int, c_int, c_int, c_void_p],
+    "dlt_gemm_r64": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "dlt_gemm_r64_nn": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "dlt_gemm_bf16_qkv_rope": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                c_void_p],
     "dlt_gemm_bf16_gu_swiglu": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
@@ -2084,6 +2086,48 @@ def gemm_dgrad(dy: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = 
     _req(c, dt, "gemm_dgrad.out", M * Nout)
     _chk(lib().dlt_gemm_bf16_nn(_p(dy), _p(w), _p(c), M, Nout, Nred, Nred, Nout, Nout, _GB_FLAGS, _WG_HK[dt],
                                 _stream()), "gemm_dgrad")
+    return c
+
+
+# ------------------------------------------------- 64-granular GEMM (csrc/gemm_r64.hip)
+def gemm_r64_fits(M: int, N: int, K: int) -> bool:
+    """Shapes k_gemm_r64 takes (N: output columns, K: reduction): 256-row tiles, 128-column
+    tiles plus one 64-column tail tile, any number >= 2 of 64-wide K-tiles."""
+    return M > 0 and N > 0 and M % 256 == 0 and N % 64 == 0 and K % 64 == 0 and K >= 128
+
+
+def gemm_r64(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None,
+             grid: int = 0) -> Optional[torch.Tensor]:
+    """C[M,N] = A[M,K] @ B[N,K]^T (bf16 or fp16 in/out, one format; fp32 accumulate) with the
+    64-granular MFMA kernel.  ``grid``: cap on the workgroups (0: one per tile, at most one per
+    CU); every tile is computed whole by one workgroup, so the result does not depend on it.
+    Returns None (nothing launched) when the shape does not fit (``gemm_r64_fits``)."""
+    M, K = a.shape
+    N = b.shape[0]
+    if not gemm_r64_fits(M, N, K) or b.shape[1] != K:
+        return None
+    hk = _req_act(a, a.dtype, "gemm_r64.a")
+    _req(b, a.dtype, "gemm_r64.b")
+    c = torch.empty(M, N, dtype=a.dtype, device=a.device) if out is None else out
+    _req(c, a.dtype, "gemm_r64.c", M * N)
+    _chk(lib().dlt_gemm_r64(_p(a), _p(b), _p(c), M, N, K, int(grid), hk, _stream()), "gemm_r64")
+    return c
+
+
+def gemm_r64_dgrad(dy: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None,
+                   grid: int = 0) -> Optional[torch.Tensor]:
+    """dX[M, Nout] = dY[M, Nred] @ W[Nred, Nout] with W read as stored, by the 64-granular MFMA
+    kernel's reduction-major-B form; bf16 or fp16 (all three tensors one dtype).  None (nothing
+    launched) when the shape does not fit (``gemm_r64_fits(M, Nout, Nred)``)."""
+    M, Nred = dy.shape
+    Nout = w.shape[1]
+    if not gemm_r64_fits(M, Nout, Nred) or w.shape[0] != Nred:
+        return None
+    hk = _req_act(dy, dy.dtype, "gemm_r64_dgrad.dy")
+    _req(w, dy.dtype, "gemm_r64_dgrad.w")
+    c = torch.empty(M, Nout, dtype=dy.dtype, device=dy.device) if out is None else out
+    _req(c, dy.dtype, "gemm_r64_dgrad.out", M * Nout)
+    _chk(lib().dlt_gemm_r64_nn(_p(dy), _p(w), _p(c), M, Nout, Nred, int(grid), hk, _stream()), "gemm_r64_dgrad")
     return c
 
 
