@@ -157,30 +157,44 @@ def forward_cached(model, ids: torch.Tensor, cache: KVCache) -> torch.Tensor:
     hw = prov.head()
     h = hw.embed.index_select(0, ids.reshape(-1)).float().view(B, T, -1)
     scale = 1.0 / math.sqrt(hd)
+    fused = _prefill_fused(model, T)
     for i in range(cfg.num_layers):
         prov.pre_forward(i)
         w = prov.layer(i)
         n1 = _rms(h, w.ln1, eng.eps).to(dt)
-        q, k, v = _split_qkv(torch.matmul(n1, w.wqkv.t()).float(), cfg)
-        q, k = _qk_norm(q, k, w, eng.eps)
-        q = _rope(q, cos, sin)
-        k = _rope(k, cos, sin)
-        cache.k[i][:, :, p0:p0 + T] = k.transpose(1, 2).to(dt)
-        cache.v[i][:, :, p0:p0 + T] = v.transpose(1, 2).to(dt)
-        K = _rep_kv(cache.k[i][:, :, :p0 + T].float(), cfg)
-        Vv = _rep_kv(cache.v[i][:, :, :p0 + T].float(), cfg)
-        qh = q.to(dt).float().transpose(1, 2)  # [B, nh, T, hd]
-        s = _cap_scores(torch.matmul(qh, K.transpose(-2, -1)) * scale, cfg)
         W = _layer_window(cfg, i)
-        if T > 1 or (W is not None and W < p0 + T):
-            qpos = torch.arange(p0, p0 + T, device=ids.device)[:, None]
-            kpos = torch.arange(0, p0 + T, device=ids.device)[None, :]
-            hidden = kpos > qpos
-            if W is not None:  # sliding window: the keys at or below qpos - W are out
-                hidden = hidden | (kpos <= qpos - W)
-            s = s.masked_fill(hidden, float("-inf"))
-        pr = _sink_softmax(s, w)
-        o = torch.matmul(pr, Vv).transpose(1, 2).reshape(B, T, nh * hd).to(dt)
+        if fused:
+            # HIP prefill (ops/csrc/prefill.hip): the QKV output stays 16-bit and packed; norm, RoPE
+            # and the cache rows in one kernel, flash attention over the cache in the other
+            qkv = torch.matmul(n1, w.wqkv.t()).view(B * T, -1)
+            qn = getattr(w, "qn", None)
+            eng.ops.prefill_qkv_cache(qkv, cache.k[i], cache.v[i], cos_t, sin_t, p0, nh, cfg.num_kv_heads,
+                                      qk_norm=None if qn is None else (qn, w.kn), eps=eng.eps)
+            o = torch.empty(B * T, nh * hd, dtype=dt, device=ids.device)
+            eng.ops.prefill_attn(qkv, cache.k[i], cache.v[i], p0, o, scale, nh, window=W or 0,
+                                 sink=getattr(w, "sk", None), softcap=getattr(cfg, "attn_softcap", None))
+            o = o.view(B, T, nh * hd)
+            del qkv  # dead from here on: not held through the MLP's fp32 temporaries
+        else:
+            q, k, v = _split_qkv(torch.matmul(n1, w.wqkv.t()).float(), cfg)
+            q, k = _qk_norm(q, k, w, eng.eps)
+            q = _rope(q, cos, sin)
+            k = _rope(k, cos, sin)
+            cache.k[i][:, :, p0:p0 + T] = k.transpose(1, 2).to(dt)
+            cache.v[i][:, :, p0:p0 + T] = v.transpose(1, 2).to(dt)
+            K = _rep_kv(cache.k[i][:, :, :p0 + T].float(), cfg)
+            Vv = _rep_kv(cache.v[i][:, :, :p0 + T].float(), cfg)
+            qh = q.to(dt).float().transpose(1, 2)  # [B, nh, T, hd]
+            s = _cap_scores(torch.matmul(qh, K.transpose(-2, -1)) * scale, cfg)
+            if T > 1 or (W is not None and W < p0 + T):
+                qpos = torch.arange(p0, p0 + T, device=ids.device)[:, None]
+                kpos = torch.arange(0, p0 + T, device=ids.device)[None, :]
+                hidden = kpos > qpos
+                if W is not None:  # sliding window: the keys at or below qpos - W are out
+                    hidden = hidden | (kpos <= qpos - W)
+                s = s.masked_fill(hidden, float("-inf"))
+            pr = _sink_softmax(s, w)
+            o = torch.matmul(pr, Vv).transpose(1, 2).reshape(B, T, nh * hd).to(dt)
         h = h + _branch(torch.matmul(o, w.wo.t()), getattr(w, "pn1", None), eng.eps)
         n2 = _rms(h, w.ln2, eng.eps).to(dt)
         gu = torch.matmul(n2, w.wgu.t()).float()
@@ -432,6 +446,23 @@ def _fused_step(model, B: int) -> Optional[FusedStep]:
             return None
     kind = _kind_without_norms(model, B)
     return None if kind is None else FusedStep(kind, qkn, pn)
+
+
+PREFILL_FUSED_MIN_T = 2  # T == 1 is the decode kernels' case (and the ATen reference of their tests)
+
+
+def _prefill_fused(model, T: int) -> bool:
+    """``forward_cached`` runs its attention side on the HIP prefill kernels (``prefill_qkv_cache``
+    / ``prefill_attn``, ops/csrc/prefill.hip) in place of the dense ATen scores: a GPU model whose
+    ops have them, 16-bit activations, head_dim 64 or 128, at least PREFILL_FUSED_MIN_T tokens and
+    ``DLT_PREFILL_FUSED != 0``.  It does not depend on the model's attention features: the
+    kernels have every form the model can combine."""
+    eng = model.engine
+    dev = getattr(eng.provider, "device", None)
+    return (dev is not None and torch.device(dev).type == "cuda" and hasattr(eng.ops, "prefill_attn")
+            and getattr(eng, "act_dtype", None) in (torch.bfloat16, torch.float16)
+            and model.config.head_dim in (64, 128) and T >= PREFILL_FUSED_MIN_T
+            and os.environ.get("DLT_PREFILL_FUSED", "1") != "0")
 
 
 def _fused_kind(model, B: int) -> Optional[str]:

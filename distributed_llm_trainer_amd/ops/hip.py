@@ -152,6 +152,11 @@ _SIGS = {
                            c_int, c_int, c_int, c_int, c_void_p],
     "dlt_dec_norm_head_pn": [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                              c_void_p, c_float, c_int, c_int, c_int, c_void_p],
+    # prefill over the KV cache (csrc/prefill.hip)
+    "dlt_prefill_qkv_cache": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int,
+                              c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "dlt_prefill_attn": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                         c_int, c_int, c_float, c_float, c_int, c_void_p],
 }
 
 
@@ -570,6 +575,88 @@ def dec_sample(logits, temperature, top_k, seed, pos, ids, hist, hist_base, ws=N
 def dec_advance(pos):
     _req(pos, torch.int64, "dec.pos", 1)
     _chk(lib().dlt_dec_advance(_p(pos), _stream()), "dec_advance")
+
+
+# ---------------------------------------------------------------- prefill over the KV cache
+def _prefill_dims(qkv, kc, vc, p0, nh, name: str):
+    """(B, T, nkv, maxS, hd) of a prefill call: ``qkv`` [B*T, (nh + 2*nkv)*hd] packed q | k | v rows
+    of the T tokens appended at cache positions p0 .. p0 + T - 1, caches [B, nkv, maxS, hd]."""
+    if not isinstance(kc, torch.Tensor) or kc.dim() != 4 or vc.shape != kc.shape:
+        raise ValueError(f"{name}: the caches must be two [B, nkv, maxS, hd] tensors of one shape")
+    B, nkv, maxS, hd = kc.shape
+    if hd not in ATTN_HEAD_DIMS:
+        raise ValueError(f"{name}: the caches must be [B, nkv, maxS, hd] with hd in {ATTN_HEAD_DIMS}, got hd {hd}")
+    if isinstance(nh, bool) or not isinstance(nh, int) or nh < 1 or nkv < 1 or nh % nkv:
+        raise ValueError(f"{name}: nkv ({nkv}) must divide nh ({nh})")
+    width = (nh + 2 * nkv) * hd
+    if qkv.dim() != 2 or qkv.shape[1] != width or qkv.shape[0] < B or qkv.shape[0] % B:
+        raise ValueError(f"{name}: qkv must be [B*T, (nh + 2*nkv)*hd] = [{B}*T, {width}], got {list(qkv.shape)}")
+    T = qkv.shape[0] // B
+    if isinstance(p0, bool) or not isinstance(p0, int) or p0 < 0 or p0 + T > maxS:
+        raise ValueError(f"{name}: positions p0 .. p0 + T - 1 = {p0} .. {p0 + T - 1} must lie in the cache "
+                         f"(maxS {maxS})")
+    if qkv.numel() >= 2 ** 31 or maxS * hd * 2 >= 2 ** 32:
+        raise ValueError(f"{name}: the packed buffer or one head's cache rows overflow the kernels' 32-bit index")
+    return B, T, nkv, maxS, hd
+
+
+def _prefill_tensors(qkv, kc, vc, name: str) -> int:
+    hk = _req_act(qkv, qkv.dtype, f"{name}.qkv")
+    _req(kc, qkv.dtype, f"{name}.k_cache")
+    _req(vc, qkv.dtype, f"{name}.v_cache")
+    if kc.device != qkv.device or vc.device != qkv.device:
+        raise ValueError(f"{name}: the caches must be on {qkv.device}")
+    return hk
+
+
+def prefill_qkv_cache(qkv, kc, vc, cos, sin, p0, nh, nkv, qk_norm=None, eps=1e-6):
+    """The packed QKV GEMM output ``qkv`` [B*T, (nh + 2*nkv)*hd] (16-bit) of T tokens appended at
+    cache positions p0 .. p0 + T - 1: every q and k head is rotated (RoPE at its absolute position,
+    tables ``cos`` / ``sin`` fp32 [>= p0 + T, hd/2]), after the RMSNorm over head_dim with
+    ``qk_norm=(q_norm, k_norm)`` ([hd] each, eps ``eps``) when given; q is written back in place,
+    the k and v rows go into ``kc`` / ``vc`` [B, nkv, maxS, hd] at [b, kvh, p0 + t].  fp32 math,
+    one rounding (k_prefill_qkv_cache)."""
+    B, T, nkv_c, maxS, hd = _prefill_dims(qkv, kc, vc, p0, nh, "prefill_qkv_cache")
+    if nkv != nkv_c:
+        raise ValueError(f"prefill_qkv_cache: nkv is {nkv} but the caches hold {nkv_c} heads")
+    if cos.dim() != 2 or cos.shape[0] < p0 + T or cos.shape[1] != hd // 2 or sin.shape != cos.shape:
+        raise ValueError("prefill_qkv_cache: rope tables too short")
+    hk = _prefill_tensors(qkv, kc, vc, "prefill_qkv_cache")
+    _req(cos, torch.float32, "prefill_qkv_cache.cos")
+    _req(sin, torch.float32, "prefill_qkv_cache.sin")
+    qw = kw = None
+    if qk_norm is not None:
+        if not isinstance(qk_norm, (tuple, list)) or len(qk_norm) != 2:
+            raise ValueError("prefill_qkv_cache: qk_norm must be (q_norm, k_norm)")
+        qw = _qknorm_weight(qk_norm[0], hd, "prefill_qkv_cache.q_norm")
+        kw = _qknorm_weight(qk_norm[1], hd, "prefill_qkv_cache.k_norm")
+    _chk(lib().dlt_prefill_qkv_cache(_p(qkv), _p(kc), _p(vc), _p(cos), _p(sin), _p(qw), _p(kw), float(eps), B, T, p0,
+                                     nh, nkv, hd, maxS, hk, _stream()), "prefill_qkv_cache")
+    return qkv
+
+
+def prefill_attn(qkv, kc, vc, p0, o_out, scale, nh, window=0, sink=None, softcap=None):
+    """Flash attention of the T queries in the q columns of ``qkv`` (as :func:`prefill_qkv_cache`
+    left them), at cache positions p0 .. p0 + T - 1, over the rows 0 .. p0 + T - 1 of the caches
+    [B, nkv, maxS, hd]; query head h reads K/V head h // (nh // nkv).  o_out [B*T, nh*hd].
+    ``window`` = W > 0: the query at position q sees the keys q - W < k <= q (W >= p0 + T is no
+    window).  ``sink`` (fp32 [nh]): one more softmax logit per query head with no value row.
+    ``softcap`` = CAP: scores CAP * tanh(scale q.k / CAP), bounded as in :func:`attention_fwd`
+    (k_prefill_attn)."""
+    window = _dec_window(window, "prefill_attn")
+    B, T, nkv, maxS, hd = _prefill_dims(qkv, kc, vc, p0, nh, "prefill_attn")
+    cap = 0.0 if softcap is None else _attn_cap(softcap, "prefill_attn")["softcap"]
+    hk = _prefill_tensors(qkv, kc, vc, "prefill_attn")
+    _req(o_out, qkv.dtype, "prefill_attn.o", B * T * nh * hd)
+    if o_out.device != qkv.device:
+        raise ValueError(f"prefill_attn: o_out must be on {qkv.device}")
+    if sink is not None:
+        sink = _dec_sink(sink, nh, qkv.device, "prefill_attn")
+    if window >= p0 + T:
+        window = 0
+    _chk(lib().dlt_prefill_attn(_p(qkv), _p(kc), _p(vc), _p(o_out), _p(sink), B, T, p0, nh, nkv, hd, maxS, window,
+                                float(scale), cap, hk, _stream()), "prefill_attn")
+    return o_out
 
 
 def _p(t: Optional[torch.Tensor]):
