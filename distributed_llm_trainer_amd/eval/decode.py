@@ -31,13 +31,18 @@ from typing import NamedTuple, Optional
 import torch
 import torch.nn.functional as F
 
-from ..ops.hip import check_top_p_min_p
+from ..ops.hip import KV_FP8, check_top_p_min_p
 
 
 class KVCache:
-    def __init__(self, cfg, B: int, device, dtype):
+    def __init__(self, cfg, B: int, device, dtype, kv_dtype=None):
+        """``kv_dtype`` (None: ``dtype``, the activation dtype): the element type of the cache
+        tensors.  ``torch.float8_e4m3fn`` is the FP8 KV cache, written and read by HIP kernels only (an
+        element is e4m3(clamp(x, -448, 448)) of the value the 16-bit cache would hold): the fused decode
+        step (:class:`DecodeGraph`) runs on one, :func:`forward_cached` does not yet."""
         # grouped-query attention: the cache holds the num_kv_heads K/V heads (not repeated)
-        self.k = [torch.zeros(B, cfg.num_kv_heads, cfg.max_seq_len, cfg.head_dim, device=device, dtype=dtype)
+        self.k = [torch.zeros(B, cfg.num_kv_heads, cfg.max_seq_len, cfg.head_dim, device=device,
+                              dtype=dtype if kv_dtype is None else kv_dtype)
                   for _ in range(cfg.num_layers)]
         self.v = [torch.zeros_like(t) for t in self.k]
         self.len = 0
@@ -158,6 +163,10 @@ def forward_cached(model, ids: torch.Tensor, cache: KVCache) -> torch.Tensor:
     h = hw.embed.index_select(0, ids.reshape(-1)).float().view(B, T, -1)
     scale = 1.0 / math.sqrt(hd)
     fused = _prefill_fused(model, T)
+    if cache.k[0].dtype == KV_FP8:
+        # an FP8 cache is written and read by HIP kernels only, and the prompt's attention has none yet
+        # (ops.prefill_attn); the captured fused step (DecodeGraph) is what runs on one
+        raise NotImplementedError("forward_cached: no prefill attention over an FP8 KV cache yet (DecodeGraph steps only)")
     for i in range(cfg.num_layers):
         prov.pre_forward(i)
         w = prov.layer(i)
@@ -239,6 +248,8 @@ class DecodeGraph:
         # (a grouped-query model: the _gqa forms of the two attention-side kernels; a QK-norm model:
         # dec_norm_qkv_qkn; a post-norm model: dec_gemv_out and the post= forms of the norm kernels)
         step = _fused_step(model, B)
+        if step is None and cache.k[0].dtype == KV_FP8:  # the ATen step cannot read or write e4m3 bytes
+            raise NotImplementedError(f"DecodeGraph: an FP8 KV cache needs the fused HIP step (_fused_step at batch {B})")
         self.kind = step.kind if step is not None else None
         self.qkn = step is not None and step.qk_norm
         self.pn = step is not None and step.post_norm

@@ -41,15 +41,19 @@ def _src_flags(src: str):
 
 
 # wrapper sources: each #includes the named source of its directory
-WRAPPERS = {"decode_norms.hip": "decode.hip"}
+WRAPPERS = {"decode_norms.hip": "decode.hip", "decode_kv8.hip": "decode_norms.hip", "prefill_kv8.hip": "prefill.hip"}
 
 
 def _src_deps(src: str, headers):
-    """Headers plus, for a wrapper ``X_geglu.hip`` (it #includes ``X.hip``) or one of WRAPPERS, that source."""
+    """Headers plus, for a wrapper ``X_geglu.hip`` (it #includes ``X.hip``) or one of WRAPPERS, that
+    source (and, where that is a wrapper too, what it includes)."""
     inc = src[:-len("_geglu.hip")] + ".hip" if src.endswith("_geglu.hip") else None
-    if os.path.basename(src) in WRAPPERS:
-        inc = os.path.join(os.path.dirname(src), WRAPPERS[os.path.basename(src)])
-    return list(headers) + ([inc] if inc and os.path.exists(inc) else [])
+    incs = [inc] if inc and os.path.exists(inc) else []
+    name = os.path.basename(src)
+    while name in WRAPPERS:
+        name = WRAPPERS[name]
+        incs.append(os.path.join(os.path.dirname(src), name))
+    return list(headers) + [i for i in incs if os.path.exists(i)]
 
 
 def hipcc() -> str:

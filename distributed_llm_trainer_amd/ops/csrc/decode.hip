@@ -283,7 +283,9 @@ __device__ __forceinline__ void rows_dot(const bf16_t* const (&wrow)[NR], int K,
 // the 8 NeoX RoPE pairs of a quarter head) of head hb = g / 4 of the packed q | k | v row
 // (nh query heads, then nkv key heads, then nkv value heads; weight rows hb * 64 ..) -- 16
 // rows, 4 per wave, one load round trip.  nkv == nh is the multi-head layout [3H, H].
-template <int B, bool PN = false>
+// F8 (decode_kv8.hip only): kc / vc are e4m3 caches, one byte an element; the row's value is
+// rounded to bf16 exactly as below and then converted (kv_fp8.h kv8_byte).
+template <int B, bool PN = false, bool F8 = false>
 __global__ __launch_bounds__(DEC_NT) void k_dec_norm_qkv(const float* __restrict__ h, const void* __restrict__ lnw,
                                                          int wbf16, float eps, const bf16_t* __restrict__ wqkv,
                                                          const float* __restrict__ cosT, const float* __restrict__ sinT,
@@ -336,6 +338,10 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_norm_qkv(const float* __restrict
     }
     if (blk == 0)
       qout[(size_t)b * H + head * 64 + d] = f2bf(y);
+#ifdef DLT_KV8_TU
+    else if constexpr (F8)
+      reinterpret_cast<uint8_t*>(blk == 1 ? kc : vc)[(((size_t)b * nkv + head) * maxS + pos) * 64 + d] = kv8_byte(bf_round(y));
+#endif
     else
       (blk == 1 ? kc : vc)[(((size_t)b * nkv + head) * maxS + pos) * 64 + d] = f2bf(y);
   }
@@ -1420,6 +1426,12 @@ static int dec_attn_gqa_launch(const bf16_t* q, const bf16_t* kc, const bf16_t* 
   }
 #undef L
   if (NS > 1) k_dec_attn_combine<<<B * nh, 64, 0, st>>>(ws, o, NS, sink, nh);
+  DLT_CHECK_LAUNCH();
+}
+
+// k_dec_attn_combine for decode_kv8.hip, whose FP8 grouped-query kernel writes the same partials
+int dec_attn_combine_launch(const float* ws, bf16_t* o, int B, int nh, int NS, const float* sink, hipStream_t st) {
+  k_dec_attn_combine<<<B * nh, 64, 0, st>>>(ws, o, NS, sink, nh);
   DLT_CHECK_LAUNCH();
 }
 

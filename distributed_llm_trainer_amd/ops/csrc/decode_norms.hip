@@ -25,7 +25,8 @@
 // to bf16: eval/decode.py's _qk_norm, _rope and .to(dt).  V heads skip norm and RoPE.
 // NT per B (qkn_nt): 16 waves hold a wave to 128 VGPRs, which B <= 2 fits; B = 4 takes 8 waves and
 // two passes, B = 8 4 waves and four (no scratch anywhere: profiles/decode_norms.md).
-template <int B, bool PN, int NT>
+// F8 (decode_kv8.hip only): e4m3 caches, as k_dec_norm_qkv's F8 form.
+template <int B, bool PN, int NT, bool F8 = false>
 __global__ __launch_bounds__(NT) void k_dec_norm_qkv_qkn(
     const float* __restrict__ h, const void* __restrict__ lnw, int wbf16, float eps, const bf16_t* __restrict__ wqkv,
     const void* __restrict__ qnw, const void* __restrict__ knw, int qkbf16, const float* __restrict__ cosT,
@@ -83,10 +84,29 @@ __global__ __launch_bounds__(NT) void k_dec_norm_qkv_qkn(
     }
     if (blk == 0)
       qout[(size_t)b * H + head * 64 + d] = f2bf(y);
+#ifdef DLT_KV8_TU
+    else if constexpr (F8)
+      reinterpret_cast<uint8_t*>(blk == 1 ? kc : vc)[(((size_t)b * nkv + head) * maxS + pos) * 64 + d] = kv8_byte(bf_round(y));
+#endif
     else
       (blk == 1 ? kc : vc)[(((size_t)b * nkv + head) * maxS + pos) * 64 + d] = f2bf(y);
   }
 }
+
+// DLT_KV8_TU: this file as included by decode_kv8.hip, which sees the helpers, k_dec_norm_qkv and
+// k_dec_norm_qkv_qkn (for their F8 forms), the two budget functions below and no launcher.
+constexpr int qkn_nt(int B) { return B <= 2 ? 1024 : (B == 4 ? 512 : 256); }
+
+// LDS of k_dec_norm_qkv_qkn: the normed rows, 16 partials and one head's outputs per batch row
+static size_t dec_lds_qkn(int B, int K) { return (size_t)B * K * 2 + (size_t)B * 16 * 4 + (size_t)B * 64 * 4; }
+
+// The post-norm operands of a PN launch: all of pa, pnw set, hout distinct from h (null for the
+// head, which stores no residual).
+static bool dec_pn_ok(const float* h, const bf16_t* pa, const void* pnw, const float* hout) {
+  return pa && pnw && hout != h;
+}
+
+#ifndef DLT_KV8_TU
 
 // a[b][r] = bf16(x[b] . W[r]): k_dec_gemv_res with a store in place of the residual add.
 template <int B>
@@ -115,16 +135,6 @@ __global__ __launch_bounds__(DEC_NT) void k_dec_gemv_out(const bf16_t* __restric
 }
 
 // ------------------------------------------------------------------------ launchers
-constexpr int qkn_nt(int B) { return B <= 2 ? 1024 : (B == 4 ? 512 : 256); }
-
-// LDS of k_dec_norm_qkv_qkn: the normed rows, 16 partials and one head's outputs per batch row
-static size_t dec_lds_qkn(int B, int K) { return (size_t)B * K * 2 + (size_t)B * 16 * 4 + (size_t)B * 64 * 4; }
-
-// The post-norm operands of a PN launch: all of pa, pnw set, hout distinct from h (null for the
-// head, which stores no residual).
-static bool dec_pn_ok(const float* h, const bf16_t* pa, const void* pnw, const float* hout) {
-  return pa && pnw && hout != h;
-}
 
 // dlt_dec_norm_qkv_gqa (nkv == nh: the multi-head layout) with the post-norm prologue.
 DLT_API int dlt_dec_norm_qkv_pn(const float* h, const void* lnw, int wbf16, float eps, const bf16_t* wqkv,
@@ -208,3 +218,4 @@ DLT_API int dlt_dec_norm_head_pn(const float* h, const void* lnw, int wbf16, flo
 #undef L
   DLT_CHECK_LAUNCH();
 }
+#endif  // DLT_KV8_TU

@@ -43,7 +43,10 @@
 // them (head_sum) and the rotation needs no exchange.  fp32 math on the GEMM's rounded output, one
 // rounding -- k_qknorm_rope_inplace / k_rope_qk_inplace at position p0 + t, with the k and v rows
 // stored to the cache instead of in place.
-template <int HK, int D, bool QKN>
+// F8 (prefill_kv8.hip only): kc / vc are e4m3 caches, one byte an element.  The k and v values are
+// the 16-bit ones (k rounded to the activation dtype first), clamped and packed 8 + 8 to 2 x 8
+// bytes (kv_fp8.h kv8_pack8); q is written back in 16 bits as ever.
+template <int HK, int D, bool QKN, bool F8 = false>
 __global__ __launch_bounds__(256) void k_prefill_qkv_cache(bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc,
                                                            bf16_t* __restrict__ vc, const float* __restrict__ cosT,
                                                            const float* __restrict__ sinT,
@@ -74,6 +77,14 @@ __global__ __launch_bounds__(256) void k_prefill_qkv_cache(bf16_t* __restrict__ 
     // the lanes of a head take the same branches below; the butterfly runs before any of them
     const float rstd = QKN ? rsqrtf(head_sum<CPR>(ss) * (1.f / D) + eps) : 1.f;
     if (hh >= nh + nkv) {  // v: the row as it is
+#ifdef DLT_KV8_TU
+      if constexpr (F8) {
+        uint8_t* d8 = reinterpret_cast<uint8_t*>(vc) + (((size_t)b * nkv + (hh - nh - nkv)) * maxS + pos) * D;
+        *reinterpret_cast<uint2*>(d8 + j) = kv8_pack8(x1);
+        *reinterpret_cast<uint2*>(d8 + HALF + j) = kv8_pack8(x2);
+        continue;
+      }
+#endif
       bf16_t* d = vc + (((size_t)b * nkv + (hh - nh - nkv)) * maxS + pos) * D;
       *reinterpret_cast<u16x8*>(d + j) = a;
       *reinterpret_cast<u16x8*>(d + HALF + j) = c;
@@ -104,12 +115,31 @@ __global__ __launch_bounds__(256) void k_prefill_qkv_cache(bf16_t* __restrict__ 
       o1.v[e] = f2h<HK>(x1[e] * cc[e] - x2[e] * sn[e]);
       o2.v[e] = f2h<HK>(x2[e] * cc[e] + x1[e] * sn[e]);
     }
+#ifdef DLT_KV8_TU
+    if constexpr (F8) {
+      if (hh >= nh) {
+        float y1[8], y2[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          y1[e] = h2f<HK>(o1.v[e]);
+          y2[e] = h2f<HK>(o2.v[e]);
+        }
+        uint8_t* d8 = reinterpret_cast<uint8_t*>(kc) + (((size_t)b * nkv + (hh - nh)) * maxS + pos) * D;
+        *reinterpret_cast<uint2*>(d8 + j) = kv8_pack8(y1);
+        *reinterpret_cast<uint2*>(d8 + HALF + j) = kv8_pack8(y2);
+        continue;
+      }
+    }
+#endif
     bf16_t* d = hh < nh ? p : kc + (((size_t)b * nkv + (hh - nh)) * maxS + pos) * D;
     *reinterpret_cast<u16x8*>(d + j) = o1;
     *reinterpret_cast<u16x8*>(d + HALF + j) = o2;
   }
 }
 
+// DLT_KV8_TU: this file as included by prefill_kv8.hip, which sees k_prefill_qkv_cache (for its F8
+// form) and the argument checks, and neither the attention kernel nor an entry point.
+#ifndef DLT_KV8_TU
 // ============================================================================ attention
 // Eight fp32 values as a 16-bit MFMA operand (round to nearest even), and back.
 template <int HK>
@@ -356,6 +386,7 @@ __global__ __launch_bounds__(NT) ATTN_WAVES(D) void k_prefill_attn(
   }
 }
 
+#endif  // DLT_KV8_TU
 // ============================================================================ C entry points
 // Return codes of the two entry points: 0 = launched; a positive value is the hipError_t of the
 // launch; a negative one names the argument check that failed, and nothing was launched:
@@ -376,6 +407,7 @@ static inline int prefill_check(const void* qkv, const void* kc, const void* vc,
   return 0;
 }
 
+#ifndef DLT_KV8_TU
 // qkv [B*T, (nh + 2 nkv) * hd] (q | k | v), kc / vc [B, nkv, maxS, hd], cosT / sinT fp32
 // [>= p0 + T, hd / 2]; qw, kw: fp32 [hd], both (QK-norm) or neither
 DLT_API int dlt_prefill_qkv_cache(bf16_t* qkv, bf16_t* kc, bf16_t* vc, const float* cosT, const float* sinT,
@@ -415,3 +447,4 @@ DLT_API int dlt_prefill_attn(const bf16_t* qkv, const bf16_t* kc, const bf16_t* 
               qkv, kc, vc, o, sink, T, p0, nh, nkv, G, maxS, W, c_log2, cap_k)))))));
   DLT_CHECK_LAUNCH();
 }
+#endif  // DLT_KV8_TU

@@ -158,6 +158,31 @@ _SIGS = {
     "dlt_prefill_attn": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                          c_int, c_int, c_float, c_float, c_int, c_void_p],
 }
+# FP8 (e4m3) KV cache forms (csrc/decode_kv8.hip, prefill_kv8.hip): one entry covers the forms of its
+# 16-bit family, with the arguments of the family's fullest member
+_SIGS.update({
+    "dlt_dec_norm_qkv_kv8": _SIGS["dlt_dec_norm_qkv_pn"],
+    "dlt_dec_norm_qkv_qkn_kv8": _SIGS["dlt_dec_norm_qkv_qkn"],
+    "dlt_dec_attn_kv8": _SIGS["dlt_dec_attn_cap"],
+    "dlt_dec_attn_gqa_kv8": _SIGS["dlt_dec_attn_gqa_cap"],
+    "dlt_prefill_qkv_cache_kv8": _SIGS["dlt_prefill_qkv_cache"],
+})
+KV_FP8 = torch.float8_e4m3fn  # the cache dtype that selects them
+
+
+def _kv8(kc, vc, name: str, hds=(64,)) -> bool:
+    """True where the caches are an FP8 (e4m3) KV cache: every wrapper that touches the cache asks
+    this before anything else and launches the FP8 form of its kernel.  kc and vc must share a
+    dtype; an FP8 cache needs a head_dim of ``hds``.  False: a 16-bit cache takes the path it took."""
+    if kc.dtype != vc.dtype:
+        raise TypeError(f"{name}: k_cache is {kc.dtype} but v_cache is {vc.dtype}")
+    if kc.dtype != KV_FP8:
+        return False
+    if kc.dim() != 4 or kc.shape[3] not in hds or vc.shape != kc.shape:
+        raise ValueError(f"{name}: an FP8 cache must be [B, nkv, maxS, hd] with hd in {hds}")
+    _req(kc, KV_FP8, f"{name}.k_cache")
+    _req(vc, KV_FP8, f"{name}.v_cache")
+    return True
 
 
 def library_path() -> str:
@@ -239,7 +264,7 @@ def dec_norm_qkv(h, ln, eps, wqkv, cos, sin, pos, q_out, kc, vc, nh, post=None):
     """h [B, H] fp32 -> RMSNorm -> QKV GEMV -> RoPE; k/v rows written into the caches
     [B, nh, maxS, 64] at device position ``pos`` (int64 [1]); q (roped, bf16) into q_out.
     ``post``: see :func:`_dec_post` (None: the call that was always made)."""
-    if post is not None:
+    if post is not None or _kv8(kc, vc, "dec_norm_qkv"):  # an FP8 cache: the grouped form's FP8 kernels, nkv = nh
         return dec_norm_qkv_gqa(h, ln, eps, wqkv, cos, sin, pos, q_out, kc, vc, nh, nh, post=post)
     B, H = h.shape
     _req(h, torch.float32, "dec.h", B * H)
@@ -283,10 +308,23 @@ def dec_attn(q, kc, vc, pos, o_out, scale, window=0, sink=None, softcap=None):
     ``softcap`` = CAP (finite, > 0): the scores are CAP * tanh(scale q.k / CAP) (the CAP kernels;
     the sink is not capped).  None: the call is what it was."""
     window = _dec_window(window, "dec_attn")
+    if kc.dim() != 4:
+        raise ValueError("dec_attn: caches must be [B, nh, maxS, 64]")
+    f8 = _kv8(kc, vc, "dec_attn")
     B, nh, maxS, hd = kc.shape
     H = nh * hd
     _req(q, torch.bfloat16, "dec.q", B * H)
     _req(o_out, torch.bfloat16, "dec.o", B * H)
+    if f8:  # k_dec_attn_f8: window 0 = none, a null sink = none, cap 0 = none
+        _req(pos, torch.int64, "dec.pos", 1)
+        if q.device != kc.device or o_out.device != kc.device or pos.device != kc.device:
+            raise ValueError(f"dec_attn: every tensor must be on {kc.device}")
+        cap = 0.0 if softcap is None else _score_cap(softcap, "dec_attn.softcap")
+        if sink is not None:
+            sink = _dec_sink(sink, nh, kc.device, "dec_attn")
+        _chk(lib().dlt_dec_attn_kv8(_p(q), _p(kc), _p(vc), _p(pos), _p(o_out), B, H, nh, maxS, float(scale), window,
+                                    _p(sink), cap, _stream()), "dec_attn_kv8")
+        return
     if sink is not None or softcap is not None:
         cap = None if softcap is None else _score_cap(softcap, "dec_attn.softcap")
         if sink is not None:
@@ -324,13 +362,14 @@ def dec_norm_qkv_gqa(h, ln, eps, wqkv, cos, sin, pos, q_out, kc, vc, nh, nkv, po
         raise ValueError("dec_norm_qkv_gqa: h must be [B, H]")
     B, H = h.shape
     nkv = _req_nkv(nh, nkv, "dec_norm_qkv_gqa")
+    f8 = _kv8(kc, vc, "dec_norm_qkv_gqa")  # an FP8 cache: the F8 forms of the same kernels
     _req(h, torch.float32, "dec.h", B * H)
     w, wbf16 = _norm_weight(ln, H, "dec.ln1")
     _dec_w(wqkv, "dec.wqkv")
     _req(q_out, torch.bfloat16, "dec.q", B * H)
     _req(pos, torch.int64, "dec.pos", 1)
-    _req(kc, torch.bfloat16, "dec.k_cache")
-    _req(vc, torch.bfloat16, "dec.v_cache")
+    _req(kc, KV_FP8 if f8 else torch.bfloat16, "dec.k_cache")
+    _req(vc, KV_FP8 if f8 else torch.bfloat16, "dec.v_cache")
     maxS = kc.shape[2] if kc.dim() == 4 else -1
     if (H != nh * 64 or kc.shape != (B, nkv, maxS, 64) or vc.shape != kc.shape
             or wqkv.shape != (H + 2 * nkv * 64, H) or cos.shape[0] < maxS or sin.shape[0] < maxS):
@@ -349,9 +388,16 @@ def dec_norm_qkv_gqa(h, ln, eps, wqkv, cos, sin, pos, q_out, kc, vc, nh, nkv, po
             raise ValueError("dec_norm_qkv_qkn: q_norm and k_norm must share a dtype and the device of h")
         if B not in DECODE_BATCHES or B * H * 2 + B * 16 * 4 + B * 64 * 4 > DEC_LDS_MAX:
             raise ValueError(f"dec_norm_qkv_qkn: B must be one of {DECODE_BATCHES} and B * H fit the LDS budget")
-        _chk(lib().dlt_dec_norm_qkv_qkn(_p(h), _p(w), wbf16, float(eps), _p(wqkv), _p(qn), _p(kn), qbf, _p(cos),
-                                        _p(sin), _p(pos), _p(q_out), _p(kc), _p(vc), _p(pa), _p(pw), pbf or 0,
-                                        _p(ho), B, H, nh, nkv, maxS, _stream()), "dec_norm_qkv_qkn")
+        fn = lib().dlt_dec_norm_qkv_qkn_kv8 if f8 else lib().dlt_dec_norm_qkv_qkn
+        _chk(fn(_p(h), _p(w), wbf16, float(eps), _p(wqkv), _p(qn), _p(kn), qbf, _p(cos), _p(sin), _p(pos), _p(q_out),
+                _p(kc), _p(vc), _p(pa), _p(pw), pbf or 0, _p(ho), B, H, nh, nkv, maxS, _stream()), "dec_norm_qkv_qkn")
+        return
+    if f8:  # one entry for the plain and the post-norm form
+        if B not in DECODE_BATCHES or B * H * 2 + B * 4 * 4 + B * 16 * 4 > DEC_LDS_MAX:
+            raise ValueError(f"dec_norm_qkv: B must be one of {DECODE_BATCHES} and B * H fit the LDS budget")
+        _chk(lib().dlt_dec_norm_qkv_kv8(_p(h), _p(w), wbf16, float(eps), _p(wqkv), _p(cos), _p(sin), _p(pos),
+                                        _p(q_out), _p(kc), _p(vc), _p(pa), _p(pw), pbf or 0, _p(ho), B, H, nh, nkv,
+                                        maxS, _stream()), "dec_norm_qkv_kv8")
         return
     if post is not None:
         if B not in DECODE_BATCHES or B * H * 2 + B * 4 * 4 + B * 16 * 4 > DEC_LDS_MAX:
@@ -432,10 +478,11 @@ def dec_attn_gqa(q, kc, vc, pos, o_out, scale, nh, splits=1, ws=None, window=0, 
     if splits not in DEC_ATTN_SPLITS:
         raise ValueError(f"dec_attn_gqa: splits must be one of {DEC_ATTN_SPLITS}")
     H = nh * 64
+    f8 = _kv8(kc, vc, "dec_attn_gqa")
     _req(q, torch.bfloat16, "dec.q", B * H)
     _req(o_out, torch.bfloat16, "dec.o", B * H)
-    _req(kc, torch.bfloat16, "dec.k_cache")
-    _req(vc, torch.bfloat16, "dec.v_cache")
+    _req(kc, KV_FP8 if f8 else torch.bfloat16, "dec.k_cache")
+    _req(vc, KV_FP8 if f8 else torch.bfloat16, "dec.v_cache")
     _req(pos, torch.int64, "dec.pos", 1)
     if splits > 1:
         if ws is None:
@@ -443,6 +490,14 @@ def dec_attn_gqa(q, kc, vc, pos, o_out, scale, nh, splits=1, ws=None, window=0, 
         _req(ws, torch.float32, "dec.attn_ws", B * nh * splits * DEC_ATTN_WS)
     if sink is not None:
         sink = _dec_sink(sink, nh, kc.device, "dec_attn_gqa")
+    if f8:  # k_dec_attn_gqa_f8: window 0 = none, a null sink = none, cap 0 = none
+        if q.device != kc.device or o_out.device != kc.device or pos.device != kc.device:
+            raise ValueError(f"dec_attn_gqa: every tensor must be on {kc.device}")
+        cap = 0.0 if softcap is None else _score_cap(softcap, "dec_attn_gqa.softcap")
+        _chk(lib().dlt_dec_attn_gqa_kv8(_p(q), _p(kc), _p(vc), _p(pos), _p(o_out), _p(ws if splits > 1 else None), B,
+                                        H, nh, nkv, maxS, splits, float(scale), window, _p(sink), cap, _stream()),
+             "dec_attn_gqa_kv8")
+        return
     if softcap is not None:  # the CAP kernels: window 0 = none, a null sink = none
         cap = _score_cap(softcap, "dec_attn_gqa.softcap")
         _chk(lib().dlt_dec_attn_gqa_cap(_p(q), _p(kc), _p(vc), _p(pos), _p(o_out), _p(ws if splits > 1 else None), B,
@@ -600,10 +655,10 @@ def _prefill_dims(qkv, kc, vc, p0, nh, name: str):
     return B, T, nkv, maxS, hd
 
 
-def _prefill_tensors(qkv, kc, vc, name: str) -> int:
+def _prefill_tensors(qkv, kc, vc, name: str, f8: bool = False) -> int:
     hk = _req_act(qkv, qkv.dtype, f"{name}.qkv")
-    _req(kc, qkv.dtype, f"{name}.k_cache")
-    _req(vc, qkv.dtype, f"{name}.v_cache")
+    _req(kc, KV_FP8 if f8 else qkv.dtype, f"{name}.k_cache")
+    _req(vc, KV_FP8 if f8 else qkv.dtype, f"{name}.v_cache")
     if kc.device != qkv.device or vc.device != qkv.device:
         raise ValueError(f"{name}: the caches must be on {qkv.device}")
     return hk
@@ -617,11 +672,12 @@ def prefill_qkv_cache(qkv, kc, vc, cos, sin, p0, nh, nkv, qk_norm=None, eps=1e-6
     the k and v rows go into ``kc`` / ``vc`` [B, nkv, maxS, hd] at [b, kvh, p0 + t].  fp32 math,
     one rounding (k_prefill_qkv_cache)."""
     B, T, nkv_c, maxS, hd = _prefill_dims(qkv, kc, vc, p0, nh, "prefill_qkv_cache")
+    f8 = _kv8(kc, vc, "prefill_qkv_cache", (64, 128))  # an FP8 cache: the kernel's F8 form
     if nkv != nkv_c:
         raise ValueError(f"prefill_qkv_cache: nkv is {nkv} but the caches hold {nkv_c} heads")
     if cos.dim() != 2 or cos.shape[0] < p0 + T or cos.shape[1] != hd // 2 or sin.shape != cos.shape:
         raise ValueError("prefill_qkv_cache: rope tables too short")
-    hk = _prefill_tensors(qkv, kc, vc, "prefill_qkv_cache")
+    hk = _prefill_tensors(qkv, kc, vc, "prefill_qkv_cache", f8)
     _req(cos, torch.float32, "prefill_qkv_cache.cos")
     _req(sin, torch.float32, "prefill_qkv_cache.sin")
     qw = kw = None
@@ -630,8 +686,9 @@ def prefill_qkv_cache(qkv, kc, vc, cos, sin, p0, nh, nkv, qk_norm=None, eps=1e-6
             raise ValueError("prefill_qkv_cache: qk_norm must be (q_norm, k_norm)")
         qw = _qknorm_weight(qk_norm[0], hd, "prefill_qkv_cache.q_norm")
         kw = _qknorm_weight(qk_norm[1], hd, "prefill_qkv_cache.k_norm")
-    _chk(lib().dlt_prefill_qkv_cache(_p(qkv), _p(kc), _p(vc), _p(cos), _p(sin), _p(qw), _p(kw), float(eps), B, T, p0,
-                                     nh, nkv, hd, maxS, hk, _stream()), "prefill_qkv_cache")
+    fn = lib().dlt_prefill_qkv_cache_kv8 if f8 else lib().dlt_prefill_qkv_cache
+    _chk(fn(_p(qkv), _p(kc), _p(vc), _p(cos), _p(sin), _p(qw), _p(kw), float(eps), B, T, p0, nh, nkv, hd, maxS, hk,
+            _stream()), "prefill_qkv_cache")
     return qkv
 
 
@@ -645,6 +702,8 @@ def prefill_attn(qkv, kc, vc, p0, o_out, scale, nh, window=0, sink=None, softcap
     (k_prefill_attn)."""
     window = _dec_window(window, "prefill_attn")
     B, T, nkv, maxS, hd = _prefill_dims(qkv, kc, vc, p0, nh, "prefill_attn")
+    if _kv8(kc, vc, "prefill_attn", (64, 128)):  # no silent detour through a 16-bit copy
+        raise NotImplementedError("prefill_attn: there is no prefill attention kernel over an FP8 (e4m3) KV cache yet")
     cap = 0.0 if softcap is None else _attn_cap(softcap, "prefill_attn")["softcap"]
     hk = _prefill_tensors(qkv, kc, vc, "prefill_attn")
     _req(o_out, qkv.dtype, "prefill_attn.o", B * T * nh * hd)
